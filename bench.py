@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark of the demod_2400 hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sparse|dense|stream|shard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sparse|dense|stream|shard] [--dump-outputs DIR]
 
 A step = one pass of the hot path over one 256 MiB synthetic 2.4 MSPS i16 IQ buffer (512
 131072-sample buffers) that is already resident in HBM: ONE icao_flush per step, then what the
@@ -104,7 +104,13 @@ def parse(argv=None):
     ap.add_argument("--sync", action="store_true",
                     help="one blocking adsb_demod_iq_device call per step instead of the "
                          "submit/collect pipeline")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="sparse / dense workloads: after the timed steps, write the message list of the last timed "
+                         "step (rank 0's) as DIR/<field>.npy, float32 / float64, at most 64 MB in all (dump_messages)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.workload not in ("sparse", "dense"):
+        ap.error("--dump-outputs: the sparse and dense workloads only")
+    return args
 
 
 def self_launch(args) -> int:
@@ -160,6 +166,35 @@ def _cpu_quota():
         return None if q <= 0 else q / per
     except (OSError, ValueError):
         return None
+
+
+DUMP_MAX_BYTES = 64 << 20
+# field of adsb_msg -> (file name, dtype written); every value is exact in its dtype
+DUMP_FIELDS = (("msg", "msg", "float32"), ("len", "msglen", "float32"), ("try_phase", "try_phase", "float32"),
+               ("score", "score", "float64"), ("j", "j", "float64"), ("chunk", "chunk", "float64"),
+               ("signal_level", "signal_level", "float64"))
+
+
+def dump_messages(dirpath, msgs, seed: int = 0) -> dict:
+    """--dump-outputs: one step's messages (a numpy view of adsb_msg entries, in the order the caller receives
+    them) as DIR/<field>.npy, one row per message, plus index.npy = each row's position in the list.  Above
+    DUMP_MAX_BYTES in all, a fixed seeded sample of the rows, in ascending order."""
+    import numpy as np
+
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    n = len(msgs)
+    row_bytes = 8 + sum(np.dtype(dt).itemsize * int(np.prod(msgs.dtype[f].shape, dtype=np.int64))
+                        for f, _, dt in DUMP_FIELDS)
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(seed).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+    arrays = {name: msgs[f][rows].astype(dt) for f, name, dt in DUMP_FIELDS}
+    arrays["index"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    return {"dir": str(d), "messages": n, "rows": len(rows), "files": sorted(f"{k}.npy" for k in arrays),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def _same(got, want) -> bool:
@@ -273,10 +308,13 @@ class Env:
             self.dist.destroy_process_group()
 
 
-def run_resident(env: Env, args, workload: str, steps: int, warmup: int, level2: bool = True, short_block: int = 0):
+def run_resident(env: Env, args, workload: str, steps: int, warmup: int, level2: bool = True, short_block: int = 0,
+                 keep_last: bool = False):
     """The device-resident pass loop (BASELINE configs 2 and 5).  Returns a dict of raw numbers and
-    keeps the context / buffers alive in it for the parity leg."""
+    keeps the context / buffers alive in it for the parity leg (`keep_last`: and a copy of the last
+    timed step's messages, "last_step_msgs")."""
     torch = env.torch
+    import numpy as np
     from dump1090_rs_amd import Context, synth
     from dump1090_rs_amd._lib import AdsbMsg
 
@@ -291,6 +329,7 @@ def run_resident(env: Env, args, workload: str, steps: int, warmup: int, level2:
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
     cap = 1 << 20
     out = (AdsbMsg * cap)()
+    last = [0]   # messages of the last step collected (every collect fills `out` from its start)
     depth = max(1, min(4, args.depth))
 
     def run_steps(first: int, count: int, level: int, blocking: bool = args.sync):
@@ -313,16 +352,19 @@ def run_resident(env: Env, args, workload: str, steps: int, warmup: int, level2:
             b = bufs[(first + i) % len(bufs)]
             ctx.icao_flush()
             if blocking:
-                frames += ctx.demod_iq_device_raw(b.data_ptr(), n, out, cap)
+                last[0] = ctx.demod_iq_device_raw(b.data_ptr(), n, out, cap)
+                frames += last[0]
                 account()
             else:
                 ctx.submit_iq_device(b.data_ptr(), n)
                 if i >= depth - 1:
-                    frames += ctx.collect_raw(out, cap)
+                    last[0] = ctx.collect_raw(out, cap)
+                    frames += last[0]
                     account()
         if not blocking:
             for _ in range(min(count, depth - 1)):
-                frames += ctx.collect_raw(out, cap)
+                last[0] = ctx.collect_raw(out, cap)
+                frames += last[0]
                 account()
         return frames, tot, stamps
 
@@ -343,6 +385,8 @@ def run_resident(env: Env, args, workload: str, steps: int, warmup: int, level2:
     frames, tot, stamps = run_steps(warmup, steps, args.timed_profiling)
     env.fence()
     elapsed = time.perf_counter() - t0
+    # (what the timed path gave its caller in its last step, before the blocks below overwrite `out`)
+    last_msgs = np.ctypeslib.as_array(out)[:last[0]].copy() if keep_last else None
     # The spread: the same K steps again, block after block, each between the same fences.  Not the
     # headline (that is the block above, as the driver's contract wants it) -- what one 2 ms sample cannot
     # say about itself.
@@ -379,7 +423,8 @@ def run_resident(env: Env, args, workload: str, steps: int, warmup: int, level2:
     iv = [b - a for a, b in zip(stamps, stamps[1:])]
     return {"ctx": ctx, "bufs": bufs, "n": n, "n_bursts": n_bursts, "cap": cap, "frames": frames, "elapsed": elapsed,
             "tot": tot, "tot2": tot2, "stats": stats, "intervals": iv, "depth": depth, "ramp": ramp,
-            "alone_ms": alone_ms, "blocks": blocks, "short_block_ms": short_ms}
+            "alone_ms": alone_ms, "blocks": blocks, "short_block_ms": short_ms, "last_step_msgs": last_msgs,
+            "last_step_buffer": (warmup + steps - 1) % len(bufs)}
 
 
 def clock_ramp(env: Env, args, run) -> dict:
@@ -1560,8 +1605,12 @@ def main():
     elif args.workload == "shard":
         result = run_shard(env, args)
     else:
-        r = run_resident(env, args, args.workload, args.steps, args.warmup)
+        dump = bool(args.dump_outputs) and env.rank == 0
+        r = run_resident(env, args, args.workload, args.steps, args.warmup, keep_last=dump)
         result = resident_result(env, args, r, args.workload)
+        if dump:
+            result["outputs_dumped"] = {**dump_messages(args.dump_outputs, r["last_step_msgs"]),
+                                        "step": args.warmup + args.steps - 1, "buffer": r["last_step_buffer"]}
         if env.rank == 0 and not args.no_cpu_baseline:
             # N = 1: the CPU baseline beside the line; N > 1: the parity gate alone (rank 0's buffer 0
             # against the oracle), so that the line verifies itself wherever the driver runs it

@@ -5,7 +5,7 @@ src/icao_filter.rs:8-9).  An adsb_multi cuts a capture into contiguous ranges of
 device, runs the two shard phases on a thread per device, unites the learned addresses in memory and replays all
 shards' trial records once through ONE filter.  On the one-GPU test box `devices = [0] * 8` (eight contexts,
 eight threads, one device) stands in for eight GPUs; wherever the box has several devices the same tests run over
-`range(device_count)` as well.  Every result is compared with the CPU oracle over the whole capture AND with the
+`range(device_count)` as well (on a box with one, over more [0] * n forms instead).  Every result is compared with the CPU oracle over the whole capture AND with the
 single-stream GPU result.
 """
 import ctypes as C
@@ -23,12 +23,16 @@ pytestmark = pytest.mark.gpu
 
 
 def device_sets():
-    """[0] * 8 and [0] * 3 always; every real device once, and twice round, when the box has more than one."""
+    """[0] * 8, [0] * 3 and [0] always; then every real device once, twice round and in reverse order when the box
+    has more than one -- and where it has one, three more [0] * n forms in their place: two shards (halves), five
+    (uneven ranges, 8,8,8,7,7 buffers) and sixteen (ranges of three and two buffers, the couplings many shards apart)."""
     import torch
     sets = [[0] * 8, [0] * 3, [0]]
     n = torch.cuda.device_count()
     if n >= 2:
         sets += [list(range(n)), [k % n for k in range(2 * n)], list(range(n - 1, -1, -1))]
+    else:
+        sets += [[0] * 2, [0] * 5, [0] * 16]
     return sets
 
 
@@ -54,10 +58,7 @@ def test_one_capture_over_n_devices_with_a_preloaded_filter_equals_single_stream
     import torch
     from dump1090_rs_amd import Context
     from dump1090_rs_amd.multi import MultiContext
-    sets = device_sets()
-    if which >= len(sets):
-        pytest.skip("one HIP device: the [0] * n forms cover the code, more devices add the placement")
-    devices = sets[which]
+    devices = device_sets()[which]
     iq, pre = coupled_capture8(), preface_capture()
     orc = oracle_mod.Oracle()
     want_pre, _ = orc.demod_iq(pre)

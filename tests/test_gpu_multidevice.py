@@ -4,9 +4,10 @@ run before that day.
 * `bench.py` as ONE rank with the `nccl` backend (= RCCL) forced: process-group init with `device_id`, and every
   collective the bench issues (barrier in the fences, MAX / SUM all-reduce, all-gather of the per-rank step times,
   broadcast of rank 0's loop flag) on real hardware, on the one-GPU box of the driver's GPU suite.
-* everything that takes a device index, on every device BUT 0: skipped (cleanly) on a one-GPU box, run wherever
-  `torch.cuda.device_count() >= 2` -- a context, the ring, a registered host buffer, the shard phases from a
-  worker thread, two devices at once from two threads -- each against the CPU oracle.
+* everything that takes a device index, on every device BUT 0 wherever `torch.cuda.device_count() >= 2` -- a
+  context, the ring, a registered host buffer, the shard phases from a worker thread, every device at once from a
+  thread each -- each against the CPU oracle.  On a one-GPU box the same calls run on device 0 (and two threads
+  share it): the device-selection paths all run, only with nothing for the caller's device to differ from.
 """
 import json
 import os
@@ -92,20 +93,14 @@ def test_bench_one_process_over_all_devices_behind_the_ranks_timed_region(hip_li
 
 # ------------------------------------------------------------------------------------------------ device > 0
 def other_devices():
+    """Every device but 0; on a box with one device, device 0 itself (the same calls and checks)."""
     import torch
-    return list(range(1, torch.cuda.device_count()))
-
-
-def needs_two_devices():
-    import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("one HIP device on this box: the device-index paths beyond 0 run where there are two or more")
+    return list(range(1, torch.cuda.device_count())) or [0]
 
 
 def test_a_context_on_every_other_device_equals_the_oracle(hip_lib, oracle_mod):
     """adsb_create(device = k > 0): blocking host / device-resident calls, the pipelined form, a large pass and
     passes of one buffer -- every launch must land on the context's device whatever the calling thread's is."""
-    needs_two_devices()
     import torch
     from dump1090_rs_amd import Context
     iq = synth.make_iq(20 * CHUNK + 4321, n_bursts=200, seed=8801, n_icao=10, df11_every=4)
@@ -113,7 +108,7 @@ def test_a_context_on_every_other_device_equals_the_oracle(hip_lib, oracle_mod):
     one = iq[3 * CHUNK:4 * CHUNK]
     want_one, _ = oracle_mod.Oracle().demod_iq(one)
     for dev in other_devices():
-        torch.cuda.set_device(0)                      # (the caller's current device is NOT the context's)
+        torch.cuda.set_device(0)                      # (with two devices or more the caller's current device is NOT the context's)
         resident = torch.from_numpy(iq).to(f"cuda:{dev}")
         torch.cuda.synchronize(dev)
         with Context(dev, 32) as c:
@@ -138,7 +133,6 @@ def test_a_context_on_every_other_device_equals_the_oracle(hip_lib, oracle_mod):
 def test_the_ring_and_a_registered_host_buffer_on_every_other_device(hip_lib, oracle_mod):
     """Pinned, mapped host memory is mapped for the context's device: the ring's slots read in place by device k,
     the caller's own registered buffer, slots copied in front of their pass."""
-    needs_two_devices()
     from dump1090_rs_amd import Context
     iq = synth.make_iq(24 * CHUNK, n_bursts=240, seed=8802, n_icao=12, df11_every=5)
     want, _ = oracle_mod.Oracle().demod_iq(iq)
@@ -171,7 +165,6 @@ def test_the_ring_and_a_registered_host_buffer_on_every_other_device(hip_lib, or
 def test_shard_phases_from_a_worker_thread_on_every_other_device(hip_lib, oracle_mod):
     """adsb_shard_scan / adsb_shard_finish called from threads that never touched HIP (their current device is 0)
     on a context of device k: the entry points select the context's device themselves."""
-    needs_two_devices()
     import torch
     from dump1090_rs_amd import Context
     from dump1090_rs_amd.context import replay_records
@@ -194,27 +187,28 @@ def test_shard_phases_from_a_worker_thread_on_every_other_device(hip_lib, oracle
 
 def test_every_device_at_once_from_its_own_thread(hip_lib, oracle_mod):
     """One host thread and one context per device, all demodulating at the same time (each its own stream of
-    buffers, its own filter): what `bench.py --gpus N` does with processes, with threads."""
-    needs_two_devices()
+    buffers, its own filter): what `bench.py --gpus N` does with processes, with threads.  (One device: two threads
+    and two contexts on it.)"""
     import torch
     from dump1090_rs_amd import Context
-    n_dev = torch.cuda.device_count()
-    iqs = [synth.make_iq(12 * CHUNK, n_bursts=100, seed=8810 + d, n_icao=8) for d in range(n_dev)]
+    devs = list(range(torch.cuda.device_count()))
+    devs = devs if len(devs) >= 2 else [0, 0]
+    iqs = [synth.make_iq(12 * CHUNK, n_bursts=100, seed=8810 + k, n_icao=8) for k in range(len(devs))]
     wants = [[want_key(w) for w in oracle_mod.Oracle().demod_iq(iq)[0]] for iq in iqs]
     errors = []
 
-    def worker(d):
+    def worker(k):
         try:
-            with Context(d, 12) as c:
+            with Context(devs[k], 12) as c:
                 for _ in range(5):
                     c.icao_flush()
-                    got = [key(m) for m in c.demod_iq(iqs[d])]
-                    if got != wants[d]:
-                        errors.append((d, "differs"))
+                    got = [key(m) for m in c.demod_iq(iqs[k])]
+                    if got != wants[k]:
+                        errors.append((k, "differs"))
         except Exception as e:   # noqa: BLE001
-            errors.append((d, repr(e)))
+            errors.append((k, repr(e)))
 
-    threads = [threading.Thread(target=worker, args=(d,)) for d in range(n_dev)]
+    threads = [threading.Thread(target=worker, args=(k,)) for k in range(len(devs))]
     for t in threads:
         t.start()
     for t in threads:

@@ -1611,3 +1611,40 @@ def test_bench_line_keeps_the_driver_contract(hip_lib, oracle_mod):
         assert r["parity_checked"] is True and r["parity_frames"] > 0 and r["value"] > 0 and r["steps"] == 4
         assert r["roofline"]["bound"] == "hbm" and r["roofline"]["unit"] == "GB/s" and 0 < r["roofline"]["frac"] < 1
         assert abs(r["roofline"]["achieved"] - 4 * 96 * 131072 / (r["ms_per_step"] * 1e-3) / 1e9) / r["roofline"]["achieved"] < 0.01
+
+
+def test_bench_dump_outputs_are_the_last_timed_steps_messages(tmp_path, oracle_mod):
+    """`bench.py --dump-outputs DIR`: the message list of the last timed step -- step W + K - 1, buffer
+    (W + K - 1) % --buffers of the rotation -- as float .npy files, field for field the CPU oracle's list for
+    that buffer (after icao_flush, as every step starts); twice with the same arguments, the same files."""
+    import json
+    import subprocess
+    import sys
+    from tests.conftest import ROOT
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--chunks", "32",
+                            "--ramp-ms", "0", "--blocks", "1", "--no-also", "--no-cpu-baseline", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["ms_per_step"] > 0
+        od = d["outputs_dumped"]
+        assert (od["step"], od["buffer"], od["rows"], od["dir"]) == (4, 1, od["messages"], str(out))
+        runs.append({f[:-4]: np.load(out / f) for f in od["files"]})
+    a, b = runs
+    assert sorted(a) == ["chunk", "index", "j", "msg", "msglen", "score", "signal_level", "try_phase"]
+    assert all(a[f].dtype in (np.float32, np.float64) for f in a)
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    orc = oracle_mod.Oracle()
+    orc.icao_flush()
+    want, _ = orc.demod_iq(synth.make_iq(32 * 131072, n_bursts=4, seed=synth.SEED_DEFAULT + 1))
+    assert len(want) > 0 and len(a["index"]) == len(want) and a["msg"].shape == (len(want), 14)
+    assert a["index"].tolist() == list(range(len(want)))
+    for f in ("chunk", "j", "try_phase", "score", "signal_level"):
+        assert a[f].tolist() == [w[f] for w in want], f
+    assert a["msglen"].tolist() == [w["len"] for w in want]
+    assert [bytes(row.astype(np.uint8)) for row in a["msg"]] == [w["msg"] for w in want]
