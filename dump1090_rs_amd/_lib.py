@@ -131,6 +131,14 @@ def lib() -> C.CDLL:
     L.adsb_ring_create.argtypes = [vp, sz]
     L.adsb_ring_acquire.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     L.adsb_ring_submit.argtypes = [vp, sz]
+    L.adsb_set_u8_table.argtypes = [vp, vp]
+    L.adsb_to_mag_u8.argtypes = [vp, vp, sz, vp, C.POINTER(sz)]
+    L.adsb_demod_iq_u8.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz)]
+    L.adsb_demod_iq_device_u8.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz)]
+    L.adsb_submit_iq_device_u8.argtypes = [vp, vp, sz]
+    L.adsb_ring_create_u8.argtypes = [vp, sz]
+    L.adsb_ring_acquire_u8.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.adsb_selftest_u8_table.argtypes = [vp, vp]
     L.adsb_read_test_data.argtypes = [C.c_char_p, vp, sz, C.POINTER(sz)]
     L.adsb_get_stats.argtypes = [vp, C.POINTER(AdsbStats)]
     L.adsb_replay_records.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz)]

@@ -71,6 +71,21 @@ def _as_iq(iq) -> np.ndarray:
     return a
 
 
+def _as_cu8(iq) -> np.ndarray:
+    """CU8 input: (N, 2) uint8 rows of [re, im] or flat interleaved bytes (rtl_sdr's I, Q order)."""
+    a = np.asarray(iq)
+    if a.dtype != np.uint8:
+        raise TypeError("CU8 IQ must be a uint8 array")
+    a = np.ascontiguousarray(a)
+    if a.ndim == 1:
+        if a.size % 2:
+            raise ValueError("interleaved CU8 IQ needs an even number of bytes")
+        a = a.reshape(-1, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("CU8 IQ must be (N, 2) uint8 rows of [re, im]")
+    return a
+
+
 # adsb_trial as a numpy record (32 bytes)
 TRIAL_DTYPE = np.dtype([("power", "<u8"), ("chunk", "<u4"), ("j_tp", "<u4"), ("msg", "u1", (14,)), ("pad", "<u2")])
 
@@ -145,6 +160,62 @@ class Context:
         self._check(st, "adsb_to_mag")
         out.length = n.value
         return out
+
+    # -- 8-bit IQ (CU8, an RTL-SDR's samples): each call returns what its CS16 twin returns on the samples widened
+    #    through the context's table (include/adsb_hip.h, "8-bit IQ")
+    def set_u8_table(self, table=None) -> None:
+        """The widening table from now on: 256 int16, or None for T_soapy (a new context's)."""
+        if table is None:
+            self._check(self._L.adsb_set_u8_table(self._h, None), "adsb_set_u8_table")
+            return
+        t = np.ascontiguousarray(table, dtype=np.int16)
+        if t.shape != (256,):
+            raise ValueError("the CU8 table holds 256 int16")
+        self._check(self._L.adsb_set_u8_table(self._h, t.ctypes.data), "adsb_set_u8_table")
+
+    def u8_table(self) -> np.ndarray:
+        """The table the context widens with (adsb_selftest_u8_table)."""
+        out = np.empty(256, dtype=np.int16)
+        self._check(self._L.adsb_selftest_u8_table(self._h, out.ctypes.data), "adsb_selftest_u8_table")
+        return out
+
+    def to_mag_u8(self, iq) -> MagnitudeBuffer:
+        a = _as_cu8(iq)
+        out = MagnitudeBuffer(data=np.empty(MAG_DATA_LEN, dtype=np.uint16))
+        n = C.c_size_t()
+        st = self._L.adsb_to_mag_u8(self._h, a.ctypes.data, a.shape[0], out.data.ctypes.data, C.byref(n))
+        if st == _lib.ADSB_ERR_TOO_LONG:
+            raise IndexError("to_mag_u8: more than 131072 samples (the reference panics here)")
+        self._check(st, "adsb_to_mag_u8")
+        out.length = n.value
+        return out
+
+    def demod_iq_u8(self, iq, cap: Optional[int] = None) -> List[ModeSMessage]:
+        a = _as_cu8(iq)
+        cap = cap or max(4096, a.shape[0] // 256)
+        ptr = a.ctypes.data
+        return self._collect(
+            lambda out, c, n: self._L.adsb_demod_iq_u8(self._h, ptr, a.shape[0], out, c, n), "adsb_demod_iq_u8", cap)
+
+    def demod_iq_device_u8(self, device_ptr: int, n_samples: int, cap: Optional[int] = None) -> List[ModeSMessage]:
+        cap = cap or max(4096, n_samples // 256)
+        return self._collect(
+            lambda out, c, n: self._L.adsb_demod_iq_device_u8(self._h, C.c_void_p(device_ptr), n_samples, out, c, n),
+            "adsb_demod_iq_device_u8", cap)
+
+    def submit_iq_device_u8(self, device_ptr: int, n_samples: int) -> None:
+        self._check(self._L.adsb_submit_iq_device_u8(self._h, C.c_void_p(device_ptr), n_samples),
+                    "adsb_submit_iq_device_u8")
+
+    def ring_create_u8(self, samples_per_slot: int) -> None:
+        self._check(self._L.adsb_ring_create_u8(self._h, samples_per_slot), "adsb_ring_create_u8")
+
+    def ring_acquire_u8(self) -> np.ndarray:
+        """The pinned (capacity, 2) uint8 [re, im] buffer of the next submission of a CU8 ring."""
+        ptr, cap = C.c_void_p(), C.c_size_t()
+        self._check(self._L.adsb_ring_acquire_u8(self._h, C.byref(ptr), C.byref(cap)), "adsb_ring_acquire_u8")
+        buf = (C.c_uint8 * (2 * cap.value)).from_address(ptr.value)
+        return np.ctypeslib.as_array(buf).reshape(-1, 2)
 
     def _collect(self, call, what: str, cap: int) -> List[ModeSMessage]:
         # (the output array is kept between calls: allocating and zeroing 4096 entries costs more than

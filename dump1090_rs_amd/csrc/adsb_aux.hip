@@ -44,6 +44,40 @@ __global__ __launch_bounds__(256) void k_to_mag(const uint32_t *__restrict__ iq,
     }
 }
 
+// The same from CU8 input (adsb_to_mag_u8): a 2-byte sample each through a resource over the n input samples,
+// widened through the table and masked by position -- T[0] is not zero, so the lead-in and tail must not be
+// left to the range check's zero bytes.
+__global__ __launch_bounds__(256) void k_to_mag_u8(const uint8_t *__restrict__ iq, uint32_t n, const uint16_t *__restrict__ tab,
+                                                   uint16_t *__restrict__ data)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t i0 = 8u * t;
+    if (i0 >= (uint32_t)kMagDataLen) return;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)iq, 0, (int)(n * 2u), 0x00020000);
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = load_u8_sample(rsrc, (int)i0 + i - kLead, (int)n, tab);
+    uint32_t pk[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) pk[i] = mag2(w[2 * i], w[2 * i + 1]);
+    if (i0 + 8u <= (uint32_t)kMagDataLen) {
+        *(uint4 *)(data + i0) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+    } else {
+        for (uint32_t i = 0; i0 + i < (uint32_t)kMagDataLen; i++) data[i0 + i] = (uint16_t)(pk[i >> 1] >> (16 * (i & 1)));
+    }
+}
+
+// CU8 samples [first, first + count) widened into CS16 dwords: the overflow fallback's staging (the reference-shaped
+// kernel reads CS16 only)
+__global__ __launch_bounds__(256) void k_widen_u8(const uint8_t *__restrict__ src, unsigned long long first, uint32_t count,
+                                                  const uint16_t *__restrict__ tab, uint32_t *__restrict__ dst)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint8_t *b = src + 2ull * (first + i);
+    dst[i] = widen_u8_pair(tab, (uint32_t)b[0] | (uint32_t)b[1] << 8);
+}
+
 // ---------------------------------------------------------------------------
 // reset: one launch per pass instead of a string of memsets.  Zeroes the counters and,
 // after an icao_flush, the 2 MiB address bitmap; address 0 always tests true
@@ -446,14 +480,14 @@ __global__ __launch_bounds__(256) void k_emit(ScanParams p)
 // kept in HBM), the 112 bits of the trial phase are sliced (demod_2400.rs:158-182) and the 33-sample
 // power summed (:191-196).
 // ---------------------------------------------------------------------------
-template <bool FROM_MAG, bool BUCKETS>
+template <bool FROM_MAG, bool BUCKETS, bool U8 = false>
 __global__ __launch_bounds__(256) void k_records(ScanParams p, TrialRecord *rec)
 {
     if (p.order_cnt) TAIL_PRIO();  // dense streams only: elsewhere the scan is what bounds the step
     // (dynamic LDS, only asked for by device-ordered launches: with 8 KB more a block of a sparse
     // stream's launch held up the next scan's workgroups on its CU -- sparse step +3.6 %)
     extern __shared__ uint64_t sorted[];
-    records_block<FROM_MAG, BUCKETS>(p, rec, blockIdx.x, gridDim.x, sorted, true);
+    records_block<FROM_MAG, BUCKETS, false, U8>(p, rec, blockIdx.x, gridDim.x, sorted, true);
 }
 
 // carry-over mode: the last kCarrySamples samples of the stream so far
@@ -463,6 +497,15 @@ __global__ __launch_bounds__(kCarrySamples) void k_update_carry(const uint32_t *
 {
     const long long i = threadIdx.x, idx = n - kCarrySamples + i;
     next[i] = idx >= 0 ? src[idx] : prev[i + n];
+}
+
+// ... from CU8 input: the carry stays CS16, widened, so that a stream may alternate the two formats
+__global__ __launch_bounds__(kCarrySamples) void k_update_carry_u8(const uint32_t *__restrict__ prev,
+                                                                  const uint8_t *__restrict__ src, long long n,
+                                                                  const uint16_t *__restrict__ tab, uint32_t *__restrict__ next)
+{
+    const long long i = threadIdx.x, idx = n - kCarrySamples + i;
+    next[i] = idx >= 0 ? widen_u8_pair(tab, (uint32_t)src[2 * idx] | (uint32_t)src[2 * idx + 1] << 8) : prev[i + n];
 }
 
 // first phase of a shard that listed its fresh addresses as it scanned (ScanParams::fresh): only the summary is
@@ -521,12 +564,25 @@ inline void hip_clear() { (void)hipGetLastError(); }
 
 }  // namespace
 
-int launch_to_mag(const void *d_iq, uint32_t n, uint16_t *d_data, void *stream)
+int launch_to_mag(const void *d_iq, uint32_t n, uint16_t *d_data, void *stream, const uint16_t *u8_table)
 {
     hip_clear();
     const int blocks = ((kMagDataLen + 7) / 8 + 255) / 256;
+    if (u8_table) {
+        hipLaunchKernelGGL(k_to_mag_u8, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)d_iq, n, u8_table, d_data);
+        return hip_ok(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_to_mag, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (const uint32_t *)d_iq, n, d_data);
+    return hip_ok(hipGetLastError());
+}
+
+int launch_widen_u8(const void *d_src, uint64_t first, uint32_t count, const uint16_t *u8_table, uint32_t *dst, void *stream)
+{
+    hip_clear();
+    if (count == 0) return 0;
+    hipLaunchKernelGGL(k_widen_u8, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)d_src,
+                       (unsigned long long)first, count, u8_table, dst);
     return hip_ok(hipGetLastError());
 }
 
@@ -549,7 +605,7 @@ int launch_match(const ScanParams &p, void *stream)
     return hip_ok(hipGetLastError());
 }
 
-int launch_records(const ScanParams &p, bool from_mag, TrialRecord *d_rec, void *stream)
+int launch_records(const ScanParams &p, SrcFormat fmt, TrialRecord *d_rec, void *stream)
 {
     hip_clear();
     // Contiguous runs of hits per block (the count lives on the device); on sparse input most
@@ -564,7 +620,14 @@ int launch_records(const ScanParams &p, bool from_mag, TrialRecord *d_rec, void 
     // profiles/r5_multi_overhead.txt; beyond 1024 blocks the runs per block simply get longer)
     uint32_t blocks = p.n_chunks + 8u;
     if (blocks > 1024) blocks = 1024;
-    if (from_mag)  // (one caller-supplied buffer: never device-ordered)
+    if (fmt == SrcFormat::kCu8) {
+        if (!p.u8_table) return (int)hipErrorInvalidValue;
+        if (p.order_cnt)
+            hipLaunchKernelGGL((k_records<false, true, true>), dim3(blocks), dim3(256), kOrderBucket * (sizeof(uint64_t) + sizeof(uint16_t)),
+                               (hipStream_t)stream, p, d_rec);
+        else
+            hipLaunchKernelGGL((k_records<false, false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, d_rec);
+    } else if (fmt == SrcFormat::kMag)  // (one caller-supplied buffer: never device-ordered)
         hipLaunchKernelGGL((k_records<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, d_rec);
     else if (p.order_cnt)  // device-ordered: dynamic LDS for the bucket being sorted
         hipLaunchKernelGGL((k_records<false, true>), dim3(blocks), dim3(256), kOrderBucket * (sizeof(uint64_t) + sizeof(uint16_t)),
@@ -607,9 +670,15 @@ int launch_shard_summary(const ScanParams &p, void *stream)
     return hip_ok(hipGetLastError());
 }
 
-int launch_update_carry(const uint32_t *prev, const void *d_src, uint64_t n_samples, uint32_t *next, void *stream)
+int launch_update_carry(const uint32_t *prev, const void *d_src, uint64_t n_samples, uint32_t *next, void *stream,
+                        const uint16_t *u8_table)
 {
     hip_clear();
+    if (u8_table) {
+        hipLaunchKernelGGL(k_update_carry_u8, dim3(1), dim3(kCarrySamples), 0, (hipStream_t)stream, prev,
+                           (const uint8_t *)d_src, (long long)n_samples, u8_table, next);
+        return hip_ok(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_update_carry, dim3(1), dim3(kCarrySamples), 0, (hipStream_t)stream, prev,
                        (const uint32_t *)d_src, (long long)n_samples, next);
     return hip_ok(hipGetLastError());

@@ -232,12 +232,12 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         c->flush_pending = false;
         rc = reseed_bitmap_from_filter(c);
         if (rc == 0)
-            rc = enqueue_pass(c, sl, sl.src, sl.from_mag, sl.n_samples, sl.n_chunks, true, false, false, false,
+            rc = enqueue_pass(c, sl, sl.src, sl.fmt, sl.n_samples, sl.n_chunks, true, false, false, false,
                               input_ready_now(), true);
         if (rc == 0) rc = finish_pass(c, sl, 0, st, out);
         c->flush_pending = keep_flush;
     }
-    if (rc > 0 && sl.from_mag) {  // a caller-supplied buffer denser than the fast scan's lists: again, the slow way
+    if (rc > 0 && sl.fmt == SrcFormat::kMag) {  // a caller-supplied buffer denser than the fast scan's lists: again, the slow way
         st.retries++;
         for (hipStream_t q : c->scan_stream)
             if (q) HIP_TRY(c, hipStreamSynchronize(q));
@@ -248,7 +248,7 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         Slot tmp;
         rc = fallback_slot(c, sl, tmp);
         if (rc == 0) rc = reseed_bitmap_from_filter(c);
-        if (rc == 0) rc = enqueue_pass(c, tmp, sl.src, true, sl.n_samples, 1, false, false, false, true);
+        if (rc == 0) rc = enqueue_pass(c, tmp, sl.src, SrcFormat::kMag, sl.n_samples, 1, false, false, false, true);
         if (rc == 0) rc = finish_pass(c, tmp, 0, st, out);
         c->flush_pending = keep_flush;
     } else if (rc > 0) {
@@ -268,7 +268,23 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
             // (carry-over mode: buffers after the first find their lead-in in src itself; the
             // carry for the next call was already taken when the pass was first enqueued)
             // the reference-shaped kernel: its lists hold the worst case of a chunk
-            rc = enqueue_pass(c, tmp, (const uint32_t *)sl.src + off, false, n, 1, false, ch > 0, false, true);
+            if (sl.fmt == SrcFormat::kCu8) {
+                // ... which reads CS16: the buffer and the lead-in it takes from src, widened into a staging buffer
+                // first (in stream order in front of the pass; the pass is finished before the next buffer's turn)
+                const uint64_t lead = ch > 0 ? kCarrySamples : 0;
+                if (!c->d_widen)
+                    if (hipError_t e = hipMalloc((void **)&c->d_widen, ((size_t)kChunkSamples + kCarrySamples) * sizeof(uint32_t)))
+                        rc = fail(c, e, "hipMalloc");
+                if (rc == 0)
+                    if (int e = launch_widen_u8(sl.src, off - lead, (uint32_t)(n + lead), c->d_u8_table, c->d_widen, c->scan_stream[0]))
+                        rc = fail(c, (hipError_t)e, "launch_widen_u8");
+                if (rc == 0)
+                    if (hipError_t e = hipStreamSynchronize(c->scan_stream[0])) rc = fail(c, e, "hipStreamSynchronize");
+                if (rc == 0)
+                    rc = enqueue_pass(c, tmp, c->d_widen + lead, SrcFormat::kCs16, n, 1, false, ch > 0, false, true);
+            } else {
+                rc = enqueue_pass(c, tmp, (const uint32_t *)sl.src + off, SrcFormat::kCs16, n, 1, false, ch > 0, false, true);
+            }
             if (rc == 0) rc = finish_pass(c, tmp, ch, st, out);
         }
         c->flush_pending = keep_flush;

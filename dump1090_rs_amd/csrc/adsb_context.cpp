@@ -296,6 +296,12 @@ try {
             HIP_TRY(c, hipMemcpy(c->d_tables, tab.data(), tab.size() * sizeof(uint32_t),
                                  hipMemcpyHostToDevice));
         }
+        HIP_TRY(c, hipMalloc((void **)&c->d_u8_table, 256 * sizeof(uint16_t)));
+        {
+            int16_t t[256];
+            soapy_u8_table(t);
+            HIP_TRY(c, hipMemcpy(c->d_u8_table, t, sizeof t, hipMemcpyHostToDevice));
+        }
         for (int si = 0; si < c->n_slots; si++) {
             Slot &sl = c->slot[si];
             // (the slot's summary and records live in the context's one pinned block: mapped + coherent, so the records
@@ -400,6 +406,8 @@ void adsb_destroy(adsb_ctx *c)
     if (c->fb.h_rec) (void)hipHostFree(c->fb.h_rec);
     for (const auto &r : c->host_ranges) (void)hipHostUnregister(r.base);
     if (c->d_tables) (void)hipFree(c->d_tables);
+    if (c->d_u8_table) (void)hipFree(c->d_u8_table);
+    if (c->d_widen) (void)hipFree(c->d_widen);
     if (c->ring_h_block) (void)hipHostFree(c->ring_h_block);
     if (c->ring_d_block) (void)hipFree(c->ring_d_block);
     if (c->d_addrs) (void)hipFree(c->d_addrs);
@@ -551,6 +559,32 @@ try {
         HIP_TRY(c, hipMemsetAsync(c->slot[si].d_carry, 0, kCarrySamples * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_carry_next, 0, kCarrySamples * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_set_u8_table(adsb_ctx *c, const int16_t *table256)
+try {
+    if (!c) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    ADSB_ON_DEVICE(c);
+    int16_t t[256];
+    if (table256) std::memcpy(t, table256, sizeof t);
+    else soapy_u8_table(t);
+    // (nothing is in flight: every pass that read the old table has been collected)
+    HIP_TRY(c, hipMemcpy(c->d_u8_table, t, sizeof t, hipMemcpyHostToDevice));
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_selftest_u8_table(adsb_ctx *c, int16_t *out256)
+try {
+    if (!out256) return ADSB_ERR_INVALID;
+    if (!c) {
+        soapy_u8_table(out256);
+        return ADSB_OK;
+    }
+    if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    ADSB_ON_DEVICE(c);
+    HIP_TRY(c, hipMemcpy(out256, c->d_u8_table, 256 * sizeof(int16_t), hipMemcpyDeviceToHost));
     return ADSB_OK;
 } ADSB_ABI_CATCH
 

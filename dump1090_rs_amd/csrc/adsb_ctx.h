@@ -35,7 +35,7 @@ using namespace adsb;
 struct Slot {
     bool busy = false;
     bool flush_before = false;  // an icao_flush precedes this pass (host filter flushed at collect)
-    bool from_mag = false;
+    SrcFormat fmt = SrcFormat::kCs16;  // what `src` holds
     const void *src = nullptr;
     uint64_t n_samples = 0;
     uint32_t n_chunks = 0;
@@ -174,6 +174,8 @@ struct adsb_ctx {
     bool next_src_host = false;    // ... reads host memory in place (ScanParams::src_host)
     hipEvent_t input_ready[kScanStreams] = {};  // per scan stream: `stream` at submit (the caller's IQ is complete)
     uint32_t *d_tables = nullptr;
+    uint16_t *d_u8_table = nullptr;   // the CU8 widening table, int16_t[256] (adsb_set_u8_table; T_soapy at create)
+    uint32_t *d_widen = nullptr;      // CU8 through the overflow fallback: one buffer and its lead-in widened to CS16 (lazy)
     uint32_t hits_cap = 0, ap_cap = 0, seg_cap = 0;
     // Lists that hold the worst case of one buffer (every position sliced, five trials each), for
     // the buffer-by-buffer fallback through the reference-shaped kernel.  58 MB, most of it pinned
@@ -211,6 +213,7 @@ struct adsb_ctx {
         void *d_iq = nullptr;
     } ring[kSlots];
     size_t ring_samples = 0;
+    SrcFormat ring_fmt = SrcFormat::kCs16;   // adsb_ring_create or adsb_ring_create_u8
     char *ring_h_block = nullptr, *ring_d_block = nullptr;   // all slots' pinned / staging buffers: one allocation each
 
     bool carry_over = false;  // adsb_set_carry_over: opt-in, not the reference's semantics
@@ -366,7 +369,7 @@ int fallback_slot(adsb_ctx *c, const Slot &sl, Slot &tmp);
 inline hipEvent_t input_ready_now() { return reinterpret_cast<hipEvent_t>(static_cast<uintptr_t>(1)); }
 bool one_launch_pass(const adsb_ctx *c, uint32_t n_chunks);
 hipStream_t next_scan_stream(const adsb_ctx *c, uint32_t n_chunks);
-int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, bool from_mag, uint64_t n_samples, uint32_t n_chunks,
+int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64_t n_samples, uint32_t n_chunks,
                  bool inline_tail = false, bool lead_from_src = false, bool advance_carry = true,
                  bool force_simple = false, hipEvent_t input_done = nullptr, bool no_fuse = false);
 int wait_for_tail_of(adsb_ctx *c, hipStream_t waiter, Slot &other);
@@ -377,11 +380,14 @@ int order_behind_fused(adsb_ctx *c, Slot &sl, hipStream_t waiter);
 inline int order_behind_slot0(adsb_ctx *c) { return order_behind_fused(c, c->slot[0], c->stream); }
 int resync_exact(adsb_ctx *c);
 int reseed_bitmap_from_filter(adsb_ctx *c);
-int submit(adsb_ctx *c, const void *d_src, bool from_mag, uint64_t n_samples, bool inline_tail = false,
+int submit(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, bool inline_tail = false,
            hipEvent_t input_done = nullptr);
-int run_sync(adsb_ctx *c, const void *d_src, bool from_mag, uint64_t n_samples, std::vector<adsb_msg> &out,
+int run_sync(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, std::vector<adsb_msg> &out,
              hipEvent_t input_done = nullptr);
-int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<adsb_msg> &out);
+int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<adsb_msg> &out,
+                 SrcFormat fmt = SrcFormat::kCs16);
+// T_soapy: the table SoapyRTLSDR widens an RTL-SDR's bytes with, (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f)
+void soapy_u8_table(int16_t *out256);
 int ensure_stage(adsb_ctx *c, size_t bytes);
 int ensure_host_stage(adsb_ctx *c, size_t bytes);
 

@@ -110,6 +110,25 @@ __device__ __forceinline__ uint2 mag4_of(uint4 v)
     return pk;
 }
 
+// CU8 input (adsb_*_u8): byte 2k is re, byte 2k + 1 im of sample k, each widened through the context's table T
+// (ScanParams::u8_table, int16_t[256]).  Two bytes {re (low), im (high)} -> the CS16 dword {T[re], T[im]}.
+// T[0] is a sample like any other, not zero: every caller masks by sample position, never by value.
+template <typename Tab>
+__device__ __forceinline__ uint32_t widen_u8_pair(const Tab *t, uint32_t b2)
+{
+    return (uint32_t)t[b2 & 0xFFu] | (uint32_t)t[(b2 >> 8) & 0xFFu] << 16;
+}
+
+// Sample s (index in the resource) of a CU8 buffer resource of n_valid samples, widened; 0 outside [0, n_valid)
+// (a negative s wraps to a huge unsigned one and is out of range of the load as well).
+__device__ __forceinline__ uint32_t load_u8_sample(__amdgpu_buffer_rsrc_t rsrc, int s, int n_valid, const uint16_t *t)
+{
+    int off = s * 2;
+    asm volatile("" : "+v"(off));   // (not folded into the immediate: adsb_tail_dev.h, records)
+    const uint32_t b = __builtin_amdgcn_raw_buffer_load_b16(rsrc, off, 0, 0);
+    return (uint32_t)s < (uint32_t)n_valid ? widen_u8_pair(t, b) : 0u;
+}
+
 __device__ __forceinline__ uint2 mag4(const uint32_t *__restrict__ iq, int k, int len)
 {
     return mag4_of(load_iq4(iq, k, len));

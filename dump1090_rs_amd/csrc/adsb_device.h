@@ -260,6 +260,9 @@ struct ScanParams {
     uint32_t src_host;      // one-launch pass: `src` is host memory read in place over the link (its tiles trickle in)
     uint32_t order_polls;   // ... how often a workgroup polls for the tiles before its own before it gives up
                             // (200, ~0.2 ms; the self-test hook sets 0: every tile gives up, the second look decides)
+    // CU8 passes (the U8 instantiations): `src` holds 2 bytes per sample, widened through this int16_t[256] table
+    // in device memory (adsb_set_u8_table).  Last, so that the CS16 instantiations see the layout they always had.
+    const uint16_t *u8_table;
 };
 
 
@@ -292,19 +295,27 @@ constexpr uint32_t kOrderBucket = 1024;
 constexpr uint32_t kTileBucket = 56;   // (x 18 tiles <= kOrderBucket, should the tile ever shrink: adsb_scan_geometry.h)
 constexpr int kCarrySamples = 328;  // kLead rounded up to whole 16-byte loads
 
+// What a pass's `src` holds: caller-supplied magnitudes (adsb_demodulate2400), CS16 IQ ({re, im} int16 pairs) or
+// CU8 IQ ({re, im} bytes, widened through ScanParams::u8_table).  Each is its own kernel instantiation.
+enum class SrcFormat : uint8_t { kMag, kCs16, kCu8 };
+inline uint32_t src_bytes_per_sample(SrcFormat f) { return f == SrcFormat::kCu8 ? 2u : 4u; }
+
 // launches; all asynchronous on `stream`, return a hipError_t as int
-int launch_to_mag(const void *d_iq, uint32_t n, uint16_t *d_data, void *stream);
+// (u8_table: the CU8 widening table, device memory; null for CS16 input)
+int launch_to_mag(const void *d_iq, uint32_t n, uint16_t *d_data, void *stream, const uint16_t *u8_table = nullptr);
+// CU8 samples [first, first + count) of d_src widened into CS16 dwords at dst (the overflow fallback's staging)
+int launch_widen_u8(const void *d_src, uint64_t first, uint32_t count, const uint16_t *u8_table, uint32_t *dst, void *stream);
 // zero a counters block and, when `bitmap` is non-null, clear an address bitmap (bit 0 stays
 // set); only needed once per context: afterwards every pass cleans up for the next one
 int launch_reset(Counters *ctr, uint32_t *bitmap, uint32_t bitmap_lg, void *stream);
-int launch_scan(const ScanParams &p, bool from_mag, void *stream);   // fast (IQ) or simple (mag)
+int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream);   // fast (IQ) or simple (mag)
 // the whole pass in one launch (p.fused_rec set): one workgroup per tile, the last one to finish matches
 // what the pass learned late, builds the records and publishes the summary; for passes of a few buffers
-int launch_pass_fused(const ScanParams &p, bool from_mag, void *stream);
+int launch_pass_fused(const ScanParams &p, SrcFormat fmt, void *stream);
 int scan_resident_blocks();  // workgroups of the fast scan's persistent grid (<= kApSegments)
-int launch_scan_simple(const ScanParams &p, bool from_mag, void *stream);  // reference-shaped path
+int launch_scan_simple(const ScanParams &p, SrcFormat fmt, void *stream);  // reference-shaped path (not CU8: launch_widen_u8 first)
 int launch_match(const ScanParams &p, void *stream);
-int launch_records(const ScanParams &p, bool from_mag, TrialRecord *d_rec, void *stream);
+int launch_records(const ScanParams &p, SrcFormat fmt, TrialRecord *d_rec, void *stream);
 // sort the hit list by (buffer, j, try_phase) on the device, so that the records come out in the
 // order the host replays them in (src/demod_2400.rs:121,158: ascending j, then try_phase)
 int launch_order_hits(const ScanParams &p, void *stream);
@@ -317,8 +328,9 @@ int launch_score(const ScanParams &p, void *stream);
 // OR a list of 24-bit addresses into a bitmap (addresses learned by other shards)
 int launch_set_addresses(const uint32_t *d_addrs, uint32_t n, uint32_t *bitmap, uint32_t bitmap_lg, void *stream);
 // next[i] = sample (n - kCarrySamples + i) of the stream: from d_src, or from `prev` where the
-// call was shorter than the carry
-int launch_update_carry(const uint32_t *prev, const void *d_src, uint64_t n_samples, uint32_t *next, void *stream);
+// call was shorter than the carry.  The carry is always CS16: CU8 input (u8_table set) is widened into it
+int launch_update_carry(const uint32_t *prev, const void *d_src, uint64_t n_samples, uint32_t *next, void *stream,
+                        const uint16_t *u8_table = nullptr);
 int launch_mag_digest(uint32_t first_bits, uint32_t count, unsigned long long *d_out, void *stream);
 
 }  // namespace adsb

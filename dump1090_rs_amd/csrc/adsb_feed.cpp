@@ -4,10 +4,13 @@
 // reference, main.rs:46) so that downstream tools (adsb_deku's radar, anything that speaks
 // the dump1090 raw format) can consume it.
 //
-//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->
+//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--buffers K] [--latency-ms T]
+//             [--readers R] <capture.iq | ->
 //
 // Input is the reference's capture format (src/utils.rs:8-20, save_test_data): little-endian
-// i16 pairs, im first; --mem-order takes {re, im} pairs instead.  The stream is cut into
+// i16 pairs, im first; --mem-order takes {re, im} pairs instead.  --format cu8 takes what rtl_sdr writes
+// (a file or a pipe): unsigned bytes, I then Q, 2 per sample, widened on the device through T_soapy
+// (include/adsb_hip.h, "8-bit IQ"); cs16, the default, is the i16 input above.  The stream is cut into
 // 131072-sample buffers exactly as consecutive SDR reads would be (no carry-over between
 // buffers, src/lib.rs:36-44); up to K of them (default 64) travel to the GPU per pass through the
 // pinned ring (adsb_ring_*), so reading, the copy and the scan overlap.  A slot does not wait to
@@ -270,7 +273,7 @@ private:
 int main(int argc, char **argv)
 {
     int device = 0, port = 0, buffers = 64, latency_ms = 100, out_cap = 0, readers = 4;
-    bool quiet = false, mem_order = false;
+    bool quiet = false, mem_order = false, cu8 = false;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -282,11 +285,17 @@ int main(int argc, char **argv)
         else if (a == "--out-cap" && i + 1 < argc) out_cap = std::atoi(argv[++i]);  // frames the output array starts with (it grows)
         else if (a == "--quiet") quiet = true;
         else if (a == "--mem-order") mem_order = true;
+        else if (a == "--format" && i + 1 < argc) {
+            const std::string f = argv[++i];
+            if (f == "cu8") cu8 = true;
+            else if (f == "cs16") cu8 = false;
+            else path = nullptr, i = argc;
+        }
         else if (a == "--help" || a == "-h") path = nullptr, i = argc;
         else path = argv[i];
     }
     if (!path || buffers < 1) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->\n");
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -305,7 +314,9 @@ int main(int argc, char **argv)
     int st = adsb_create(&ctx, device, (size_t)buffers);
     if (st != ADSB_OK) return die(nullptr, "adsb_create", st);
     const size_t slot_samples = (size_t)buffers * ADSB_MODES_MAG_BUF_SAMPLES;
-    if ((st = adsb_ring_create(ctx, slot_samples)) != ADSB_OK) return die(ctx, "adsb_ring_create", st);
+    if ((st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
+        return die(ctx, "adsb_ring_create", st);
+    const size_t bps = cu8 ? 2 : 4;   // bytes per sample
 
     // a 112 us frame every 120 us would be ~450 per 55 ms buffer; neighbouring preamble
     // positions can each emit one, so leave an order of magnitude of room
@@ -337,19 +348,27 @@ int main(int argc, char **argv)
 
     struct stat sb{};
     const bool regular = in != 0 && ::fstat(in, &sb) == 0 && S_ISREG(sb.st_mode);
-    FileFill file_fill(in, regular ? (readers < 1 ? 1 : readers > 16 ? 16 : readers) : 1, !mem_order);
+    FileFill file_fill(in, regular ? (readers < 1 ? 1 : readers > 16 ? 16 : readers) : 1, !mem_order && !cu8);
     off_t file_at = 0;
 
     const auto t_start = std::chrono::steady_clock::now();
-    const size_t buf_bytes = (size_t)ADSB_MODES_MAG_BUF_SAMPLES * 4;
+    const size_t buf_bytes = (size_t)ADSB_MODES_MAG_BUF_SAMPLES * bps;
     std::vector<char> begun(buf_bytes);  // the buffer a short pass left unfinished: the next slot starts with it
     size_t begun_bytes = 0;
     unsigned long long short_passes = 0;
     bool eof = false;
     while (!eof) {
-        int16_t *buf = nullptr;
+        void *buf = nullptr;
         size_t cap = 0;
-        st = adsb_ring_acquire(ctx, &buf, &cap);
+        if (cu8) {
+            uint8_t *b8 = nullptr;
+            st = adsb_ring_acquire_u8(ctx, &b8, &cap);
+            buf = b8;
+        } else {
+            int16_t *b16 = nullptr;
+            st = adsb_ring_acquire(ctx, &b16, &cap);
+            buf = b16;
+        }
         if (st == ADSB_ERR_BUSY) {  // every slot in flight: finish the oldest first
             if ((st = drain_one()) != ADSB_OK) return die(ctx, "adsb_collect", st);
             continue;
@@ -365,13 +384,13 @@ int main(int argc, char **argv)
         bool have_whole = fill >= buf_bytes;
         auto t_whole = std::chrono::steady_clock::now();
         if (regular) {   // all of it at once, by all the readers, swapped where it lands
-            const size_t got = file_fill.fill(dst, file_at, cap * 4);
+            const size_t got = file_fill.fill(dst, file_at, cap * bps);
             file_at += (off_t)got;
             fill = got;
-            eof = got < cap * 4;
+            eof = got < cap * bps;
             clients.accept_new();
         }
-        while (!regular && !eof && fill < cap * 4) {
+        while (!regular && !eof && fill < cap * bps) {
             int wait_ms = -1;   // nothing to hand on and no whole buffer yet: as long as it takes
             if (have_whole) {
                 const long spent = (long)std::chrono::duration_cast<std::chrono::milliseconds>(
@@ -382,7 +401,7 @@ int main(int argc, char **argv)
                 wait_ms = latency_ms;
             }
             bool idle = false;
-            fill = read_once(in, dst, fill, cap * 4, wait_ms, &eof, &idle);
+            fill = read_once(in, dst, fill, cap * bps, wait_ms, &eof, &idle);
             if (!have_whole && fill >= buf_bytes) {
                 have_whole = true;
                 t_whole = std::chrono::steady_clock::now();
@@ -392,14 +411,14 @@ int main(int argc, char **argv)
                 if ((st = drain_one()) != ADSB_OK) return die(ctx, "adsb_collect", st);
         }
         size_t bytes = fill;
-        if (!eof && fill < cap * 4) {  // short pass: whole buffers only, the begun one waits for its rest
+        if (!eof && fill < cap * bps) {  // short pass: whole buffers only, the begun one waits for its rest
             bytes = fill / buf_bytes * buf_bytes;
             begun_bytes = fill - bytes;
             std::memcpy(begun.data(), dst + bytes, begun_bytes);
             short_passes++;
         }
-        const size_t n = bytes / 4;
-        if (!mem_order && !regular) swap_pairs(dst, n);
+        const size_t n = bytes / bps;
+        if (!mem_order && !cu8 && !regular) swap_pairs(dst, n);
         if (n == 0) break;
         if ((st = adsb_ring_submit(ctx, n)) != ADSB_OK) return die(ctx, "adsb_ring_submit", st);
         total_samples += n;

@@ -75,10 +75,11 @@ hipStream_t next_scan_stream(const adsb_ctx *c, uint32_t n_chunks)
     return c->scan_stream[c->submitted % (uint64_t)period];
 }
 
-int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, bool from_mag, uint64_t n_samples,
+int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64_t n_samples,
                  uint32_t n_chunks, bool inline_tail, bool lead_from_src,
                  bool advance_carry, bool force_simple, hipEvent_t input_done, bool no_fuse)
 {
+    const bool from_mag = fmt == SrcFormat::kMag;
     // Passes of many buffers of a dense stream hand their hits over in (buffer, j, try_phase) order and
     // scored; a small pass is all launch overhead and a sparse one leaves a few hundred records that
     // the host sorts and scores in no time; the worst-case lists of the fallback are the host's too.
@@ -126,6 +127,7 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, bool from_mag, uint64
     p.debug_stop = c->debug_stop;
     p.timeline = c->d_timeline;
     p.carry = c->carry_over && !from_mag ? sl.d_carry : nullptr;
+    p.u8_table = fmt == SrcFormat::kCu8 ? c->d_u8_table : nullptr;
     p.lead_from_src = lead_from_src ? 1u : 0u;
     p.order_cnt = order_on_device ? sl.d_order_cnt : nullptr;
     p.order_base = order_on_device ? sl.d_order_base : nullptr;
@@ -149,7 +151,7 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, bool from_mag, uint64
     }
 
     sl.src = d_src;
-    sl.from_mag = from_mag;
+    sl.fmt = fmt;
     sl.n_samples = n_samples;
     sl.n_chunks = n_chunks;
     sl.flush_before = c->flush_pending;
@@ -306,15 +308,15 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, bool from_mag, uint64
                                   hipMemcpyDeviceToDevice, ss));
     {
         HT(c, HT_SCAN_LAUNCH);
-        if (int e = fused ? launch_pass_fused(p, from_mag, ss)
-                          : (force_simple ? launch_scan_simple(p, from_mag, ss) : launch_scan(p, from_mag, ss)))
+        if (int e = fused ? launch_pass_fused(p, fmt, ss)
+                          : (force_simple ? launch_scan_simple(p, fmt, ss) : launch_scan(p, fmt, ss)))
             return fail(c, (hipError_t)e, "launch_scan");
     }
     if (classic) HIP_TRY(c, hipEventRecord(sl.ev[1], ss));
     if (p.carry && advance_carry) {
         // the next submission starts from the end of this one's input (taken now: the caller
         // may reuse the buffer as soon as this pass is collected)
-        if (int e = launch_update_carry(sl.d_carry, d_src, n_samples, c->d_carry_next, ss))
+        if (int e = launch_update_carry(sl.d_carry, d_src, n_samples, c->d_carry_next, ss, p.u8_table))
             return fail(c, (hipError_t)e, "launch_update_carry");
     }
     if (fused) {
@@ -373,7 +375,7 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, bool from_mag, uint64
     // memory with write-through stores; `done` only has to say the kernel has drained
     {
         HT(c, HT_RECORDS_LAUNCH);
-        if (int e = launch_records(p, from_mag, sl.h_rec_dev, ts))
+        if (int e = launch_records(p, fmt, sl.h_rec_dev, ts))
             return fail(c, (hipError_t)e, "launch_records");
     }
     sl.tail_q = ts;
@@ -451,17 +453,17 @@ int reseed_bitmap_from_filter(adsb_ctx *c)
     return ADSB_OK;
 }
 
-int submit(adsb_ctx *c, const void *d_src, bool from_mag, uint64_t n_samples, bool inline_tail,
+int submit(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, bool inline_tail,
            hipEvent_t input_done)
 {
-    const uint64_t n_chunks = from_mag ? 1 : (n_samples + kChunkSamples - 1) / kChunkSamples;
+    const uint64_t n_chunks = fmt == SrcFormat::kMag ? 1 : (n_samples + kChunkSamples - 1) / kChunkSamples;
     if (n_chunks == 0 || n_chunks > kMaxChunks || n_chunks > c->max_chunks) return ADSB_ERR_INVALID;
     Slot &sl = c->slot[c->submitted % (uint64_t)c->n_slots];
     if (sl.busy || sl.parked || c->shard_active) return ADSB_ERR_BUSY;
 #ifdef ADSB_TUNING
     const auto te0 = std::chrono::steady_clock::now();
 #endif
-    int rc = enqueue_pass(c, sl, d_src, from_mag, n_samples, (uint32_t)n_chunks, inline_tail, false, true, false,
+    int rc = enqueue_pass(c, sl, d_src, fmt, n_samples, (uint32_t)n_chunks, inline_tail, false, true, false,
                           input_done);
 #ifdef ADSB_TUNING
     c->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - te0).count();
@@ -473,17 +475,17 @@ int submit(adsb_ctx *c, const void *d_src, bool from_mag, uint64_t n_samples, bo
 }
 
 // synchronous pass: everything pending is finished first, in order
-int run_sync(adsb_ctx *c, const void *d_src, bool from_mag, uint64_t n_samples, std::vector<adsb_msg> &out,
+int run_sync(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, std::vector<adsb_msg> &out,
              hipEvent_t input_done)
 {
     if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
-    int rc = submit(c, d_src, from_mag, n_samples, true, input_done);
+    int rc = submit(c, d_src, fmt, n_samples, true, input_done);
     if (rc) return rc;
     return collect_next(c, out);
 }
 
 // IQ stream of any length resident on the device.
-int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<adsb_msg> &out)
+int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<adsb_msg> &out, SrcFormat fmt)
 {
     if (n_samples == 0) {
         c->stats = adsb_stats{};
@@ -497,7 +499,7 @@ int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<
     for (uint64_t off = 0; off < n_samples; off += piece) {
         const uint64_t n = std::min<uint64_t>(piece, n_samples - off);
         std::vector<adsb_msg> part;
-        int rc = run_sync(c, (const uint32_t *)d_iq + off, false, n, part);
+        int rc = run_sync(c, (const char *)d_iq + off * src_bytes_per_sample(fmt), fmt, n, part);
         if (rc) return rc;
         const uint64_t chunk0 = off / kChunkSamples;
         for (auto &m : part) {
@@ -545,13 +547,20 @@ int ensure_stage(adsb_ctx *c, size_t bytes)
     return ADSB_OK;
 }
 
-}  // namespace host
-}  // namespace adsb
+void soapy_u8_table(int16_t *out256)
+{
+    // float32 at every step and a truncating conversion, as SoapyRTLSDR builds its lookup table
+    for (int x = 0; x < 256; x++) {
+        volatile float v = (float)x - 127.4f;   // (volatile: one rounding per operation, never contracted)
+        v = v * (1.0f / 128.0f);
+        v = v * 32767.0f;
+        out256[x] = (int16_t)v;
+    }
+}
 
-extern "C" {
-
-int adsb_to_mag(adsb_ctx *c, const int16_t *iq, size_t n, uint16_t *data_out, size_t *length_out)
-try {
+namespace {
+int to_mag_host(adsb_ctx *c, const void *iq, size_t n, uint16_t *data_out, size_t *length_out, SrcFormat fmt)
+{
     if (!c || (!iq && n) || !data_out) return ADSB_ERR_INVALID;
     if (n > kChunkSamples) return ADSB_ERR_TOO_LONG;  // reference: index panic, lib.rs:48
     ADSB_ON_DEVICE(c);
@@ -562,65 +571,45 @@ try {
     const size_t in_bytes = (size_t)kChunkSamples * 4, out_bytes = (size_t)kMagDataLen * sizeof(uint16_t);
     const size_t out_off = (in_bytes + 255) & ~(size_t)255;
     if (int rc = ensure_host_stage(c, out_off + out_bytes)) return rc;
-    if (n) std::memcpy(c->h_stage, iq, n * 4);
+    if (n) std::memcpy(c->h_stage, iq, n * src_bytes_per_sample(fmt));
     uint16_t *h_mag = reinterpret_cast<uint16_t *>((char *)c->h_stage + out_off);
     uint16_t *h_mag_dev = reinterpret_cast<uint16_t *>((char *)c->h_stage_dev + out_off);
-    if (int e = launch_to_mag(c->h_stage_dev, (uint32_t)n, h_mag_dev, c->stream))
+    if (int e = launch_to_mag(c->h_stage_dev, (uint32_t)n, h_mag_dev, c->stream,
+                                fmt == SrcFormat::kCu8 ? c->d_u8_table : nullptr))
         return fail(c, (hipError_t)e, "launch_to_mag");
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     std::memcpy(data_out, h_mag, out_bytes);
     if (length_out) *length_out = n;
     return ADSB_OK;
-} ADSB_ABI_CATCH
+}
 
-int adsb_demodulate2400(adsb_ctx *c, const uint16_t *data, size_t length, adsb_msg *out, size_t cap,
-                        size_t *n_out)
-try {
-    if (!c || !data || (!out && cap)) return ADSB_ERR_INVALID;
-    if (length > kChunkSamples) return ADSB_ERR_TOO_LONG;
-    ADSB_ON_DEVICE(c);
-    if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
-    c->stats = adsb_stats{};
-    c->stats.n_samples = length;
-    c->stats.n_chunks = 1;
-    std::vector<adsb_msg> msgs;
-    if (length) {
-        // the caller's MagnitudeBuffer into pinned memory; the pass (one launch) reads it in place
-        const size_t bytes = (size_t)kMagDataLen * sizeof(uint16_t);
-        if (int rc = ensure_host_stage(c, bytes)) return rc;
-        std::memcpy(c->h_stage, data, bytes);
-        int rc = run_sync(c, c->h_stage_dev, true, length, msgs, input_ready_now());
-        if (rc) return rc;
-    }
-    return deliver(c, msgs, out, cap, n_out);
-} ADSB_ABI_CATCH
-
-int adsb_demod_iq_device(adsb_ctx *c, const void *d_iq, size_t n_samples, adsb_msg *out, size_t cap,
-                         size_t *n_out)
-try {
+int demod_device_entry(adsb_ctx *c, const void *d_iq, size_t n_samples, adsb_msg *out, size_t cap, size_t *n_out, SrcFormat fmt)
+{
     if (!c || (!d_iq && n_samples) || (!out && cap)) return ADSB_ERR_INVALID;
     if (((uintptr_t)d_iq & 15u) != 0) return ADSB_ERR_INVALID;
     ADSB_ON_DEVICE(c);
     std::vector<adsb_msg> msgs;
-    int rc = demod_device(c, d_iq, n_samples, msgs);
+    int rc = demod_device(c, d_iq, n_samples, msgs, fmt);
     if (rc) return rc;
     return deliver(c, msgs, out, cap, n_out);
-} ADSB_ABI_CATCH
+}
 
-int adsb_submit_iq_device(adsb_ctx *c, const void *d_iq, size_t n_samples)
-try {
+int submit_device_entry(adsb_ctx *c, const void *d_iq, size_t n_samples, SrcFormat fmt)
+{
     if (!c || !d_iq || n_samples == 0) return ADSB_ERR_INVALID;
     if (((uintptr_t)d_iq & 15u) != 0) return ADSB_ERR_INVALID;
     if ((n_samples + kChunkSamples - 1) / kChunkSamples > std::min<uint64_t>(kMaxChunks, c->max_chunks))
         return ADSB_ERR_INVALID;  // more buffers than the context was created for
     ADSB_ON_DEVICE(c);
-    return submit(c, d_iq, false, n_samples);
-} ADSB_ABI_CATCH
+    return submit(c, d_iq, fmt, n_samples);
+}
 
-int adsb_demod_iq(adsb_ctx *c, const int16_t *iq, size_t n_samples, adsb_msg *out, size_t cap,
-                  size_t *n_out)
-try {
+// adsb_demod_iq / adsb_demod_iq_u8: a host IQ stream of either format (bps bytes per sample)
+int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, size_t cap, size_t *n_out, SrcFormat fmt)
+{
     if (!c || (!iq && n_samples) || (!out && cap)) return ADSB_ERR_INVALID;
+    const size_t bps = src_bytes_per_sample(fmt);
+    const char *iqb = static_cast<const char *>(iq);
     ADSB_ON_DEVICE(c);
     // stage through the device in pieces of at most max_chunks chunks
     std::vector<adsb_msg> msgs;
@@ -633,38 +622,38 @@ try {
     // that reads them where they are, no host copy at all.
     if (n_samples && n_samples <= std::min<size_t>(piece, (size_t)kInlineTailChunks * kChunkSamples) && !c->carry_over &&
         ((uintptr_t)iq & 15u) == 0) {
-        const char *b = reinterpret_cast<const char *>(iq);
+        const char *b = iqb;
         for (const auto &r : c->host_ranges)
-            if (b >= r.base && b + n_samples * 4 <= r.base + r.bytes) {
+            if (b >= r.base && b + n_samples * bps <= r.base + r.bytes) {
                 if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
-                int rc = run_sync(c, r.dev + (b - r.base), false, n_samples, msgs, input_ready_now());
+                int rc = run_sync(c, r.dev + (b - r.base), fmt, n_samples, msgs, input_ready_now());
                 if (rc) return rc;
                 c->stats.n_samples = n_samples;
                 return deliver(c, msgs, out, cap, n_out);
             }
     }
     const bool in_place = n_samples <= (size_t)kInlineTailChunks * kChunkSamples && !c->carry_over;
-    int rc = in_place ? ensure_host_stage(c, std::max<size_t>(n_samples, 1) * 4 + 512)   // (+ the progress word)
-                      : ensure_stage(c, std::min(piece, std::max<size_t>(n_samples, 1)) * 4);
+    int rc = in_place ? ensure_host_stage(c, std::max<size_t>(n_samples, 1) * bps + 512)   // (+ the progress word)
+                      : ensure_stage(c, std::min(piece, std::max<size_t>(n_samples, 1)) * bps);
     if (rc) return rc;
     if (in_place && n_samples && n_samples <= piece &&
         one_launch_pass(c, (uint32_t)((n_samples + kChunkSamples - 1) / kChunkSamples))) {
         // One pass of one launch: launch it FIRST and copy the samples into the pinned buffer while the launch is on its way
         // (dispatch latency ~5 us, the copy ~10): each workgroup waits for the host's progress word to pass the
         // end of its tile (ScanParams::src_ready), so the copy and the first tiles overlap instead of adding up.
-        const size_t ready_off = (n_samples * 4 + 255) & ~(size_t)255;
+        const size_t ready_off = (n_samples * bps + 255) & ~(size_t)255;
         if (int rc2 = ensure_host_stage(c, ready_off + 64)) return rc2;
         unsigned long long *ready = reinterpret_cast<unsigned long long *>((char *)c->h_stage + ready_off);
         __atomic_store_n(ready, 0ull, __ATOMIC_RELEASE);
         if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
         c->next_src_ready = reinterpret_cast<const unsigned long long *>((char *)c->h_stage_dev + ready_off);
-        rc = submit(c, c->h_stage_dev, false, n_samples, true, input_ready_now());
+        rc = submit(c, c->h_stage_dev, fmt, n_samples, true, input_ready_now());
         c->next_src_ready = nullptr;
         // (whatever submit said, the copy is finished before anything else: a pass that was launched reads it)
-        constexpr size_t kStep = 16384;   // samples per progress update: 64 KB, two tiles
+        constexpr size_t kStep = 16384;   // samples per progress update: two tiles
         for (size_t done = 0; done < n_samples;) {
             const size_t k = std::min(kStep, n_samples - done);
-            std::memcpy((char *)c->h_stage + done * 4, iq + 2 * done, k * 4);
+            std::memcpy((char *)c->h_stage + done * bps, iqb + done * bps, k * bps);
             done += k;
             __atomic_store_n(ready, (unsigned long long)done, __ATOMIC_RELEASE);
         }
@@ -675,11 +664,11 @@ try {
         return deliver(c, msgs, out, cap, n_out);
     }
     if (in_place && n_samples) {
-        std::memcpy(c->h_stage, iq, n_samples * 4);
+        std::memcpy(c->h_stage, iqb, n_samples * bps);
         for (size_t off = 0; off < n_samples; off += piece) {
             const size_t n = std::min(piece, n_samples - off);
             std::vector<adsb_msg> part;
-            rc = run_sync(c, (const uint32_t *)c->h_stage_dev + off, false, n, part, input_ready_now());
+            rc = run_sync(c, (const char *)c->h_stage_dev + off * bps, fmt, n, part, input_ready_now());
             if (rc) return rc;
             const uint64_t chunk0 = off / kChunkSamples;
             for (auto &m : part) {
@@ -698,10 +687,10 @@ try {
     }
     for (size_t off = 0; off < n_samples; off += piece) {
         const size_t n = std::min(piece, n_samples - off);
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage, iq + 2 * off, n * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage, iqb + off * bps, n * bps, hipMemcpyHostToDevice, c->stream));
         c->own_stream_dirty = true;
         std::vector<adsb_msg> part;
-        rc = demod_device(c, c->d_stage, n, part);
+        rc = demod_device(c, c->d_stage, n, part, fmt);
         if (rc) return rc;
         const uint64_t chunk0 = off / kChunkSamples;
         for (auto &m : part) {
@@ -722,6 +711,76 @@ try {
     total.n_samples = n_samples;
     c->stats = total;
     return deliver(c, msgs, out, cap, n_out);
+}
+}  // namespace
+
+}  // namespace host
+}  // namespace adsb
+
+extern "C" {
+
+int adsb_to_mag(adsb_ctx *c, const int16_t *iq, size_t n, uint16_t *data_out, size_t *length_out)
+try {
+    return to_mag_host(c, iq, n, data_out, length_out, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_to_mag_u8(adsb_ctx *c, const uint8_t *iq, size_t n, uint16_t *data_out, size_t *length_out)
+try {
+    return to_mag_host(c, iq, n, data_out, length_out, SrcFormat::kCu8);
+} ADSB_ABI_CATCH
+
+int adsb_demodulate2400(adsb_ctx *c, const uint16_t *data, size_t length, adsb_msg *out, size_t cap,
+                        size_t *n_out)
+try {
+    if (!c || !data || (!out && cap)) return ADSB_ERR_INVALID;
+    if (length > kChunkSamples) return ADSB_ERR_TOO_LONG;
+    ADSB_ON_DEVICE(c);
+    if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
+    c->stats = adsb_stats{};
+    c->stats.n_samples = length;
+    c->stats.n_chunks = 1;
+    std::vector<adsb_msg> msgs;
+    if (length) {
+        // the caller's MagnitudeBuffer into pinned memory; the pass (one launch) reads it in place
+        const size_t bytes = (size_t)kMagDataLen * sizeof(uint16_t);
+        if (int rc = ensure_host_stage(c, bytes)) return rc;
+        std::memcpy(c->h_stage, data, bytes);
+        int rc = run_sync(c, c->h_stage_dev, SrcFormat::kMag, length, msgs, input_ready_now());
+        if (rc) return rc;
+    }
+    return deliver(c, msgs, out, cap, n_out);
+} ADSB_ABI_CATCH
+
+int adsb_demod_iq_device(adsb_ctx *c, const void *d_iq, size_t n_samples, adsb_msg *out, size_t cap,
+                         size_t *n_out)
+try {
+    return demod_device_entry(c, d_iq, n_samples, out, cap, n_out, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_demod_iq_device_u8(adsb_ctx *c, const void *d_iq, size_t n_samples, adsb_msg *out, size_t cap, size_t *n_out)
+try {
+    return demod_device_entry(c, d_iq, n_samples, out, cap, n_out, SrcFormat::kCu8);
+} ADSB_ABI_CATCH
+
+int adsb_submit_iq_device(adsb_ctx *c, const void *d_iq, size_t n_samples)
+try {
+    return submit_device_entry(c, d_iq, n_samples, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_submit_iq_device_u8(adsb_ctx *c, const void *d_iq, size_t n_samples)
+try {
+    return submit_device_entry(c, d_iq, n_samples, SrcFormat::kCu8);
+} ADSB_ABI_CATCH
+
+int adsb_demod_iq(adsb_ctx *c, const int16_t *iq, size_t n_samples, adsb_msg *out, size_t cap,
+                  size_t *n_out)
+try {
+    return demod_host(c, iq, n_samples, out, cap, n_out, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_demod_iq_u8(adsb_ctx *c, const uint8_t *iq, size_t n_samples, adsb_msg *out, size_t cap, size_t *n_out)
+try {
+    return demod_host(c, iq, n_samples, out, cap, n_out, SrcFormat::kCu8);
 } ADSB_ABI_CATCH
 
 }  // extern "C"

@@ -8,17 +8,19 @@ namespace {
 constexpr uint32_t kRingInPlaceChunks = 2;
 }
 
-extern "C" {
+namespace {
 
-int adsb_ring_create(adsb_ctx *c, size_t samples_per_slot)
-try {
+// adsb_ring_create / adsb_ring_create_u8: the slots hold samples_per_slot samples of `fmt` (4 or 2 bytes each)
+int ring_create(adsb_ctx *c, size_t samples_per_slot, SrcFormat fmt)
+{
     if (!c || samples_per_slot == 0 || c->ring_samples) return ADSB_ERR_INVALID;
+    const size_t bps = src_bytes_per_sample(fmt);
     if ((samples_per_slot + kChunkSamples - 1) / kChunkSamples > c->max_chunks) return ADSB_ERR_INVALID;
     ADSB_ON_DEVICE(c);
     auto body = [&]() -> int {
         // every slot's pinned buffer from ONE allocation, and every staging buffer from one (slot starts 4 KB aligned):
         // mapped and coherent -- slots of a few buffers are read in place by the pass itself
-        const size_t stride = (samples_per_slot * 4 + 4095) & ~(size_t)4095;
+        const size_t stride = (samples_per_slot * bps + 4095) & ~(size_t)4095;
         char *h_dev = nullptr;
         HIP_TRY(c, hipHostMalloc((void **)&c->ring_h_block, stride * (size_t)c->n_slots, hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(c, hipHostGetDevicePointer((void **)&h_dev, c->ring_h_block, 0));
@@ -33,7 +35,7 @@ try {
         // pair of buffers; left to the first pipelined submit (a ring that starts with its slots read in place) every
         // later hipMemcpyAsync of the ring took 12-19 us of the submitting thread instead of 2-5 (measured: 16-buffer
         // slots, eight in flight, 12.5 Gsample/s instead of 13.2; profiles/r4_ring_copy_ab.txt).
-        const size_t warm = std::min<size_t>(samples_per_slot * 4, 64 << 10);
+        const size_t warm = std::min<size_t>(samples_per_slot * bps, 64 << 10);
         for (int k = 0; k < c->n_slots; k++)
             HIP_TRY(c, hipMemcpyAsync(c->ring[k].d_iq, c->ring[k].h_iq, warm, hipMemcpyHostToDevice, c->scan_stream[k % c->n_scan_streams]));
         for (int k = 0; k < c->n_scan_streams; k++) HIP_TRY(c, hipStreamSynchronize(c->scan_stream[k]));
@@ -50,16 +52,47 @@ try {
         return rc;
     }
     c->ring_samples = samples_per_slot;
+    c->ring_fmt = fmt;
     return ADSB_OK;
-} ADSB_ABI_CATCH
+}
 
-int adsb_ring_acquire(adsb_ctx *c, int16_t **host_iq, size_t *capacity_samples)
-try {
-    if (!c || !host_iq || !c->ring_samples) return ADSB_ERR_INVALID;
+int ring_acquire(adsb_ctx *c, void **host_iq, size_t *capacity_samples, SrcFormat fmt)
+{
+    if (!c || !host_iq || !c->ring_samples || c->ring_fmt != fmt) return ADSB_ERR_INVALID;
     if (c->slot[c->submitted % (uint64_t)c->n_slots].busy || c->slot[c->submitted % (uint64_t)c->n_slots].parked) return ADSB_ERR_BUSY;  // collect the oldest pass first
     *host_iq = c->ring[c->submitted % (uint64_t)c->n_slots].h_iq;
     if (capacity_samples) *capacity_samples = c->ring_samples;
     return ADSB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int adsb_ring_create(adsb_ctx *c, size_t samples_per_slot)
+try {
+    return ring_create(c, samples_per_slot, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_ring_create_u8(adsb_ctx *c, size_t samples_per_slot)
+try {
+    return ring_create(c, samples_per_slot, SrcFormat::kCu8);
+} ADSB_ABI_CATCH
+
+int adsb_ring_acquire(adsb_ctx *c, int16_t **host_iq, size_t *capacity_samples)
+try {
+    void *p = nullptr;
+    const int rc = ring_acquire(c, &p, capacity_samples, SrcFormat::kCs16);
+    if (rc == ADSB_OK) *host_iq = static_cast<int16_t *>(p);
+    return rc;
+} ADSB_ABI_CATCH
+
+int adsb_ring_acquire_u8(adsb_ctx *c, uint8_t **host_iq, size_t *capacity_samples)
+try {
+    void *p = nullptr;
+    const int rc = ring_acquire(c, &p, capacity_samples, SrcFormat::kCu8);
+    if (rc == ADSB_OK) *host_iq = static_cast<uint8_t *>(p);
+    return rc;
 } ADSB_ABI_CATCH
 
 int adsb_ring_submit(adsb_ctx *c, size_t n_samples)
@@ -90,18 +123,18 @@ try {
     }
     if (in_place) {
         c->next_src_host = true;
-        const int rc = submit(c, r.h_iq_dev, false, n_samples, false, input_ready_now());
+        const int rc = submit(c, r.h_iq_dev, c->ring_fmt, n_samples, false, input_ready_now());
         c->next_src_host = false;
         return rc;
     }
     hipStream_t q = next_scan_stream(c, n_chunks);
     {
         HT(c, HT_RING_MEMCPY);
-        HIP_TRY(c, hipMemcpyAsync(r.d_iq, r.h_iq, n_samples * 4, hipMemcpyHostToDevice, q));
+        HIP_TRY(c, hipMemcpyAsync(r.d_iq, r.h_iq, n_samples * src_bytes_per_sample(c->ring_fmt), hipMemcpyHostToDevice, q));
     }
     // (enqueue_pass checks that the pass does land on q, and orders it behind q with an event if it ever does not)
     c->input_on_stream = q;
-    const int rc = submit(c, r.d_iq, false, n_samples, false, input_ready_now());
+    const int rc = submit(c, r.d_iq, c->ring_fmt, n_samples, false, input_ready_now());
     c->input_on_stream = nullptr;
     return rc;
 } ADSB_ABI_CATCH

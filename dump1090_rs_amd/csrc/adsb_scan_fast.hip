@@ -493,7 +493,7 @@ __device__ __forceinline__ TileRef tile_ref(const ScanParams &p, uint32_t t)
 // back to back with no branch and no wait between them.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-template <bool FROM_MAG>
+template <bool FROM_MAG, bool U8 = false>
 __device__ __forceinline__ void load_tile_iq(const ScanParams &p, const TileRef &r, int tid,
                                              uint4 (&pre)[kLoadsPerThread])
 {
@@ -509,6 +509,26 @@ __device__ __forceinline__ void load_tile_iq(const ScanParams &p, const TileRef 
             // (opaque: a "+ 2048 i" folded into the instruction's immediate offset is added to a
             // negative register offset without wrapping, i.e. out of range -- adsb_aux.hip: k_records)
             int off = (d0 + 4 * (tid + i * kThreads)) * 2;
+            asm volatile("" : "+v"(off));
+            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0);
+            pre[i] = make_uint4(v.x, v.y, 0u, 0u);
+        }
+        return;
+    }
+    if constexpr (U8) {
+        // CU8: one dwordx2 per four samples, the bytes as they are (widened in P1: mag4_u8).  The
+        // resource covers whole dwords -- the one that holds the last sample of a ragged end also holds the
+        // two bytes behind it, in the same page -- and the lead-in and tail are masked by sample position there.
+        const uint8_t *iq8 = (const uint8_t *)p.src + r.chunk * (uint64_t)kChunkSamples * 2u;
+        const bool lead = p.carry != nullptr && (r.chunk > 0 || p.lead_from_src);
+        const int shift = lead ? kCarrySamples : 0;
+        const __amdgpu_buffer_rsrc_t rsrc =
+            __builtin_amdgcn_make_buffer_rsrc((void *)(iq8 - 2 * shift), 0, ((r.len + shift) * 2 + 3) & ~3, 0x00020000);
+        const int k0 = r.jbase - kPad - kLead + shift;
+#pragma unroll
+        for (int i = 0; i < kLoadsPerThread; i++) {
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+            int off = (k0 + 4 * (tid + i * kThreads)) * 2;
             asm volatile("" : "+v"(off));
             const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0);
             pre[i] = make_uint4(v.x, v.y, 0u, 0u);
@@ -546,8 +566,19 @@ __device__ __forceinline__ void load_tile_iq(const ScanParams &p, const TileRef 
 }
 
 // Load i of the eight alone (a tile read in place from host memory, no carry-over: k_scan_fast trickles those).
+template <bool U8 = false>
 __device__ __forceinline__ void load_tile_iq_one(const ScanParams &p, const TileRef &r, int tid, uint4 (&pre)[kLoadsPerThread], int i)
 {
+    if constexpr (U8) {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const uint8_t *iq8 = (const uint8_t *)p.src + r.chunk * (uint64_t)kChunkSamples * 2u;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)iq8, 0, (r.len * 2 + 3) & ~3, 0x00020000);
+        int off = (r.jbase - kPad - kLead + 4 * (tid + i * kThreads)) * 2;
+        asm volatile("" : "+v"(off));
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0);
+        pre[i] = make_uint4(v.x, v.y, 0u, 0u);
+        return;
+    }
     const uint32_t *iq = (const uint32_t *)p.src + r.chunk * (uint64_t)kChunkSamples;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)iq, 0, r.len * 4, 0x00020000);
     const int k0 = r.jbase - kPad - kLead;
@@ -555,6 +586,71 @@ __device__ __forceinline__ void load_tile_iq_one(const ScanParams &p, const Tile
     asm volatile("" : "+v"(off));
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
     pre[i] = make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// The CU8 widening table in LDS as f32 (1 KB; every int16 is exact in f32).  Only the U8 instantiations reach it, so
+// only they are given LDS for it.
+__device__ __forceinline__ float *u8_table_lds()
+{
+    __shared__ float t[256];
+    return t;
+}
+
+// P1 of a CU8 tile: load i's eight bytes (pre.x, pre.y: load_tile_iq<.., true>) -> four magnitudes packed as u16
+// pairs, bit for bit mag4_of of the widened CS16 dwords.  The f32 table makes the lookup the very int -> float
+// conversion mag2 does for CS16, so the widening costs two table reads a sample and nothing else.  `full` (tile-
+// uniform): every sample the tile loads is inside the resource.  Otherwise -- lead-in, zero tail, ragged end -- a
+// sample outside it is zero by its POSITION (T[0] is a sample, not zero), and on the first buffer of a call in
+// carry-over mode the CS16 carry is ORed into the lead-in, as load_tile_iq does it for CS16: after widening.
+template <bool FULL>
+__device__ __forceinline__ uint2 mag4_u8(const ScanParams &p, const TileRef &r, int tid, const uint4 &pre, int i,
+                                         const float *tab)
+{
+    f32x2 re01 = {tab[pre.x & 0xFFu], tab[(pre.x >> 16) & 0xFFu]}, im01 = {tab[(pre.x >> 8) & 0xFFu], tab[pre.x >> 24]};
+    f32x2 re23 = {tab[pre.y & 0xFFu], tab[(pre.y >> 16) & 0xFFu]}, im23 = {tab[(pre.y >> 8) & 0xFFu], tab[pre.y >> 24]};
+    if constexpr (!FULL) {
+        const bool lead = p.carry != nullptr && (r.chunk > 0 || p.lead_from_src);
+        const int shift = lead ? kCarrySamples : 0;
+        const int k = r.jbase - kPad - kLead + shift + 4 * (tid + i * kThreads);  // resource index of the first sample
+        const uint32_t nv = (uint32_t)(r.len + shift);
+        const bool v0 = (uint32_t)k < nv, v1 = (uint32_t)(k + 1) < nv, v2 = (uint32_t)(k + 2) < nv, v3 = (uint32_t)(k + 3) < nv;
+        re01 = {v0 ? re01.x : 0.0f, v1 ? re01.y : 0.0f};
+        im01 = {v0 ? im01.x : 0.0f, v1 ? im01.y : 0.0f};
+        re23 = {v2 ? re23.x : 0.0f, v3 ? re23.y : 0.0f};
+        im23 = {v2 ? im23.x : 0.0f, v3 ? im23.y : 0.0f};
+        if (i == 0 && p.carry != nullptr && !lead && r.tile == 0) {
+            const __amdgpu_buffer_rsrc_t crsrc =
+                __builtin_amdgcn_make_buffer_rsrc((void *)p.carry, 0, kCarrySamples * 4, 0x00020000);
+            const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(crsrc, (k + kCarrySamples) * 4, 0, 0);
+            const auto w = [](float re, float im) { return ((uint32_t)(int)re & 0xFFFFu) | (uint32_t)(int)im << 16; };
+            return mag4_of(make_uint4(w(re01.x, im01.x) | c.x, w(re01.y, im01.y) | c.y, w(re23.x, im23.x) | c.z,
+                                      w(re23.y, im23.y) | c.w));
+        }
+    }
+    // mag2's arithmetic on the same f32 values (the separately rounded square, then fi.mul_add(fi, fq*fq))
+    uint2 pk;
+    pk.x = mag_tail2(pk_fma(im01, im01, re01 * re01));
+    pk.y = mag_tail2(pk_fma(im23, im23, re23 * re23));
+    return pk;
+}
+
+// P1 of a CU8 tile: the eight loads' magnitudes into LDS (k_scan_fast's P1 loop, with the trickle of a tile read in
+// place from host memory).  FULL: no sample of the tile is out of range (see mag4_u8).
+template <bool FULL, bool FUSED>
+__device__ __forceinline__ void p1_u8(const ScanParams &p, FastLds &s, const TileRef &cur, int tid, uint4 (&pre)[kLoadsPerThread],
+                                      bool trickle)
+{
+#pragma unroll
+    for (int i = 0; i < kLoadsPerThread; i++) {
+        if constexpr (FUSED) {
+            if (trickle && i + kTrickle < kLoadsPerThread) {   // load i has arrived: the next one may go
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kTrickle - 1) : "memory");
+                load_tile_iq_one<true>(p, cur, tid, pre, i + kTrickle);
+            }
+        }
+        const int g = tid + i * kThreads;
+        if (g < kAllocSlots / 4) *(uint2 *)(s.mag + 4 * g) = mag4_u8<FULL>(p, cur, tid, pre[i], i, u8_table_lds());
+    }
 }
 
 // A lane writes its own matches (bits of m; the branch 0..4 of each from the three code planes)
@@ -735,7 +831,8 @@ __device__ __forceinline__ bool fused_match_entry(const ScanParams &p, const uin
     return false;
 }
 
-template <bool FROM_MAG, bool SELFTEST = false, bool FUSED = false, bool FIELDS = false>
+// U8: CU8 input (ScanParams::u8_table); a compile-time parameter, so that the CS16 instantiations are untouched by it.
+template <bool FROM_MAG, bool SELFTEST = false, bool FUSED = false, bool FIELDS = false, bool U8 = false>
 __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIGNED void k_scan_fast(ScanParams p)
 {
     __shared__ FastLds s;
@@ -781,6 +878,10 @@ __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIG
     }
     if (tid < kPlanes) s.plane[tid * kPlaneDw + kPlaneDw - 1] = 0;  // read slack
     if (tid < 2) s.nhit[tid] = 0;
+    if constexpr (U8) {   // the widening table, read by P1 of the first tile already
+        for (int i = tid; i < 256; i += kThreads) u8_table_lds()[i] = (float)(int16_t)p.u8_table[i];
+        __syncthreads();
+    }
 
     const uint32_t seg_cap = p.seg_cap;
     const uint32_t my_seg = blockIdx.x * kWaves + (uint32_t)(tid >> 6);
@@ -833,9 +934,9 @@ __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIG
     if (t_first < t_end) {
         if (trickle) {
 #pragma unroll
-            for (int i = 0; i < kTrickle; i++) load_tile_iq_one(p, tile_ref<FROM_MAG>(p, t_first), tid, pre, i);
+            for (int i = 0; i < kTrickle; i++) load_tile_iq_one<U8>(p, tile_ref<FROM_MAG>(p, t_first), tid, pre, i);
         } else {
-            load_tile_iq<FROM_MAG>(p, tile_ref<FROM_MAG>(p, t_first), tid, pre);
+            load_tile_iq<FROM_MAG, U8>(p, tile_ref<FROM_MAG>(p, t_first), tid, pre);
         }
     }
 
@@ -868,6 +969,16 @@ __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIG
     const uint32_t par = iter & 1u;  // which copy of the tile counters this tile uses
 
     // ---------------------------------------------------------------- P1 magnitudes
+    if constexpr (U8) {
+        // (the tile's first and last loads decide, once per tile, whether any sample needs its position checked:
+        // all but the first and last tiles of a buffer take the loop without the checks)
+        const int shift = p.carry != nullptr && (chunk > 0 || p.lead_from_src) ? kCarrySamples : 0;
+        const int k_first = jbase - kPad - kLead + shift;
+        if (k_first >= 0 && k_first + 4 * kThreads * kLoadsPerThread <= len + shift)
+            p1_u8<true, FUSED>(p, s, cur, tid, pre, trickle);
+        else
+            p1_u8<false, FUSED>(p, s, cur, tid, pre, trickle);
+    } else {
 #pragma unroll
     for (int i = 0; i < kLoadsPerThread; i++) {
         if constexpr (FUSED && !FROM_MAG) {
@@ -879,7 +990,8 @@ __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIG
         const int g = tid + i * kThreads;
         if (g < kAllocSlots / 4) *(uint2 *)(s.mag + 4 * g) = FROM_MAG ? make_uint2(pre[i].x, pre[i].y) : mag4_of(pre[i]);
     }
-    if (t + t_stride < t_end) load_tile_iq<FROM_MAG>(p, tile_ref<FROM_MAG>(p, t + t_stride), tid, pre);
+    }
+    if (t + t_stride < t_end) load_tile_iq<FROM_MAG, U8>(p, tile_ref<FROM_MAG>(p, t + t_stride), tid, pre);
     ACCT(0);
     if constexpr (FUSED) {
         // (bitmap_wait) behind an icao_flush the first workgroup clears the pass's bitmap: it has, by the time this
@@ -1348,7 +1460,7 @@ tile_end:
         FSTAMP(5);
         // (d) records, checksum, summary into mapped host memory; the counters back to zero
         // (the records built in place are there already; what is left is what the second look found, if it ran)
-        records_block<FROM_MAG, false, true>(p, p.fused_rec, 0u, 1u, nullptr, false, gridDim.x, fs.bits);
+        records_block<FROM_MAG, false, true, U8>(p, p.fused_rec, 0u, 1u, nullptr, false, gridDim.x, fs.bits);
         FSTAMP(6);
     }
 }
@@ -1384,7 +1496,7 @@ int scan_resident_blocks()
     return r;
 }
 
-int launch_pass_fused(const ScanParams &p, bool from_mag, void *stream)
+int launch_pass_fused(const ScanParams &p, SrcFormat fmt, void *stream)
 {
     hip_clear();
     const uint32_t tiles = p.n_chunks * kTilesPerChunk;  // one workgroup per tile: a pass of a few buffers
@@ -1392,14 +1504,17 @@ int launch_pass_fused(const ScanParams &p, bool from_mag, void *stream)
     // (one-launch passes stage their hits with their bit fields: p.hit_fields is set for them, for the hits of
     // a tile that did not fit the staging)
     if (!p.hit_fields) return (int)hipErrorInvalidValue;
-    if (from_mag)
+    if (fmt == SrcFormat::kCu8 && !p.u8_table) return (int)hipErrorInvalidValue;
+    if (fmt == SrcFormat::kMag)
         hipLaunchKernelGGL((k_scan_fast<true, false, true, true>), dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, p);
+    else if (fmt == SrcFormat::kCu8)
+        hipLaunchKernelGGL((k_scan_fast<false, false, true, true, true>), dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL((k_scan_fast<false, false, true, true>), dim3(tiles), dim3(kThreads), 0, (hipStream_t)stream, p);
     return hip_ok(hipGetLastError());
 }
 
-int launch_scan(const ScanParams &p, bool from_mag, void *stream)
+int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream)
 {
     hip_clear();
     const uint32_t tiles = p.n_chunks * kTilesPerChunk;
@@ -1408,9 +1523,23 @@ int launch_scan(const ScanParams &p, bool from_mag, void *stream)
     const uint32_t blocks = tiles < (uint32_t)resident ? tiles : (uint32_t)resident;
     // With events, the launch itself carries them (hipExtLaunchKernelGGL): the dispatch
     // packet's own begin/end timestamps, no barrier packets in the stream around it.
+    if (fmt == SrcFormat::kCu8) {   // CU8: the same choice of instantiation as for CS16 below, without the self-test's
+        if (!p.u8_table || p.cand_out) return (int)hipErrorInvalidValue;
+        if (p.hit_fields && p.ev_start && p.ev_stop)
+            hipExtLaunchKernelGGL((k_scan_fast<false, false, false, true, true>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream,
+                                  (hipEvent_t)p.ev_start, (hipEvent_t)p.ev_stop, 0, p);
+        else if (p.hit_fields)
+            hipLaunchKernelGGL((k_scan_fast<false, false, false, true, true>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p);
+        else if (p.ev_start && p.ev_stop)
+            hipExtLaunchKernelGGL((k_scan_fast<false, false, false, false, true>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream,
+                                  (hipEvent_t)p.ev_start, (hipEvent_t)p.ev_stop, 0, p);
+        else
+            hipLaunchKernelGGL((k_scan_fast<false, false, false, false, true>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p);
+        return hip_ok(hipGetLastError());
+    }
     if (p.cand_out)  // the self-test's instantiation: also writes the gate-stage position list
         hipLaunchKernelGGL((k_scan_fast<false, true>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p);
-    else if (from_mag)  // adsb_demodulate2400: one caller-supplied MagnitudeBuffer
+    else if (fmt == SrcFormat::kMag)  // adsb_demodulate2400: one caller-supplied MagnitudeBuffer
         hipLaunchKernelGGL(k_scan_fast<true>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p);
     else if (p.hit_fields && p.ev_start && p.ev_stop)  // dense stream: the scan hands its hits' bit fields to the record builder
         hipExtLaunchKernelGGL((k_scan_fast<false, false, false, true>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream,

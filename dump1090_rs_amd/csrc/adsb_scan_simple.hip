@@ -144,12 +144,14 @@ inline void hip_clear() { (void)hipGetLastError(); }
 
 }  // namespace
 
-int launch_scan_simple(const ScanParams &p, bool from_mag, void *stream)
+int launch_scan_simple(const ScanParams &p, SrcFormat fmt, void *stream)
 {
     hip_clear();
+    // (CU8 reaches this cold path widened into a CS16 staging buffer first: launch_widen_u8)
+    if (fmt == SrcFormat::kCu8) return (int)hipErrorInvalidValue;
     const uint32_t blocks = p.n_chunks * kTilesPerChunk;
     if (blocks == 0) return 0;
-    if (from_mag)
+    if (fmt == SrcFormat::kMag)
         hipLaunchKernelGGL(k_scan_simple<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(k_scan_simple<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);

@@ -46,7 +46,7 @@ int selftest_pass(adsb_ctx *c, const void *d_iq, size_t n_samples, std::vector<u
         p.cand_out = d_cand;
         p.cand_count = d_count;
         p.cand_cap = dev_cap;
-        if (int e = launch_scan(p, false, c->stream)) return fail(c, (hipError_t)e, "launch_scan");
+        if (int e = launch_scan(p, SrcFormat::kCs16, c->stream)) return fail(c, (hipError_t)e, "launch_scan");
         Counters ctr;
         uint32_t count = 0;
         HIP_TRY(c, hipMemcpyAsync(&ctr, sl.d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
@@ -95,7 +95,7 @@ int selftest_pass(adsb_ctx *c, const void *d_iq, size_t n_samples, std::vector<u
         if (c->next_seq == 0) c->next_seq = 1;
         sl.h_sum->seq = 0;
         p.seq = sl.seq;
-        if (int e = launch_records(p, false, sl.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
+        if (int e = launch_records(p, SrcFormat::kCs16, sl.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (overflow) {
             c->last_error = "selftest: the pass overflowed the fast scan's lists";

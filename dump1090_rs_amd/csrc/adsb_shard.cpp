@@ -61,10 +61,10 @@ int shard_chunk_pass(adsb_ctx *c, Slot &sl, ScanParams p, uint64_t ch, bool with
     sl.seq = next_seq(c);
     sl.h_sum->seq = 0;
     p.seq = sl.seq;
-    if (int e = launch_scan_simple(p, false, c->stream)) return fail(c, (hipError_t)e, "launch_scan_simple");
+    if (int e = launch_scan_simple(p, SrcFormat::kCs16, c->stream)) return fail(c, (hipError_t)e, "launch_scan_simple");
     if (with_match)
         if (int e = launch_match(p, c->stream)) return fail(c, (hipError_t)e, "launch_match");
-    if (int e = launch_records(p, false, c->fb.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
+    if (int e = launch_records(p, SrcFormat::kCs16, c->fb.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (__atomic_load_n(&sl.h_sum->seq, __ATOMIC_ACQUIRE) != sl.seq || sl.h_sum->overflow) {
         c->last_error = "shard: a single buffer overflowed the worst-case lists";
@@ -217,11 +217,11 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
     if (fresh)
         if (int e = launch_reset(sl.d_ctr, p.bitmap, p.bitmap_lg, ss)) return fail(c, (hipError_t)e, "launch_reset");
     if (fresh_list) HIP_TRY(c, hipMemsetAsync(job.d_fresh_seen, 0, (size_t(1) << 24) / 8, ss));
-    if (int e = launch_scan(p, false, ss)) return fail(c, (hipError_t)e, "launch_scan");
+    if (int e = launch_scan(p, SrcFormat::kCs16, ss)) return fail(c, (hipError_t)e, "launch_scan");
     if (fresh_list) {
         if (int e = launch_shard_summary(p, ss)) return fail(c, (hipError_t)e, "launch_shard_summary");
     } else {
-        if (int e = launch_records(p, false, sl.h_rec_dev, ss)) return fail(c, (hipError_t)e, "launch_records");
+        if (int e = launch_records(p, SrcFormat::kCs16, sl.h_rec_dev, ss)) return fail(c, (hipError_t)e, "launch_records");
     }
     HIP_TRY(c, hipEventRecord(sl.scanned, ss));   // (the second phase, on the tail stream, orders itself behind this launch)
     job.waiting = true;
@@ -362,7 +362,7 @@ int shard_learned(adsb_ctx *c, int k, std::vector<uint32_t> &addrs)
             ScanParams q1 = job.p;
             q1.score = ScoreDev{};   // (the first phase's records go to the host, whoever scores the second's)
             if (int e = launch_order_hits(q1, job.scan_q)) return fail(c, (hipError_t)e, "launch_order_hits");   // (device-ordered: the buckets' places)
-            if (int e = launch_records(q1, false, sl.h_rec_dev, job.scan_q)) return fail(c, (hipError_t)e, "launch_records");
+            if (int e = launch_records(q1, SrcFormat::kCs16, sl.h_rec_dev, job.scan_q)) return fail(c, (hipError_t)e, "launch_records");
             HIP_TRY(c, hipEventRecord(sl.scanned, job.scan_q));
             job.waiting = true;
             if (int rc = shard_phase_wait(c, k)) return rc;
@@ -384,7 +384,7 @@ int shard_learned(adsb_ctx *c, int k, std::vector<uint32_t> &addrs)
         job.scored = false;
         job.p.score = ScoreDev{};
         if (int e = launch_order_hits(q, c->stream)) return fail(c, (hipError_t)e, "launch_order_hits");
-        if (int e = launch_records(q, false, sl.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
+        if (int e = launch_records(q, SrcFormat::kCs16, sl.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (uint64_t ch = 0; ch < p.n_chunks; ch++) {
             size_t n = 0;
@@ -491,7 +491,7 @@ int shard_match(adsb_ctx *c, int k, const uint32_t *extra, size_t n_extra, const
         HIP_TRY(c, hipStreamWaitEvent(ts, sl.scanned, 0));
         if (int e = launch_match(p, ts)) return fail(c, (hipError_t)e, "launch_match");
         if (int e = launch_order_hits(p, ts)) return fail(c, (hipError_t)e, "launch_order_hits");   // (device-ordered shards only)
-        if (int e = launch_records(p, false, sl.h_rec_dev, ts)) return fail(c, (hipError_t)e, "launch_records");
+        if (int e = launch_records(p, SrcFormat::kCs16, sl.h_rec_dev, ts)) return fail(c, (hipError_t)e, "launch_records");
         HIP_TRY(c, hipEventRecord(sl.recorded, ts));
         job.ran = true;
         if (int rc = exact_side(true)) return rc;

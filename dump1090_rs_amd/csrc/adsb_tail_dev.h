@@ -117,7 +117,8 @@ constexpr int kRecGroup = ADSB_REC_GROUP;  // hits a wave works on at once
 // count, totals and zeroing over the `used_blocks` scan workgroups' counters only, no wait for the records'
 // write acknowledgements before the summary (the host checks the checksum of what it finds and retries),
 // and the per-bit residual constants from `tb_lds` (LDS) instead of memory.
-template <bool FROM_MAG, bool BUCKETS, bool SINGLE = false>
+// U8: the IQ is CU8 (ScanParams::u8_table): every sample re-read here is widened, masked by its position.
+template <bool FROM_MAG, bool BUCKETS, bool SINGLE = false, bool U8 = false>
 __device__ __forceinline__ void records_block(const ScanParams &p, TrialRecord *rec, const uint32_t bid, const uint32_t nblk,
                                               uint64_t *sorted, const bool clean, const uint32_t used_blocks = 0,
                                               const uint32_t *tb_lds = nullptr)
@@ -300,14 +301,21 @@ __device__ __forceinline__ void records_block(const ScanParams &p, TrialRecord *
                     // the IQ behind data[j + 19 + lane] (the range-checked resource of the full path below)
                     const uint64_t chunk = entry_chunk(e[h]);
                     const int len = chunk_len(p.n_samples, chunk);
-                    const uint32_t *iq = (const uint32_t *)p.src + chunk * (uint64_t)kChunkSamples;
                     const bool lead = p.carry != nullptr && (chunk > 0 || p.lead_from_src);
                     const int shift = lead ? kCarrySamples : 0;
-                    const __amdgpu_buffer_rsrc_t rsrc =
-                        __builtin_amdgcn_make_buffer_rsrc((void *)(iq - shift), 0, (len + shift) * 4, 0x00020000);
                     int off = ((int)entry_j(e[h]) + 19 - kLead + shift + lane) * 4;
-                    asm volatile("" : "+v"(off));
-                    w[h] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0);
+                    if constexpr (U8) {
+                        const uint8_t *iq8 = (const uint8_t *)p.src + chunk * (uint64_t)kChunkSamples * 2u;
+                        const __amdgpu_buffer_rsrc_t rsrc =
+                            __builtin_amdgcn_make_buffer_rsrc((void *)(iq8 - 2 * shift), 0, (len + shift) * 2, 0x00020000);
+                        w[h] = load_u8_sample(rsrc, off / 4, len + shift, p.u8_table);
+                    } else {
+                        const uint32_t *iq = (const uint32_t *)p.src + chunk * (uint64_t)kChunkSamples;
+                        const __amdgpu_buffer_rsrc_t rsrc =
+                            __builtin_amdgcn_make_buffer_rsrc((void *)(iq - shift), 0, (len + shift) * 4, 0x00020000);
+                        asm volatile("" : "+v"(off));
+                        w[h] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0);
+                    }
                     if (p.carry != nullptr && !lead) {
                         const __amdgpu_buffer_rsrc_t crsrc =
                             __builtin_amdgcn_make_buffer_rsrc((void *)p.carry, 0, kCarrySamples * 4, 0x00020000);
@@ -360,7 +368,9 @@ __device__ __forceinline__ void records_block(const ScanParams &p, TrialRecord *
                     const bool lead = p.carry != nullptr && (chunk > 0 || p.lead_from_src);
                     const int shift = lead ? kCarrySamples : 0;
                     const __amdgpu_buffer_rsrc_t rsrc =
-                        __builtin_amdgcn_make_buffer_rsrc((void *)(iq - shift), 0, (len + shift) * 4, 0x00020000);
+                        U8 ? __builtin_amdgcn_make_buffer_rsrc((void *)((const uint8_t *)p.src + chunk * (uint64_t)kChunkSamples * 2u - 2 * shift),
+                                                               0, (len + shift) * 2, 0x00020000)
+                           : __builtin_amdgcn_make_buffer_rsrc((void *)(iq - shift), 0, (len + shift) * 4, 0x00020000);
                     const int s0 = (int)entry_j(e[h]) + 19 - kLead + shift + lane;  // IQ sample behind data[j+19+lane]
                     // (each offset is made opaque: left to itself the compiler folds the "+ 256 q5" into the
                     // instruction's immediate offset, and the hardware adds that to the register offset
@@ -370,8 +380,12 @@ __device__ __forceinline__ void records_block(const ScanParams &p, TrialRecord *
 #pragma unroll
                     for (int q5 = 0; q5 < kQ; q5++) {
                         off[q5] = (s0 + 64 * q5) * 4;
-                        asm volatile("" : "+v"(off[q5]));
-                        w[h][q5] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off[q5], 0, 0);
+                        if constexpr (U8) {
+                            w[h][q5] = load_u8_sample(rsrc, s0 + 64 * q5, len + shift, p.u8_table);
+                        } else {
+                            asm volatile("" : "+v"(off[q5]));
+                            w[h][q5] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off[q5], 0, 0);
+                        }
                     }
                     w[h][kQ] = 0;
                     if (p.carry != nullptr && !lead) {

@@ -209,6 +209,41 @@ int adsb_fetch_messages(adsb_ctx *ctx, adsb_msg *out, size_t cap, size_t *n_out)
 int adsb_ring_create(adsb_ctx *ctx, size_t samples_per_slot);
 int adsb_ring_acquire(adsb_ctx *ctx, int16_t **host_iq_re_im, size_t *capacity_samples);
 int adsb_ring_submit(adsb_ctx *ctx, size_t n_samples);
+/* The same ring for CU8 input (see "8-bit IQ" below): slots of 2 * samples_per_slot bytes, filled with rtl_sdr's
+ * bytes as they come; adsb_ring_submit and adsb_collect are shared.  A context has one ring, of one format:
+ * adsb_ring_acquire on a CU8 ring, or adsb_ring_acquire_u8 on a CS16 ring, returns ADSB_ERR_INVALID. */
+int adsb_ring_create_u8(adsb_ctx *ctx, size_t samples_per_slot);
+int adsb_ring_acquire_u8(adsb_ctx *ctx, uint8_t **host_iq_re_im, size_t *capacity_samples);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * 8-bit IQ (CU8), as an RTL-SDR delivers it: 2 bytes per sample, unsigned, I then Q -- byte 2k is `re` and byte
+ * 2k + 1 `im` of sample k (the in-memory order of the CS16 calls above; read_test_data's [im][re] file order does
+ * not apply).  A context widens every byte b through its table T (int16_t[256]): CU8 input b of n samples MEANS the
+ * CS16 buffer widen(b), widen(b)[m] = T[b[m]] for every element m, and every _u8 call returns exactly what its CS16
+ * twin returns on widen(b) -- the same adsb_msg fields in the same order, the same filter evolution, the same
+ * carry-over behaviour (the carry is kept as widened CS16, so a stream may alternate the two formats) and the same
+ * status codes.  The widening happens on the device, inside the kernels that read the samples; the zero lead-in,
+ * the zero tail and the ragged end of a short buffer stay magnitude 0 (T[0] is a sample like any other).
+ *
+ * A new context's table is T_soapy, the one SoapyRTLSDR widens with (so that CU8 demodulates as the reference's
+ * CS16 from that driver does): T_soapy[x] = (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f), each
+ * operation in f32, the conversion truncating.
+ *
+ *   adsb_set_u8_table         the context's table from now on (NULL: T_soapy again); applies to the passes submitted
+ *                             after the call; ADSB_ERR_BUSY while passes are pending
+ *   adsb_to_mag_u8, adsb_demod_iq_u8, adsb_demod_iq_device_u8, adsb_submit_iq_device_u8
+ *                             the CS16 calls' arguments with CU8 IQ (device input 16-byte aligned); adsb_collect and
+ *                             adsb_fetch_messages are shared */
+int adsb_set_u8_table(adsb_ctx *ctx, const int16_t *table256);
+int adsb_to_mag_u8(adsb_ctx *ctx, const uint8_t *iq_re_im, size_t n, uint16_t *data_out, size_t *length_out);
+int adsb_demod_iq_u8(adsb_ctx *ctx, const uint8_t *iq_re_im, size_t n_samples, adsb_msg *out, size_t cap,
+                     size_t *n_out);
+int adsb_demod_iq_device_u8(adsb_ctx *ctx, const void *device_iq_re_im, size_t n_samples, adsb_msg *out,
+                            size_t cap, size_t *n_out);
+int adsb_submit_iq_device_u8(adsb_ctx *ctx, const void *device_iq_re_im, size_t n_samples);
+/* The table a context widens with (ctx NULL: T_soapy as the library computes it, no device needed).  For the tests.
+ * ADSB_ERR_BUSY while passes are pending. */
+int adsb_selftest_u8_table(adsb_ctx *ctx, int16_t *out256);
 
 /* For a host that keeps its own sample buffer (the Vec the SDR reads land in, dump1090_rs/src/main.rs:
  * 154-167, is allocated once): pin it and map it for the device, so that adsb_demod_iq on samples

@@ -114,6 +114,14 @@ unsafe extern "C" {
     pub fn adsb_ring_create(ctx: *mut AdsbCtx, samples_per_slot: usize) -> c_int;
     pub fn adsb_ring_acquire(ctx: *mut AdsbCtx, host_iq_re_im: *mut *mut i16, capacity_samples: *mut usize) -> c_int;
     pub fn adsb_ring_submit(ctx: *mut AdsbCtx, n_samples: usize) -> c_int;
+    pub fn adsb_ring_create_u8(ctx: *mut AdsbCtx, samples_per_slot: usize) -> c_int;
+    pub fn adsb_ring_acquire_u8(ctx: *mut AdsbCtx, host_iq_re_im: *mut *mut u8, capacity_samples: *mut usize) -> c_int;
+    pub fn adsb_set_u8_table(ctx: *mut AdsbCtx, table256: *const i16) -> c_int;
+    pub fn adsb_to_mag_u8(ctx: *mut AdsbCtx, iq_re_im: *const u8, n: usize, data_out: *mut u16, length_out: *mut usize) -> c_int;
+    pub fn adsb_demod_iq_u8(ctx: *mut AdsbCtx, iq_re_im: *const u8, n_samples: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_demod_iq_device_u8(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_submit_iq_device_u8(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize) -> c_int;
+    pub fn adsb_selftest_u8_table(ctx: *mut AdsbCtx, out256: *mut i16) -> c_int;
     pub fn adsb_shard_scan(ctx: *mut AdsbCtx, device_iq: *const c_void, n_samples: usize, addrs_out: *mut u32, cap: usize, n_addrs: *mut usize) -> c_int;
     pub fn adsb_shard_finish(ctx: *mut AdsbCtx, extra_addrs: *const u32, n_extra: usize, records_out: *mut AdsbTrial, cap: usize, n_records: *mut usize) -> c_int;
     pub fn adsb_multi_create(out: *mut *mut AdsbMulti, devices: *const c_int, n_devices: c_int, max_chunks_per_device: usize) -> c_int;
