@@ -17,6 +17,8 @@ ADSB_ERR_NOMEM = -6
 ADSB_ERR_BUSY = -7
 ADSB_ERR_POISONED = -8
 ADSB_WAIT_AUTO, ADSB_WAIT_SPIN, ADSB_WAIT_BLOCK = 0, 1, 2
+ADSB_FIX_NONE, ADSB_FIX_1BIT = 0, 1
+ADSB_SCORE_FIXED_1BIT = 1200
 ADSB_FAULT_PHASE1, ADSB_FAULT_PHASE2, ADSB_FAULT_HANG, ADSB_FAULT_RECORDS = 1, 2, 3, 4
 
 
@@ -144,6 +146,19 @@ def lib() -> C.CDLL:
     L.adsb_replay_records.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz)]
     L.adsb_set_carry_over.argtypes = [vp, C.c_int]
     L.adsb_set_carry_over.restype = C.c_int
+    L.adsb_set_error_correction.argtypes = [vp, C.c_int]
+    L.adsb_set_error_correction.restype = C.c_int
+    L.adsb_get_error_correction.argtypes = [vp]
+    L.adsb_get_error_correction.restype = C.c_int
+    L.adsb_replay_records_fix.argtypes = [vp, vp, sz, C.c_int, vp, sz, C.POINTER(sz)]
+    L.adsb_replay_records_fix.restype = C.c_int
+    L.adsb_selftest_fix_table.argtypes = [vp]
+    L.adsb_selftest_fix_table.restype = C.c_int
+    L.adsb_selftest_fix_hash.argtypes = [C.POINTER(C.c_uint32), vp, sz]
+    L.adsb_selftest_fix_hash.restype = C.c_int
+    L.adsb_selftest_parallel_replay_fix.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, C.POINTER(sz),
+                                                    C.POINTER(C.c_int)]
+    L.adsb_selftest_parallel_replay_fix.restype = C.c_int
     L.adsb_format_raw.argtypes = [vp, C.c_char_p, sz]
     L.adsb_format_raw.restype = C.c_int
     L.adsb_shard_scan.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz)]
@@ -187,6 +202,8 @@ def lib() -> C.CDLL:
     L.adsb_multi_set_wait.argtypes = [vp, C.c_int]
     L.adsb_multi_get_wait.argtypes = [vp]
     L.adsb_multi_set_timeout_ms.argtypes = [vp, C.c_uint32]
+    L.adsb_multi_set_error_correction.argtypes = [vp, C.c_int]
+    L.adsb_multi_set_error_correction.restype = C.c_int
     L.adsb_multi_selftest_fail.argtypes = [vp, C.c_uint32, C.c_int, C.c_int]
     L.adsb_multi_fetch_messages.argtypes = [vp, vp, sz, C.POINTER(sz)]
     L.adsb_multi_get_stats.argtypes = [vp, C.POINTER(AdsbMultiStats)]

@@ -90,10 +90,11 @@ def _as_cu8(iq) -> np.ndarray:
 TRIAL_DTYPE = np.dtype([("power", "<u8"), ("chunk", "<u4"), ("j_tp", "<u4"), ("msg", "u1", (14,)), ("pad", "<u2")])
 
 
-def replay_records(records: np.ndarray, filter_table: Optional[np.ndarray] = None, cap: Optional[int] = None
-                   ) -> List["ModeSMessage"]:
+def replay_records(records: np.ndarray, filter_table: Optional[np.ndarray] = None, cap: Optional[int] = None,
+                   mode: int = 0) -> List["ModeSMessage"]:
     """adsb_replay_records: the ordered host replay (scoring + best-of-5 + ICAO filter) over raw
-    trial records; `filter_table` (4096 u32, table A of the filter) is read and updated."""
+    trial records; `filter_table` (4096 u32, table A of the filter) is read and updated.  `mode`: the
+    error-correction mode (adsb_replay_records_fix; _lib.ADSB_FIX_NONE is adsb_replay_records itself)."""
     L = _lib.lib()
     rec = np.ascontiguousarray(records, dtype=TRIAL_DTYPE).copy()
     table = filter_table if filter_table is not None else np.zeros(4096, dtype=np.uint32)
@@ -101,7 +102,10 @@ def replay_records(records: np.ndarray, filter_table: Optional[np.ndarray] = Non
     cap = cap or max(4096, rec.shape[0])
     out = (AdsbMsg * cap)()
     n = C.c_size_t()
-    st = L.adsb_replay_records(table.ctypes.data, rec.ctypes.data, rec.shape[0], out, cap, C.byref(n))
+    if mode == _lib.ADSB_FIX_NONE:
+        st = L.adsb_replay_records(table.ctypes.data, rec.ctypes.data, rec.shape[0], out, cap, C.byref(n))
+    else:
+        st = L.adsb_replay_records_fix(table.ctypes.data, rec.ctypes.data, rec.shape[0], int(mode), out, cap, C.byref(n))
     if st != _lib.ADSB_OK:
         raise AdsbError(st, f"adsb_replay_records: {L.adsb_strerror(st).decode()}")
     return [ModeSMessage(bytes(m.msg), int(m.len), float(m.signal_level), int(m.score), int(m.j),
@@ -387,6 +391,15 @@ class Context:
     def set_carry_over(self, enabled: bool) -> None:
         """Opt-in, not the reference's semantics: buffer lead-ins hold the preceding samples."""
         self._check(self._L.adsb_set_carry_over(self._h, 1 if enabled else 0), "adsb_set_carry_over")
+
+    def set_error_correction(self, mode: int) -> None:
+        """adsb_set_error_correction: _lib.ADSB_FIX_NONE (default, the reference) or _lib.ADSB_FIX_1BIT (single-bit
+        repair of DF17/18 from known aircraft, score _lib.ADSB_SCORE_FIXED_1BIT); for the passes submitted after it."""
+        self._check(self._L.adsb_set_error_correction(self._h, int(mode)), "adsb_set_error_correction")
+
+    @property
+    def error_correction(self) -> int:
+        return int(self._L.adsb_get_error_correction(self._h))
 
     def set_profiling(self, level: int) -> None:
         """0 = no HIP events, 1 = scan kernel + whole chain (default), 2 = every kernel."""

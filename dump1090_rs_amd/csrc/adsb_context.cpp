@@ -293,6 +293,10 @@ try {
             tab.insert(tab.end(), r16.begin(), r16.end());
             tab.insert(tab.end(), ft.begin(), ft.end());
             tab.insert(tab.end(), bits.begin(), bits.end());
+            uint32_t fix_mult = 0;
+            const std::vector<uint32_t> fix = build_fix_table(&fix_mult);
+            tab.insert(tab.end(), fix.begin(), fix.end());
+            tab.push_back(fix_mult);
             HIP_TRY(c, hipMemcpy(c->d_tables, tab.data(), tab.size() * sizeof(uint32_t),
                                  hipMemcpyHostToDevice));
         }
@@ -561,6 +565,18 @@ try {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return ADSB_OK;
 } ADSB_ABI_CATCH
+
+int adsb_set_error_correction(adsb_ctx *c, int mode)
+try {
+    if (!c || (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT)) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    // (the one copy of the mode: the host replay scores with c->crc, and every pass built after this takes
+    // ScanParams::fix from it)
+    c->crc.set_fix(mode);
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_get_error_correction(const adsb_ctx *c) { return c ? c->crc.fix : ADSB_ERR_INVALID; }
 
 int adsb_set_u8_table(adsb_ctx *c, const int16_t *table256)
 try {

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "adsb_record.h"
+#include "adsb_tables.h"
 
 // Measurement switches (tools/*.sh: ADSB_DEBUG_STOP, ADSB_STAGGER, ADSB_SCAN_BLOCKS_PER_CU,
 // ADSB_STREAM_PRIO, ADSB_NO_EXT_EVENTS, ADSB_ONE_SCAN_STREAM, ADSB_DONE_FENCE, ADSB_TIMELINE) exist
@@ -138,7 +139,8 @@ __host__ __device__ inline uint32_t summary_check(const uint32_t w[9])
 constexpr int kTabF = 0, kTabX56 = 3, kTabCount = 6;
 // after them in the same buffer: R16 (16 u32, adsb_tables.h) and the field table (300 u32)
 constexpr int kTabR16Off = kTabCount * 256, kTabFieldOff = kTabR16Off + 16, kTabBitsOff = kTabFieldOff + 300,
-              kTabWords = kTabBitsOff + 168;  // + per-bit residual constants (build_bit_residuals)
+              kTabFixOff = kTabBitsOff + 168,  // + per-bit residual constants (build_bit_residuals)
+              kTabWords = kTabFixOff + kFixSlots + 1;  // + the single-bit repair table and its multiplier (build_fix_table)
 
 // Device-side scoring of a pass whose hits are in (buffer, j, try_phase) order: the sequential part
 // of demodulate2400 (src/mode_s/mod.rs:34-139 scores read AND write the ICAO filter,
@@ -263,6 +265,9 @@ struct ScanParams {
     // CU8 passes (the U8 instantiations): `src` holds 2 bytes per sample, widened through this int16_t[256] table
     // in device memory (adsb_set_u8_table).  Last, so that the CS16 instantiations see the layout they always had.
     const uint16_t *u8_table;
+    // 1: the pass repairs single-bit errors (adsb_set_error_correction): its scan is a fix instantiation (k_scan_fix,
+    // k_scan_simple<.., true>), whose DF17/18 trials with a repairable residual are hits.  After everything else.
+    uint32_t fix;
 };
 
 

@@ -4,8 +4,11 @@
 // reference, main.rs:46) so that downstream tools (adsb_deku's radar, anything that speaks
 // the dump1090 raw format) can consume it.
 //
-//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--buffers K] [--latency-ms T]
-//             [--readers R] <capture.iq | ->
+//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit] [--buffers K]
+//             [--latency-ms T] [--readers R] <capture.iq | ->
+//
+// --fix 1bit repairs DF17/18 frames with one flipped bit from aircraft already heard (adsb_set_error_correction);
+// none, the default, is the reference's output.
 //
 // Input is the reference's capture format (src/utils.rs:8-20, save_test_data): little-endian
 // i16 pairs, im first; --mem-order takes {re, im} pairs instead.  --format cu8 takes what rtl_sdr writes
@@ -274,6 +277,7 @@ int main(int argc, char **argv)
 {
     int device = 0, port = 0, buffers = 64, latency_ms = 100, out_cap = 0, readers = 4;
     bool quiet = false, mem_order = false, cu8 = false;
+    int fix = ADSB_FIX_NONE;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -291,11 +295,17 @@ int main(int argc, char **argv)
             else if (f == "cs16") cu8 = false;
             else path = nullptr, i = argc;
         }
+        else if (a == "--fix" && i + 1 < argc) {
+            const std::string f = argv[++i];
+            if (f == "1bit") fix = ADSB_FIX_1BIT;
+            else if (f == "none") fix = ADSB_FIX_NONE;
+            else path = nullptr, i = argc;
+        }
         else if (a == "--help" || a == "-h") path = nullptr, i = argc;
         else path = argv[i];
     }
     if (!path || buffers < 1) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->\n");
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -313,6 +323,7 @@ int main(int argc, char **argv)
     adsb_ctx *ctx = nullptr;
     int st = adsb_create(&ctx, device, (size_t)buffers);
     if (st != ADSB_OK) return die(nullptr, "adsb_create", st);
+    if ((st = adsb_set_error_correction(ctx, fix)) != ADSB_OK) return die(ctx, "adsb_set_error_correction", st);
     const size_t slot_samples = (size_t)buffers * ADSB_MODES_MAG_BUF_SAMPLES;
     if ((st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
         return die(ctx, "adsb_ring_create", st);

@@ -1302,6 +1302,17 @@ int adsb_multi_selftest_fail(adsb_multi *m, uint32_t captures_from_now, int shar
     return ADSB_OK;
 }
 
+int adsb_multi_set_error_correction(adsb_multi *m, int mode)
+{
+    if (!m || (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT)) return ADSB_ERR_INVALID;
+    if (m->submitted != m->collected) return ADSB_ERR_BUSY;
+    // the device contexts' scans (k_scan_fix, host-scored shards) and the collector's replay; the learned-address
+    // exchange is the same in both modes (a repaired trial never adds to the filter)
+    for (auto &d : m->dev) d->ctx->crc.set_fix(mode);   // (as adsb_set_error_correction; the device threads are idle)
+    m->crc.set_fix(mode);
+    return ADSB_OK;
+}
+
 int adsb_multi_selftest_tune(adsb_multi *m, uint32_t fresh_cap, uint32_t parallel_min, uint32_t score_mode)
 {
     if (!m || score_mode > 2) return ADSB_ERR_INVALID;

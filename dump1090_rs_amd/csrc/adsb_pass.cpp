@@ -84,7 +84,9 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
     // scored; a small pass is all launch overhead and a sparse one leaves a few hundred records that
     // the host sorts and scores in no time; the worst-case lists of the fallback are the host's too.
     const bool order_on_device = !force_simple && n_chunks > kInlineTailChunks && sl.hits_cap == c->hits_cap && c->dense_mode;
-    if (order_on_device && c->score.si && !c->exact_valid) {
+    // (k_score knows no repaired trials: a pass that repairs single-bit errors is scored by the host replay)
+    const bool score_on_device = order_on_device && c->score.si && c->crc.fix == ADSB_FIX_NONE;
+    if (score_on_device && !c->exact_valid) {
         // the device's copy of the filter can only be rebuilt from the host's once every pass in
         // flight has been replayed: finish them now (their results wait for adsb_collect)
         if (int rc = park_pending(c)) return rc;
@@ -128,12 +130,13 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
     p.timeline = c->d_timeline;
     p.carry = c->carry_over && !from_mag ? sl.d_carry : nullptr;
     p.u8_table = fmt == SrcFormat::kCu8 ? c->d_u8_table : nullptr;
+    p.fix = (uint32_t)c->crc.fix;
     p.lead_from_src = lead_from_src ? 1u : 0u;
     p.order_cnt = order_on_device ? sl.d_order_cnt : nullptr;
     p.order_base = order_on_device ? sl.d_order_base : nullptr;
     p.order_tmp = order_on_device ? sl.d_order_tmp : nullptr;
     sl.device_scored = false;
-    if (order_on_device && c->score.si) {
+    if (score_on_device) {
         if (c->exact_valid) {
             p.score = sl.score;
             p.score.exact_retired = nullptr;

@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "adsb_replay_host.h"
+#include "adsb_tables.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -116,7 +117,7 @@ void replay_in_order(Filter &filter, const Crc24 &crc, size_t n, uint64_t chunk_
             // records built on the device bring the CRC residual along (pad bit 0) and the filter
             // hash of the value their DF asks about (pad bit 1, hash in bits 4..15)
             const Score s = (r.pad & 1) ? score_modes_message(filter, (uint32_t)(r.power >> 40), r.msg,
-                                                              (r.pad & 2) ? (int)(r.pad >> 4) : -1)
+                                                              (r.pad & 2) ? (int)(r.pad >> 4) : -1, &crc)
                                         : score_modes_message(filter, crc, r.msg);
             if (!s.some || s.value <= best_score.value) continue;
             best = &r;
@@ -125,6 +126,7 @@ void replay_in_order(Filter &filter, const Crc24 &crc, size_t n, uint64_t chunk_
         if (!best || best_score.value < 0) continue;
         adsb_msg m{};
         std::memcpy(m.msg, best->msg, 14);
+        if (best_score.fix_bit >= 0) m.msg[best_score.fix_bit >> 3] ^= (uint8_t)(0x80u >> (best_score.fix_bit & 7));   // the repaired bytes
         m.len = (uint8_t)best_score.len;
         m.score = best_score.value;
         m.try_phase = (uint8_t)(best->j_tp >> 24);
@@ -312,6 +314,7 @@ void ParallelReplay::scan_part(int i)
             const TrialRecord &r = piece.run.rec[q];
             const uint32_t df = r.msg[0] >> 3;
             if (df != 17 && df != 18 && df != 11) continue;
+            // (a trial repaired under ADSB_FIX_1BIT has a residual too: it adds nothing, so the plan is the same in every mode)
             if (record_residual(*crc_, r) != 0) continue;   // mod.rs:80-84 (IID 0: the whole residual is zero), :97-99
             const uint32_t addr = uint32_t(r.msg[1]) << 16 | uint32_t(r.msg[2]) << 8 | r.msg[3];
             const uint32_t value = df == 18 ? (addr | IcaoFilter::kAdsbNt) : addr;
@@ -435,6 +438,8 @@ void learned_addresses(const Crc24 &crc, const TrialRecord *rec, size_t n, std::
     for (size_t i = 0; i < n; i++) {
         const uint8_t *m = rec[i].msg;
         const uint32_t df = m[0] >> 3;
+        // (under ADSB_FIX_1BIT a repairable DF17 with a residual is listed too: it adds nothing, and the list only has
+        // to hold every address the replay can add -- the address bits it sets are a superset, matched exactly later)
         const bool adds = df == 17 || (df == 11 && crc.residual(m, 7) == 0);
         if (adds) addrs.push_back(uint32_t(m[1]) << 16 | uint32_t(m[2]) << 8 | m[3]);
     }
@@ -467,9 +472,17 @@ static_assert(sizeof(adsb_trial) == sizeof(TrialRecord), "adsb_trial mirrors Tri
 
 int adsb_replay_records(uint32_t *filter_table, adsb_trial *records, size_t n, adsb_msg *out,
                         size_t cap, size_t *n_out)
+{
+    return adsb_replay_records_fix(filter_table, records, n, ADSB_FIX_NONE, out, cap, n_out);
+}
+
+int adsb_replay_records_fix(uint32_t *filter_table, adsb_trial *records, size_t n, int mode, adsb_msg *out,
+                            size_t cap, size_t *n_out)
 try {
     if (!filter_table || (!records && n) || (!out && cap)) return ADSB_ERR_INVALID;
-    static const Crc24 crc;
+    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT) return ADSB_ERR_INVALID;
+    Crc24 crc;
+    crc.set_fix(mode);
     IcaoFilter filter;
     filter.load(filter_table);
     std::vector<adsb_msg> msgs;
@@ -538,9 +551,18 @@ try {
 
 int adsb_selftest_parallel_replay(uint32_t *filter_table, const adsb_trial *records, size_t n, int runs, int parts, int threads,
                                   adsb_msg *out, size_t cap, size_t *n_out, int *went_parallel)
+{
+    return adsb_selftest_parallel_replay_fix(filter_table, records, n, runs, parts, threads, ADSB_FIX_NONE, out, cap, n_out,
+                                             went_parallel);
+}
+
+int adsb_selftest_parallel_replay_fix(uint32_t *filter_table, const adsb_trial *records, size_t n, int runs, int parts,
+                                      int threads, int mode, adsb_msg *out, size_t cap, size_t *n_out, int *went_parallel)
 try {
     if (!filter_table || (!records && n) || (!out && cap) || runs < 1 || parts < 1 || threads < 1) return ADSB_ERR_INVALID;
-    static const Crc24 crc;
+    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT) return ADSB_ERR_INVALID;
+    Crc24 crc;
+    crc.set_fix(mode);
     IcaoFilter filter;
     filter.load(filter_table);
     // the records in replay order, cut into `runs` runs at changes of the buffer index (what shards are), each handed
@@ -605,6 +627,23 @@ try {
     if (n_out) *n_out = msgs.size();
     return msgs.size() > cap ? ADSB_ERR_CAPACITY : ADSB_OK;
 } ADSB_ABI_CATCH
+
+int adsb_selftest_fix_table(uint32_t *syn112)
+{
+    if (!syn112) return ADSB_ERR_INVALID;
+    static const Crc24 crc;   // (the syndromes the host replay repairs with: mode_s_host.hpp)
+    std::memcpy(syn112, crc.syn112, sizeof(crc.syn112));
+    return ADSB_OK;
+}
+
+int adsb_selftest_fix_hash(uint32_t *mult, uint32_t *table, size_t cap)
+{
+    if (!mult || (!table && cap)) return ADSB_ERR_INVALID;
+    if (cap < (size_t)kFixSlots) return ADSB_ERR_CAPACITY;
+    const std::vector<uint32_t> t = build_fix_table(mult);
+    std::memcpy(table, t.data(), t.size() * sizeof(uint32_t));
+    return ADSB_OK;
+}
 
 int adsb_selftest_crc_table(uint32_t *out256)
 {

@@ -55,7 +55,10 @@ __device__ __forceinline__ void load_tile(const ScanParams &p, uint64_t chunk, i
     }
 }
 
-template <bool FROM_MAG>
+// FIX: single-bit repair of DF17/18 (ScanParams::fix): a residual that is the syndrome of one bit in 5..111 --
+// x^(111-b), the per-bit residual constants of adsb_tables.h -- makes a hit too (found by a plain walk: this kernel
+// is the cold path)
+template <bool FROM_MAG, bool FIX>
 __device__ __forceinline__ void scan_simple_tile(const ScanParams &p, uint32_t chunk, int jbase,
                                                  int jn, int len, uint16_t *smag, uint32_t *scrc,
                                                  uint16_t *scand, uint32_t *sncand)
@@ -106,6 +109,9 @@ __device__ __forceinline__ void scan_simple_tile(const ScanParams &p, uint32_t c
                         entry = pack_entry(c, code, j, chunk);
                         // DF18 adds addr | 1<<25, which no 24-bit test can match
                         if (df == 17) bitmap_set(p.bitmap, p.bitmap_lg, addr);
+                    } else if (FIX) {   // (a repaired trial adds nothing)
+                        for (int b = kFixFirstBit; b < 112 && !is_hit; b++) is_hit = p.tables[kTabBitsOff + b] == c;
+                        if (is_hit) entry = pack_entry(c, code, j, chunk);
                     }
                 } else if (df == 0 || df == 4 || df == 5) {  // :56-72
                     is_ap = true;
@@ -122,7 +128,7 @@ __device__ __forceinline__ void scan_simple_tile(const ScanParams &p, uint32_t c
 }
 
 // regular grid: block -> (chunk, 4096-tile)
-template <bool FROM_MAG>
+template <bool FROM_MAG, bool FIX = false>
 __global__ __launch_bounds__(256) void k_scan_simple(ScanParams p)
 {
     __shared__ __attribute__((aligned(16))) uint16_t smag[kSlots];
@@ -134,7 +140,7 @@ __global__ __launch_bounds__(256) void k_scan_simple(ScanParams p)
     const int jbase = (int)(blockIdx.x % kTilesPerChunk) * kTile;
     const int len = FROM_MAG ? (int)p.n_samples : chunk_len(p.n_samples, chunk);
     if (jbase >= len) return;
-    scan_simple_tile<FROM_MAG>(p, chunk, jbase, min(kTile, len - jbase), len, smag, scrc, scand,
+    scan_simple_tile<FROM_MAG, FIX>(p, chunk, jbase, min(kTile, len - jbase), len, smag, scrc, scand,
                                &sncand);
 }
 
@@ -151,8 +157,12 @@ int launch_scan_simple(const ScanParams &p, SrcFormat fmt, void *stream)
     if (fmt == SrcFormat::kCu8) return (int)hipErrorInvalidValue;
     const uint32_t blocks = p.n_chunks * kTilesPerChunk;
     if (blocks == 0) return 0;
-    if (fmt == SrcFormat::kMag)
+    if (fmt == SrcFormat::kMag && p.fix)
+        hipLaunchKernelGGL((k_scan_simple<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else if (fmt == SrcFormat::kMag)
         hipLaunchKernelGGL(k_scan_simple<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else if (p.fix)
+        hipLaunchKernelGGL((k_scan_simple<false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(k_scan_simple<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     return hip_ok(hipGetLastError());

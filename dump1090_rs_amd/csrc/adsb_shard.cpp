@@ -148,6 +148,7 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
     p.dap = nullptr;  // the reference-shaped kernel's list: shard_chunk_pass() fills it in
     p.dap_cap = 0;
     p.tables = c->d_tables;
+    p.fix = (uint32_t)c->crc.fix;
     p.ctr = sl.d_ctr;
     p.summary = sl.h_sum_dev;
     p.keep_counters = 1;
@@ -165,7 +166,8 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
             c->shard_device_ordered++;
             // ... and scored on the device: k_score / k_emit behind the second phase's records kernel, against the
             // context's exact bitmap and the additions of the shards before this one (ScoreDev::earlier)
-            if (c->shard_scoring && c->score.si) {
+            // (k_score knows no repaired trials: under ADSB_FIX_1BIT the host replays the shard)
+            if (c->shard_scoring && c->score.si && c->crc.fix == ADSB_FIX_NONE) {
                 job.scored = true;
                 p.score = sl.score;
                 p.score.exact = job.exact;

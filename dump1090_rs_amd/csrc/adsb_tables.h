@@ -16,6 +16,7 @@
 // multiplier is three more lookups, applied only in the match kernel.  A clean DF17/18 is
 // simply H' == 0 (x is invertible mod g).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -94,6 +95,50 @@ inline std::vector<uint32_t> build_bit_residuals()
         if (e < 56) t[112 + 55 - e] = p;
     }
     return t;
+}
+
+// Single-bit repair of DF17/18 (adsb_set_error_correction, ADSB_FIX_1BIT) on the device.  The scan knows a 112-bit
+// trial's residual only as H' = x^-56 * residual (see the top of this file), so the table of the repairable
+// syndromes is keyed in that domain: bit b (5..111) flipped leaves residual x^(111-b), i.e. H' = x^(55-b).
+// A collision-free multiplicative hash, slot = (H' * mult) >> (32 - kFixLg), entry = H' | b << 24 (0: empty; H' of
+// a repairable trial is never 0).  `mult` is the first odd number of a fixed xorshift sequence under which the 107
+// keys land in distinct slots: deterministic, and re-derived wherever it is needed.
+constexpr int kFixLg = 9, kFixSlots = 1 << kFixLg, kFixFirstBit = 5;
+
+inline uint32_t fix_key(int b)   // H' of the 112-bit message with only bit b set
+{
+    uint32_t p = 1;
+    for (int e = 0; e < 111 - b; e++) p = gf_mulx(p);
+    for (int e = 0; e < 56; e++) p = gf_divx(p);
+    return p;
+}
+
+inline uint32_t fix_slot(uint32_t key, uint32_t mult) { return (key * mult) >> (32 - kFixLg); }
+
+// the table (kFixSlots u32) and its multiplier
+inline std::vector<uint32_t> build_fix_table(uint32_t *mult_out)
+{
+    uint32_t key[112];
+    for (int b = kFixFirstBit; b < 112; b++) key[b] = fix_key(b);
+    uint32_t x = 0x9E3779B9u;
+    std::vector<uint32_t> t(kFixSlots);
+    for (;;) {
+        x ^= x << 13;
+        x ^= x >> 17;
+        x ^= x << 5;
+        const uint32_t mult = x | 1u;
+        std::fill(t.begin(), t.end(), 0u);
+        bool ok = true;
+        for (int b = kFixFirstBit; b < 112 && ok; b++) {
+            const uint32_t k = key[b], at = fix_slot(k, mult);
+            ok = t[at] == 0;
+            t[at] = k | (uint32_t)b << 24;
+        }
+        if (ok) {
+            if (mult_out) *mult_out = mult;
+            return t;
+        }
+    }
 }
 
 // Field addressing of the fast scan's trial phase.  Message bit n = 5k + r of trial phase

@@ -88,6 +88,7 @@ struct Crc24 {
             for (int k = 0; k < 8; k++) c = (c & 0x800000u) ? ((c << 1) ^ 0xFFF409u) : (c << 1);
             t[i] = c & 0xFFFFFFu;
         }
+        set_fix(0);
     }
     // :263-282; residual = syndrome of the first n-3 bytes XOR the last three
     uint32_t residual(const uint8_t *m, int nbytes) const
@@ -97,12 +98,36 @@ struct Crc24 {
             rem = ((rem << 8) ^ t[m[i] ^ ((rem >> 16) & 0xff)]) & 0xFFFFFFu;
         return rem ^ (uint32_t(m[nbytes - 3]) << 16 | uint32_t(m[nbytes - 2]) << 8 | m[nbytes - 1]);
     }
+
+    // Single-bit error correction of DF17/18 (adsb_set_error_correction): off (0, the reference) or 1 (ADSB_FIX_1BIT).
+    // The one scoring option there is; it rides along with the table because every replay is handed both.
+    int fix = 0;
+    // syn112[b]: the residual of the 112-bit message with only bit b set (bit 0 = MSB of byte 0)
+    uint32_t syn112[112];
+    void set_fix(int mode)
+    {
+        fix = mode;
+        uint8_t e[14];
+        for (int b = 0; b < 112; b++) {
+            std::memset(e, 0, sizeof e);
+            e[b >> 3] = uint8_t(0x80u >> (b & 7));
+            syn112[b] = residual(e, 14);
+        }
+    }
+    // the bit in 5..111 whose syndrome `c` is (they are distinct: tests/test_fix_cpu.py), else -1; bits 0..4 are the DF
+    int fix_bit(uint32_t c) const
+    {
+        for (int b = 5; b < 112; b++)
+            if (syn112[b] == c) return b;
+        return -1;
+    }
 };
 
 struct Score {
     bool some;    // false == the reference's None
     int len;      // 7 | 14
     int32_t value;
+    int fix_bit = -1;   // >= 0: a DF17/18 repaired by flipping this message bit (ADSB_FIX_1BIT, scored 1200 or -1)
 };
 
 // src/mode_s/mod.rs:34-139 on a 14-byte trial message whose CRC residual (over its own length:
@@ -111,8 +136,10 @@ struct Score {
 // address/parity DFs, the address for DF11/17/18) when the device supplied it, else -1.
 // `Filter`: IcaoFilter, or a stand-in with the same test(addr, start) / add(addr, start) (the position-aware view of
 // the parallel replay, adsb_replay_host.cpp).
+// `fixer`: the Crc24 whose `fix` mode applies (null: none) -- the one branch it changes is DF17/18 with a non-zero residual.
 template <class Filter>
-inline Score score_modes_message(Filter &filter, uint32_t residual, const uint8_t msg[14], int hash = -1)
+inline Score score_modes_message(Filter &filter, uint32_t residual, const uint8_t msg[14], int hash = -1,
+                                 const Crc24 *fixer = nullptr)
 {
     const uint32_t df = msg[0] >> 3;                            // :41
     const int len = (df & 0x10) ? 14 : 7;                       // :42-46
@@ -150,6 +177,14 @@ inline Score score_modes_message(Filter &filter, uint32_t residual, const uint8_
         const uint32_t h = hash >= 0 ? (uint32_t)hash : IcaoFilter::hash(addr);  // the hash takes 24 bits
         if (c != 0) {
             v = -2;
+            // ADSB_FIX_1BIT: a residual that is the syndrome of one bit in 5..111 is that bit flipped.  The repaired
+            // address is tested (DF18 too, with the plain address) and never added; `hash` is the damaged
+            // address's, so it is not used.
+            const int b = fixer && fixer->fix == 1 ? fixer->fix_bit(c) : -1;
+            if (b >= 0) {
+                const uint32_t fixed = (b >= 8 && b < 32) ? addr ^ (1u << (31 - b)) : addr;
+                return {true, len, filter.test(fixed, IcaoFilter::hash(fixed)) ? 1200 : -1, b};
+            }
         } else if (filter.test(addr, h)) {
             v = 1800;
         } else {
@@ -172,7 +207,7 @@ inline Score score_modes_message(Filter &filter, uint32_t residual, const uint8_
 template <class Filter>
 inline Score score_modes_message(Filter &filter, const Crc24 &crc, const uint8_t msg[14])
 {
-    return score_modes_message(filter, crc.residual(msg, (msg[0] & 0x80) ? 14 : 7), msg);
+    return score_modes_message(filter, crc.residual(msg, (msg[0] & 0x80) ? 14 : 7), msg, -1, &crc);
 }
 
 }  // namespace adsb

@@ -172,6 +172,10 @@ class MultiContext:
     def set_timeout_ms(self, ms: int) -> None:
         self._check(self._L.adsb_multi_set_timeout_ms(self._h, int(ms)), "adsb_multi_set_timeout_ms")
 
+    def set_error_correction(self, mode: int) -> None:
+        """adsb_multi_set_error_correction: the mode of every device context and of the collector's replay."""
+        self._check(self._L.adsb_multi_set_error_correction(self._h, int(mode)), "adsb_multi_set_error_correction")
+
     def selftest_fail(self, captures_from_now: int, shard: int, kind: int) -> None:
         """adsb_multi_selftest_fail: shard `shard` of the capture submitted `captures_from_now` submissions from now fails
         (kind: _lib.ADSB_FAULT_PHASE1 / _PHASE2 / _HANG / _RECORDS; 0 disarms)."""

@@ -275,7 +275,9 @@ typedef struct {
                        * `power` hold the CRC residual of msg over its own length (src/crc.rs:263-282),
                        * which spares adsb_replay_records the walk over the bytes; and bit 1: bits 4..15
                        * hold icao_hash (src/icao_filter.rs:19-43) of the value the message's DF asks the
-                       * filter about -- the residual for DF 0,4,5,16,20,21,24-31, else the address */
+                       * filter about -- the residual for DF 0,4,5,16,20,21,24-31, else the address.  For a
+                       * DF17/18 with a non-zero residual (one that ADSB_FIX_1BIT may repair) that hash is the
+                       * damaged address's: the replay does not use it, it hashes the repaired address itself. */
 } adsb_trial;
 
 /* Carry-over mode -- opt-in and NOT the reference's semantics.  dump1090_rs starts every
@@ -289,6 +291,30 @@ typedef struct {
  * Enabling or disabling restarts the stream (nothing precedes the next call).  Returns
  * ADSB_ERR_BUSY while passes are pending. */
 int adsb_set_carry_over(adsb_ctx *ctx, int enabled);
+
+/* Error correction -- opt-in, off by default; with ADSB_FIX_NONE every output is the reference's.
+ * ADSB_FIX_1BIT repairs extended squitters with one flipped bit, as upstream C dump1090 does, and changes one branch
+ * of score_modes_message (src/mode_s/mod.rs:91-109) and nothing else:
+ *   a DF 17 / 18 trial (112 bits) whose residual c = modes_checksum(msg, 112) is non-zero is looked up among the
+ *   syndromes syn(b) = modes_checksum(e_b, 112) of the single-bit messages e_b (bit 0 = MSB of byte 0), b = 5..111
+ *   (bits 0..4 are the DF: repairing them would change the message's class and length).  The 107 syndromes are
+ *   distinct and non-zero, so c names at most one b.  When c == syn(b), m' = msg ^ e_b and addr' = bits 9..32 of m'
+ *   (a flip in bits 8..31 changes the address); the trial scores ADSB_SCORE_FIXED_1BIT if icao_filter_test(addr')
+ *   (DF18 too, with the plain address), else -1, and adds nothing to the filter.  Any other c still scores -2.
+ * Selection is unchanged (best of the five phases by strict >, from -2; emitted when >= 0).  1200 sits below a clean
+ * DF17 (1800 / 1400) and a known DF11 IID 0 (1600), above address/parity (1000) and a new DF11 (750), and occurs nowhere
+ * in the reference: score == ADSB_SCORE_FIXED_1BIT marks a repaired message, whose msg holds the corrected bytes m'
+ * (signal_level, j, try_phase and chunk as for any message).  DF11 is not repaired: its IID is folded into the low
+ * 7 bits of the residual, where a flipped bit cannot be told from an IID.
+ * The mode applies to every demod entry point of the context (blocking, submit/collect, the ring, the _u8 twins,
+ * adsb_demodulate2400, carry-over, adsb_shard_scan / finish) for the passes submitted after the call.  Other values:
+ * ADSB_ERR_INVALID; ADSB_ERR_BUSY while passes are pending.  adsb_get_error_correction returns the mode in effect
+ * (ADSB_ERR_INVALID for a null context). */
+#define ADSB_FIX_NONE 0
+#define ADSB_FIX_1BIT 1
+#define ADSB_SCORE_FIXED_1BIT 1200
+int adsb_set_error_correction(adsb_ctx *ctx, int mode);
+int adsb_get_error_correction(const adsb_ctx *ctx);
 
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167
@@ -434,6 +460,10 @@ int adsb_multi_get_wait(const adsb_multi *m);
 /* After this long without a shard phase finishing, the device it runs on is given up (see "When a capture fails").
  * 0 = the default, 30 000 ms.  May be called at any time. */
 int adsb_multi_set_timeout_ms(adsb_multi *m, uint32_t ms);
+/* The error-correction mode (adsb_set_error_correction) of every device context of the handle and of its collector's
+ * replay, for the captures submitted after the call.  ADSB_ERR_INVALID for other values; ADSB_ERR_BUSY while captures
+ * are in flight. */
+int adsb_multi_set_error_correction(adsb_multi *m, int mode);
 
 /* Host only, no device needed: the ordered replay every demod call ends with
  * (score_modes_message src/mode_s/mod.rs:34-139 + best-of-5 selection
@@ -443,6 +473,17 @@ int adsb_multi_set_timeout_ms(adsb_multi *m, uint32_t ms);
  * src/icao_filter.rs:8), read and updated. */
 int adsb_replay_records(uint32_t *filter_table, adsb_trial *records, size_t n, adsb_msg *out,
                         size_t cap, size_t *n_out);
+/* ... under an error-correction mode (ADSB_FIX_NONE: exactly adsb_replay_records; ADSB_FIX_1BIT: see
+ * adsb_set_error_correction), for shard users who replay the records themselves. */
+int adsb_replay_records_fix(uint32_t *filter_table, adsb_trial *records, size_t n, int mode, adsb_msg *out,
+                            size_t cap, size_t *n_out);
+/* The syndromes the library repairs with: syn112[b] = modes_checksum(e_b, 112) for b = 0..111 (only 5..111 are
+ * repaired).  Host only, no context: for the test that pins them against the CRC of the reference. */
+int adsb_selftest_fix_table(uint32_t *syn112);
+/* ... and the table the scan kernels look them up in: keyed by H' = x^-56 * residual (the form in which the scan
+ * holds a 112-bit trial's residual), slot = (H' * *mult) >> 23 of 512 (`cap` >= 512), entry = H' | b << 24, 0 empty.
+ * Host only, no context: for the test that it is collision-free and complete. */
+int adsb_selftest_fix_hash(uint32_t *mult, uint32_t *table, size_t cap);
 
 /* Device self-test: digest of the magnitude tail (sqrt, *65535+0.5, saturating
  * cast; src/utils.rs:54-55) over `count` consecutive f32 bit patterns of
@@ -513,6 +554,9 @@ int adsb_multi_selftest_counters(const adsb_multi *m, uint64_t *out8);
  * replay and to the oracle. */
 int adsb_selftest_parallel_replay(uint32_t *filter_table, const adsb_trial *records, size_t n, int runs, int parts, int threads,
                                   adsb_msg *out, size_t cap, size_t *n_out, int *went_parallel);
+/* ... under an error-correction mode (adsb_set_error_correction; ADSB_FIX_NONE is the call above). */
+int adsb_selftest_parallel_replay_fix(uint32_t *filter_table, const adsb_trial *records, size_t n, int runs, int parts,
+                                      int threads, int mode, adsb_msg *out, size_t cap, size_t *n_out, int *went_parallel);
 
 /* The 256-entry CRC-24 table the host replay scores with (src/crc.rs:3-260 CRC_TABLE): for the test that
  * pins it against the reference's constants.  Host only, no context. */

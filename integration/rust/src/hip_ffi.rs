@@ -17,6 +17,11 @@ pub const ADSB_ERR_NOMEM: c_int = -6;
 pub const ADSB_ERR_BUSY: c_int = -7;
 pub const ADSB_ERR_POISONED: c_int = -8;
 
+// error-correction modes (adsb_set_error_correction) and the score of a repaired message
+pub const ADSB_FIX_NONE: i32 = 0;
+pub const ADSB_FIX_1BIT: i32 = 1;
+pub const ADSB_SCORE_FIXED_1BIT: i32 = 1200;
+
 /// `adsb_msg`: `ModeSMessage` (src/demod_2400.rs:92-102) + provenance.  40 bytes.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -101,6 +106,8 @@ unsafe extern "C" {
     pub fn adsb_set_stream(ctx: *mut AdsbCtx, hip_stream: *mut c_void) -> c_int;
     pub fn adsb_set_profiling(ctx: *mut AdsbCtx, level: c_int) -> c_int;
     pub fn adsb_set_carry_over(ctx: *mut AdsbCtx, enabled: c_int) -> c_int; // opt-in, not the reference's semantics
+    pub fn adsb_set_error_correction(ctx: *mut AdsbCtx, mode: c_int) -> c_int; // opt-in: ADSB_FIX_1BIT
+    pub fn adsb_get_error_correction(ctx: *const AdsbCtx) -> c_int;
     pub fn adsb_icao_flush(ctx: *mut AdsbCtx) -> c_int;
     pub fn adsb_to_mag(ctx: *mut AdsbCtx, iq_re_im: *const i16, n: usize, data_out: *mut u16, length_out: *mut usize) -> c_int;
     pub fn adsb_demodulate2400(ctx: *mut AdsbCtx, data: *const u16, length: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
@@ -145,7 +152,11 @@ unsafe extern "C" {
     pub fn adsb_multi_set_wait(m: *mut AdsbMulti, mode: c_int) -> c_int;
     pub fn adsb_multi_get_wait(m: *const AdsbMulti) -> c_int;
     pub fn adsb_multi_set_timeout_ms(m: *mut AdsbMulti, ms: u32) -> c_int;
+    pub fn adsb_multi_set_error_correction(m: *mut AdsbMulti, mode: c_int) -> c_int;
     pub fn adsb_replay_records(filter_table: *mut u32, records: *mut AdsbTrial, n: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_replay_records_fix(filter_table: *mut u32, records: *mut AdsbTrial, n: usize, mode: c_int, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_selftest_fix_table(syn112: *mut u32) -> c_int;
+    pub fn adsb_selftest_fix_hash(mult: *mut u32, table: *mut u32, cap: usize) -> c_int;
     pub fn adsb_format_raw(msg: *const AdsbMsg, out: *mut c_char, out_size: usize) -> c_int;
     pub fn adsb_read_test_data(path: *const c_char, iq_re_im: *mut i16, max_samples: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_selftest_mag_digest(ctx: *mut AdsbCtx, first_bits: u32, count: u32, sum_out: *mut u64, xor_out: *mut u64) -> c_int;
@@ -156,6 +167,7 @@ unsafe extern "C" {
     pub fn adsb_multi_selftest_fail(m: *mut AdsbMulti, captures_from_now: u32, shard: c_int, kind: c_int) -> c_int;
     pub fn adsb_multi_selftest_counters(m: *const AdsbMulti, out8: *mut u64) -> c_int;
     pub fn adsb_selftest_parallel_replay(filter_table: *mut u32, records: *const AdsbTrial, n: usize, runs: c_int, parts: c_int, threads: c_int, out: *mut AdsbMsg, cap: usize, n_out: *mut usize, went_parallel: *mut c_int) -> c_int;
+    pub fn adsb_selftest_parallel_replay_fix(filter_table: *mut u32, records: *const AdsbTrial, n: usize, runs: c_int, parts: c_int, threads: c_int, mode: c_int, out: *mut AdsbMsg, cap: usize, n_out: *mut usize, went_parallel: *mut c_int) -> c_int;
     pub fn adsb_selftest_crc_table(out256: *mut u32) -> c_int;
     pub fn adsb_selftest_learned_union(records: *const AdsbTrial, n: usize, known: *const u32, n_known: usize, out: *mut u32, cap: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_get_stats(ctx: *const AdsbCtx, out: *mut AdsbStats) -> c_int;

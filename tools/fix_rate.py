@@ -1,0 +1,154 @@
+"""Single-bit repair (ADSB_FIX_1BIT) against no repair on the same samples, each result checked against the CPU
+restatement of its mode (tests/fix_restatement.c over the oracle).
+
+    python tools/fix_rate.py [--out DIR] [--rounds R] [--seconds S]
+
+Shapes, each run with correction off and on in the same process, alternating round by round (R rounds, the median
+reported, the spread kept):
+  resident  BASELINE config 2's step: icao_flush + one blocking pass over 512 device-resident buffers, sparse (64
+            bursts) and busy (5000 bursts); ms per step;
+  config1   adsb_demod_iq of the one 131072-sample capture of config 1 from host memory, blocking; us per call;
+  ring      a pinned CS16 ring of 16 buffers per slot, filled once, submitted and collected for S seconds; Gsample/s.
+One JSON line per shape and mode goes to stdout and, with --out, is appended to DIR/fix_rate.jsonl.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+CHUNK = 131072
+
+
+def keys(msgs):
+    return [(m.buffer(), int(m.score), int(m.j), int(m.try_phase), int(m.chunk), float(m.signal_level)) for m in msgs]
+
+
+def parity(iq, mode, got) -> bool:
+    from tests import fix_support as fs
+    return keys(got) == fs.Restated(mode).demod_iq(iq)
+
+
+def resident(torch, rounds, n_bursts):
+    from dump1090_rs_amd import Context, synth
+    n = 512 * CHUNK
+    d = synth.make_iq_torch(n, n_bursts=n_bursts, device="cuda")
+    iq = d.cpu().numpy()
+    torch.cuda.synchronize()
+    out = {}
+    with Context(0, 512) as c:
+        ok = {}
+        for mode in (0, 1):
+            c.set_error_correction(mode)
+            c.icao_flush()
+            ok[mode] = parity(iq, mode, c.demod_iq_device(d.data_ptr(), n, cap=1 << 20))
+        t = {0: [], 1: []}
+        for r in range(rounds):
+            for mode in (0, 1):
+                c.set_error_correction(mode)
+                c.icao_flush()
+                c.demod_iq_device(d.data_ptr(), n, cap=1 << 20)   # warm-up: the stream's density
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    c.icao_flush()
+                    c.demod_iq_device(d.data_ptr(), n, cap=1 << 20)
+                t[mode].append((time.perf_counter() - t0) / 10 * 1e3)
+        for mode in (0, 1):
+            out[mode] = {"ms_per_step": statistics.median(t[mode]), "spread": [min(t[mode]), max(t[mode])], "parity": ok[mode]}
+    return out
+
+
+def config1(rounds):
+    from dump1090_rs_amd import Context, utils
+    fx = json.loads((ROOT / "tests/golden/reference_frames.json").read_text())["fixtures"][0]
+    iq = utils.read_test_data(str(ROOT / "tests/golden" / fx["file"]))
+    out = {}
+    with Context(0, 1) as c:
+        ok = {}
+        for mode in (0, 1):
+            c.set_error_correction(mode)
+            c.icao_flush()
+            ok[mode] = parity(iq, mode, c.demod_iq(iq))
+        t = {0: [], 1: []}
+        for r in range(rounds):
+            for mode in (0, 1):
+                c.set_error_correction(mode)
+                t0 = time.perf_counter()
+                for _ in range(200):
+                    c.icao_flush()
+                    c.demod_iq(iq)
+                t[mode].append((time.perf_counter() - t0) / 200 * 1e6)
+        for mode in (0, 1):
+            out[mode] = {"us_per_call": statistics.median(t[mode]), "spread": [min(t[mode]), max(t[mode])], "parity": ok[mode]}
+    return out
+
+
+def ring(rounds, seconds):
+    from dump1090_rs_amd import Context, synth
+    per = 16
+    iq = synth.make_iq(per * CHUNK, n_bursts=per * 4, seed=99)
+    out = {}
+    with Context(0, per) as c:
+        c.ring_create(per * CHUNK)
+        depth = c.max_in_flight()
+        ok = {}
+        for mode in (0, 1):   # (every slot gets the capture once: the timed loop below submits it as it stands)
+            c.set_error_correction(mode)
+            for _ in range(depth):
+                c.icao_flush()
+                buf = c.ring_acquire()
+                buf[:] = iq
+                c.ring_submit(len(iq))
+                ok[mode] = parity(iq, mode, c.collect()) and ok.get(mode, True)
+        rate = {0: [], 1: []}
+        for r in range(rounds):
+            for mode in (0, 1):
+                c.set_error_correction(mode)
+                c.icao_flush()
+                done, t0 = 0, time.perf_counter()
+                while time.perf_counter() - t0 < seconds:
+                    if c.pending() == depth:
+                        c.collect()
+                        done += 1
+                    c.ring_acquire()   # (the slot still holds the capture: the samples are the same every time)
+                    c.ring_submit(len(iq))
+                while c.pending():
+                    c.collect()
+                    done += 1
+                rate[mode].append(done * len(iq) / (time.perf_counter() - t0) / 1e9)
+        for mode in (0, 1):
+            out[mode] = {"gsample_per_s": statistics.median(rate[mode]), "spread": [min(rate[mode]), max(rate[mode])],
+                         "parity": ok[mode]}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    a = ap.parse_args()
+    import torch
+    lines = []
+    for shape, res in (("resident_sparse", resident(torch, a.rounds, 64)), ("resident_5000", resident(torch, a.rounds, 5000)),
+                       ("config1", config1(a.rounds)), ("ring16", ring(a.rounds, a.seconds))):
+        for mode in (0, 1):
+            lines.append({"shape": shape, "fix": ["none", "1bit"][mode], **res[mode]})
+    for ln in lines:
+        print(json.dumps(ln))
+    if a.out:
+        p = Path(a.out)
+        p.mkdir(parents=True, exist_ok=True)
+        with open(p / "fix_rate.jsonl", "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+    return 0 if all(ln["parity"] for ln in lines) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
