@@ -28,7 +28,57 @@ PERIODS = [
 ]
 
 
-def make_case(rng, synth, max_chunks=8):
+def formats_bursts(xrng, n, n_chunks, icaos, synth, damaged=False):
+    """--formats: bursts of the frame kinds the draws above never make (tests/formats_support.py) -- DF18 of the case's
+    aircraft and of DF18-only ones, DF11 with IID != 0 and with a bad PI, Comm-D, undefined DFs, residual 0, the two
+    zero edges, values folding onto an aircraft's superset bit; `damaged`: DF17 / DF18 copies with one bit (or two)
+    flipped.  Drawn from `xrng` only."""
+    from tests import formats_support as F
+    out = []
+    only18 = [int(x) for x in xrng.integers(1, 1 << 24, size=3)]
+    for _ in range(int(xrng.integers(0, 25 * n_chunks)) if n > 400 else 0):
+        a = icaos[int(xrng.integers(0, len(icaos)))]
+        p = int(xrng.integers(0, 1 << 62))
+        kind = int(xrng.integers(0, 11 if damaged else 9))
+        if kind == 0:
+            frame = F.es_frame(18, a if xrng.random() < 0.5 else only18[int(xrng.integers(0, 3))], p, ca=int(xrng.integers(0, 8)))
+        elif kind == 1:
+            frame = F.df11_frame(a, int(xrng.integers(0, 128)), ca=int(xrng.integers(0, 8)))
+        elif kind == 2:
+            frame = F.df11_frame(a, int(xrng.integers(0, 128)), bad_pi=0x80 << int(xrng.integers(0, 17)))
+        elif kind == 3:
+            frame = F.ap_frame(int(xrng.choice(F.COMM_D)), a if xrng.random() < 0.8 else only18[0], p)
+        elif kind == 4:
+            frame = F.undefined_frame(int(xrng.choice(F.UNDEFINED)), a, p)
+        elif kind == 5:
+            frame = F.ap_frame(int(xrng.choice(F.AP_SHORT + F.AP_LONG + F.COMM_D)), 0, p)
+        elif kind == 6:
+            frame = F.ZERO14 if xrng.random() < 0.5 else F.ZERO7_TAIL
+        elif kind == 7:
+            frame = F.ap_frame(int(xrng.choice(F.AP_SHORT + F.AP_LONG + F.COMM_D)), F.folds_onto(a, int(xrng.integers(1, 32))), p)
+        elif kind == 8:
+            frame = F.ap_frame(int(xrng.choice(F.AP_SHORT + F.AP_LONG)), only18[int(xrng.integers(0, 3))], p)
+        else:
+            good = F.es_frame(int(xrng.choice([17, 18])), a if xrng.random() < 0.8 else only18[0], p)
+            b1 = int(xrng.integers(5, 112))
+            frame = F.flip(good, b1) if kind == 9 else F.flip(good, b1, 5 + (b1 - 5 + int(xrng.integers(1, 107))) % 107)
+        tick = int(xrng.integers(-200, 5 * n))
+        if xrng.random() < 0.2:  # hug a buffer edge
+            tick = 5 * (CHUNK * int(xrng.integers(0, n_chunks + 1)) - int(xrng.integers(0, 330))) + int(xrng.integers(0, 5))
+        out.append(synth.Burst(tick, int(xrng.integers(6000, 32000)), int(xrng.integers(0, 16)), frame))
+    return out
+
+
+def add_formats(xrng, iq, synth, icaos=None, damaged=False):
+    """formats_bursts added to a capture built elsewhere (dense, mixed and multi cases)."""
+    n = len(iq)
+    if icaos is None:
+        icaos = [int(x) for x in xrng.integers(1, 1 << 24, size=int(xrng.integers(2, 20)))]
+    synth.add_bursts(iq, formats_bursts(xrng, n, max(1, -(-n // CHUNK)), icaos, synth, damaged))
+    return iq
+
+
+def make_case(rng, synth, max_chunks=8, xrng=None, damaged=False):
     n_chunks = int(rng.integers(1, max_chunks + 1))
     n = int(n_chunks * CHUNK - (rng.integers(0, CHUNK - 400) if rng.random() < 0.6 else 0))
     n -= n % 4  # device-resident entry points want 16-byte multiples between cuts; keep it simple
@@ -58,6 +108,8 @@ def make_case(rng, synth, max_chunks=8):
         if rng.random() < 0.2:  # hug a buffer edge
             tick = 5 * (CHUNK * int(rng.integers(0, n_chunks + 1)) - int(rng.integers(0, 330))) + int(rng.integers(0, 5))
         bursts.append(synth.Burst(tick, int(rng.integers(1500, 32000)), int(rng.integers(0, 16)), frame))
+    if xrng is not None:
+        bursts += formats_bursts(xrng, n, n_chunks, icaos, synth, damaged)
     synth.add_bursts(iq, bursts)
     for _ in range(int(rng.integers(0, 3))):
         if rng.random() < 0.5:
@@ -73,11 +125,14 @@ def key(m):
     return (m.chunk, m.j, m.try_phase, m.score, m.msglen, m.msg, m.signal_level)
 
 
+key_plain = key
+
+
 def okey(w):
     return (w["chunk"], w["j"], w["try_phase"], w["score"], w["len"], w["msg"], w["signal_level"])
 
 
-def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed):
+def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, xrng=None):
     """A stream of passes that switches between the host's and the device's ordering / scoring:
     dense passes of 17-30 buffers (thousands of records), the odd sparse or small one, random
     icao_flush, up to three in flight -- every pass against the oracle fed the same sequence."""
@@ -89,6 +144,8 @@ def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed):
         dense = rng.random() < 0.8
         h = synth.make_iq(n, n_bursts=int(chunks * (rng.integers(70, 110) if dense else rng.integers(0, 6))),
                           seed=int(rng.integers(1, 1 << 30)), n_icao=n_icao, df11_every=int(rng.integers(0, 5)))
+        if xrng is not None:
+            add_formats(xrng, h, synth, [0xA00000 + k * 0x101 for k in range(n_icao)])
         host.append(h)
         bufs.append(torch.from_numpy(h).cuda())
     torch.cuda.synchronize()
@@ -146,7 +203,7 @@ def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed):
     ctx.close()
 
 
-def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed):
+def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, xrng=None):
     """Cross-pass ordering: a stream of passes of very different sizes -- one to six buffers (their match
     and records run on their own scan stream) between passes of 17-48 (tail stream) -- over captures that
     share a handful of addresses, so that address/parity frames keep depending on what earlier passes
@@ -177,6 +234,8 @@ def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed):
             tick = int(5 * n * (1 - rng.random() ** 2)) if rng.random() < 0.5 else int(rng.integers(0, 5 * n))
             bursts.append(synth.Burst(min(tick, 5 * (n - 400)), int(rng.integers(6000, 30000)), int(rng.integers(0, 16)), frame))
         synth.add_bursts(iq, bursts)
+        if xrng is not None:
+            add_formats(xrng, iq, synth, icaos)
         return iq
 
     sizes = [int(rng.integers(1, 7)) if rng.random() < 0.6 else int(rng.integers(17, 49)) for _ in range(4)]
@@ -187,6 +246,8 @@ def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed):
         if c >= 17 and rng.random() < 0.5:
             host[k] = synth.make_iq(c * CHUNK, n_bursts=int(c * rng.integers(70, 110)), seed=int(rng.integers(1, 1 << 30)),
                                     n_icao=int(rng.integers(3, 40)), df11_every=int(rng.integers(0, 5)))
+            if xrng is not None:
+                add_formats(xrng, host[k], synth, icaos)
     dev = [torch.from_numpy(h).cuda() for h in host]
     torch.cuda.synchronize()
     ring_cap = int(rng.choice([6, 24])) * CHUNK
@@ -241,7 +302,7 @@ def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed):
     ctx.close()
 
 
-def multi_case(rng, synth, MultiContext, Oracle, torch, modes, case, seed, faults=True):
+def multi_case(rng, synth, MultiContext, Oracle, torch, modes, case, seed, faults=True, xrng=None):
     """adsb_multi_*: a sequence of captures of random length over a random number of contexts on the one GPU (the
     devices wherever there are several), random icao_flush, the host form and resident shards, blocking and up to four
     captures in flight -- every capture against ONE oracle stream fed the same sequence."""
@@ -281,6 +342,8 @@ def multi_case(rng, synth, MultiContext, Oracle, torch, modes, case, seed, fault
             bursts.append(synth.Burst(min(tick, max(2000, 5 * (n - 400))), int(rng.integers(6000, 30000)), int(rng.integers(0, 16)), frame))
         if n > 4000:
             synth.add_bursts(iq, bursts)
+            if xrng is not None:
+                add_formats(xrng, iq, synth, icaos)
         return iq
 
     caps = [capture() for _ in range(int(rng.integers(2, 6)))]
@@ -443,6 +506,12 @@ def main():
                          "blocking and pipelined, against one oracle stream")
     ap.add_argument("--no-multi-faults", action="store_true",
                     help="--multi sequences without injected shard failures (a third of them have one by default)")
+    ap.add_argument("--formats", action="store_true",
+                    help="also draw every other Mode S format (DF18, DF11 IID != 0, Comm-D, undefined DFs, residual 0, "
+                         "zero edges, folding values: tests/formats_support.py) into every kind of case")
+    ap.add_argument("--fix", type=float, default=0.0, metavar="P",
+                    help="run this fraction of the single-context cases under ADSB_FIX_1BIT, with damaged DF17 / DF18 "
+                         "copies, against the restatement (tests/fix_support.py)")
     args = ap.parse_args()
     import torch
     from dump1090_rs_amd import Context, sharding, synth
@@ -450,8 +519,11 @@ def main():
     from dump1090_rs_amd.context import replay_records
     from oracle import binding
     from oracle.binding import demod_iq_carry
+    from tests import fix_support as fs
 
     rng = np.random.default_rng(args.seed)
+    # --formats / --fix draw from a generator of their own: without them every case of a seed is what it always was
+    xrng = np.random.default_rng([args.seed, 3000017]) if (args.formats or args.fix > 0) else None
     ctx = Context(0, args.max_chunks)
     ring_chunks = min(2, args.max_chunks)
     ctx.ring_create(ring_chunks * CHUNK)
@@ -463,8 +535,10 @@ def main():
     ctx_big.ring_create(big_chunks * CHUNK)
     t0 = time.time()
     modes = {}
+    all_ctx = [ctx, ctx_big] + shard_ctx
     for case in range(args.cases):
-        iq, seed = make_case(rng, synth, args.max_chunks)
+        fix_case = args.fix > 0 and xrng.random() < args.fix
+        iq, seed = make_case(rng, synth, args.max_chunks, xrng if (args.formats or fix_case) else None, damaged=fix_case)
         n = len(iq)
         carry_mode = rng.random() < 0.35
         api = str(rng.choice(["host", "device", "pipelined", "ring", "ring", "shards", "magbuf"]))
@@ -481,12 +555,25 @@ def main():
         cuts = sorted(set([0, n] + [int(x) // 4 * 4 for x in cut_draw]))
         if args.ringcuts:
             cuts = list(range(0, n, ring_chunks * CHUNK)) + [n]
-        orc = binding.Oracle()
-        carry = np.zeros((326, 2), np.int16)
-        wants = []
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            w = demod_iq_carry(orc, iq[a:b], carry, cap=1 << 20)[0] if carry_mode else orc.demod_iq(iq[a:b], cap=1 << 20)[0]
-            wants.append([okey(x) for x in w])
+        # under ADSB_FIX_1BIT the restatement is the reference and messages are compared as fix_support keys
+        key = fs.key if fix_case else key_plain
+        if fix_case:
+            modes[("fix_cases", False)] = modes.get(("fix_cases", False), 0) + 1
+        for c in all_ctx:
+            c.set_error_correction(1 if fix_case else 0)
+
+        def expected(cuts):
+            if fix_case:
+                r = fs.Restated(1, carry=carry_mode)
+                return [r.demod_iq(iq[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
+            orc = binding.Oracle()
+            carry = np.zeros((326, 2), np.int16)
+            wants = []
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                w = demod_iq_carry(orc, iq[a:b], carry, cap=1 << 20)[0] if carry_mode else orc.demod_iq(iq[a:b], cap=1 << 20)[0]
+                wants.append([okey(x) for x in w])
+            return wants
+        wants = expected(cuts)
         ctx.set_carry_over(carry_mode)
         ctx.icao_flush()
         gots = []
@@ -518,12 +605,7 @@ def main():
                 rctx.icao_flush()
                 modes[("ring:copied", carry_mode)] = modes.get(("ring:copied", carry_mode), 0) + 1
             cuts = list(range(0, n, per_slot)) + [n]
-            orc = binding.Oracle()
-            carry = np.zeros((326, 2), np.int16)
-            wants = []
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                w = demod_iq_carry(orc, iq[a:b], carry, cap=1 << 20)[0] if carry_mode else orc.demod_iq(iq[a:b], cap=1 << 20)[0]
-                wants.append([okey(x) for x in w])
+            wants = expected(cuts)
             pend = 0
             for a, b in zip(cuts[:-1], cuts[1:]):
                 if pend == depth:
@@ -540,6 +622,7 @@ def main():
             # the reference's two-call shape, one 131072-sample buffer at a time (filter persists)
             from dump1090_rs_amd import MagnitudeBuffer
             orc = binding.Oracle()
+            r = fs.Restated(1)
             wants, gots = [], []
             for a in range(0, n, CHUNK):
                 part = iq[a:a + CHUNK]
@@ -548,10 +631,11 @@ def main():
                 if m.length != length or not np.array_equal(m.data, data):
                     print(f"MISMATCH case {case}: to_mag differs in buffer {a // CHUNK}")
                     sys.exit(1)
-                wants.append([okey(x) for x in orc.demodulate2400(data, length, cap=1 << 18)[0]])
+                wants.append(r.demodulate2400(data, length) if fix_case else
+                             [okey(x) for x in orc.demodulate2400(data, length, cap=1 << 18)[0]])
                 gots.append([key(x) for x in ctx.demodulate2400(m, cap=1 << 18)])
         else:  # shards: the whole capture as one stream over two contexts
-            wants = [[okey(x) for x in binding.Oracle().demod_iq(iq, cap=1 << 20)[0]]]
+            wants = [fs.Restated(1).demod_iq(iq)] if fix_case else [[okey(x) for x in binding.Oracle().demod_iq(iq, cap=1 << 20)[0]]]
             spans = [sharding.sample_range(n, 2, r) for r in range(2)]
             for c in shard_ctx:
                 c.icao_flush()
@@ -559,9 +643,9 @@ def main():
             union = np.unique(np.concatenate(learned)) if learned else np.zeros(0, np.uint32)
             recs = [c.shard_finish(union) for c in shard_ctx]
             merged = sharding.merge_records(recs, [a // CHUNK for a, _ in spans])
-            gots = [[key(m) for m in replay_records(merged, cap=1 << 20)]]
+            gots = [[key(m) for m in replay_records(merged, cap=1 << 20, mode=1 if fix_case else 0)]]
         if gots != wants:
-            print(f"MISMATCH case {case} (fuzz seed {args.seed}, noise seed {seed}): api={api} carry={carry_mode} "
+            print(f"MISMATCH case {case} (fuzz seed {args.seed}, noise seed {seed}): api={api} carry={carry_mode} fix={fix_case} "
                   f"n={n} cuts={cuts} frames want {[len(w) for w in wants]} got {[len(g) for g in gots]}")
             for w, g in zip(wants, gots):
                 for x, y in zip(w, g):
@@ -569,13 +653,22 @@ def main():
                         print(" first difference:", x, y)
                         break
             sys.exit(1)
+    for c in all_ctx:
+        c.set_error_correction(0)
     if args.only < 0:
+        def fx(*k):
+            return np.random.default_rng([args.seed, 4000037, *k]) if args.formats else None
         for k in range(args.dense):
-            dense_pipeline_case(np.random.default_rng([args.seed, k]), synth, Context, binding.Oracle, torch, modes, k, args.seed)
+            dense_pipeline_case(np.random.default_rng([args.seed, k]), synth, Context, binding.Oracle, torch, modes, k, args.seed,
+                                xrng=fx(0, k))
         for k in range(args.mixed):
-            mixed_pipeline_case(np.random.default_rng([args.seed, 1000003, k]), synth, Context, binding.Oracle, torch, modes, k, args.seed)
+            mixed_pipeline_case(np.random.default_rng([args.seed, 1000003, k]), synth, Context, binding.Oracle, torch, modes, k, args.seed,
+                                xrng=fx(1, k))
         for k in range(args.multi):
-            multi_case(np.random.default_rng([args.seed, 2000003, k]), synth, MultiContext, binding.Oracle, torch, modes, k, args.seed, faults=not args.no_multi_faults)
+            multi_case(np.random.default_rng([args.seed, 2000003, k]), synth, MultiContext, binding.Oracle, torch, modes, k, args.seed,
+                       faults=not args.no_multi_faults, xrng=fx(2, k))
+    if args.formats:
+        modes[("formats=on", False)] = 1
     print(f"{args.cases} cases identical in {time.time() - t0:.1f} s; modes: "
           + ", ".join(f"{k[0]}{'+carry' if k[1] else ''}={v}" for k, v in sorted(modes.items())))
 
