@@ -19,6 +19,8 @@ ADSB_ERR_POISONED = -8
 ADSB_WAIT_AUTO, ADSB_WAIT_SPIN, ADSB_WAIT_BLOCK = 0, 1, 2
 ADSB_FIX_NONE, ADSB_FIX_1BIT = 0, 1
 ADSB_SCORE_FIXED_1BIT = 1200
+ADSB_FIX_2BIT = 3
+ADSB_SCORE_FIXED_2BIT = 1100
 ADSB_FAULT_PHASE1, ADSB_FAULT_PHASE2, ADSB_FAULT_HANG, ADSB_FAULT_RECORDS = 1, 2, 3, 4
 
 
@@ -156,6 +158,8 @@ def lib() -> C.CDLL:
     L.adsb_selftest_fix_table.restype = C.c_int
     L.adsb_selftest_fix_hash.argtypes = [C.POINTER(C.c_uint32), vp, sz]
     L.adsb_selftest_fix_hash.restype = C.c_int
+    L.adsb_selftest_fix2_table.argtypes = [vp, vp, sz]
+    L.adsb_selftest_fix2_table.restype = C.c_int
     L.adsb_selftest_parallel_replay_fix.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, C.POINTER(sz),
                                                     C.POINTER(C.c_int)]
     L.adsb_selftest_parallel_replay_fix.restype = C.c_int

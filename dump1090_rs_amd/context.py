@@ -393,8 +393,9 @@ class Context:
         self._check(self._L.adsb_set_carry_over(self._h, 1 if enabled else 0), "adsb_set_carry_over")
 
     def set_error_correction(self, mode: int) -> None:
-        """adsb_set_error_correction: _lib.ADSB_FIX_NONE (default, the reference) or _lib.ADSB_FIX_1BIT (single-bit
-        repair of DF17/18 from known aircraft, score _lib.ADSB_SCORE_FIXED_1BIT); for the passes submitted after it."""
+        """adsb_set_error_correction: _lib.ADSB_FIX_NONE (default, the reference), _lib.ADSB_FIX_1BIT (single-bit
+        repair of DF17/18 from known aircraft, score _lib.ADSB_SCORE_FIXED_1BIT) or _lib.ADSB_FIX_2BIT (one or two
+        flipped bits; a two-bit repair scores _lib.ADSB_SCORE_FIXED_2BIT); for the passes submitted after it."""
         self._check(self._L.adsb_set_error_correction(self._h, int(mode)), "adsb_set_error_correction")
 
     @property

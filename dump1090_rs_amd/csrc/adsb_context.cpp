@@ -297,6 +297,9 @@ try {
             const std::vector<uint32_t> fix = build_fix_table(&fix_mult);
             tab.insert(tab.end(), fix.begin(), fix.end());
             tab.push_back(fix_mult);
+            tab.resize(kTabFix2Off, 0u);
+            const std::vector<uint32_t> fix2 = build_fix2_table();
+            tab.insert(tab.end(), fix2.begin(), fix2.end());
             HIP_TRY(c, hipMemcpy(c->d_tables, tab.data(), tab.size() * sizeof(uint32_t),
                                  hipMemcpyHostToDevice));
         }
@@ -568,7 +571,7 @@ try {
 
 int adsb_set_error_correction(adsb_ctx *c, int mode)
 try {
-    if (!c || (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT)) return ADSB_ERR_INVALID;
+    if (!c || (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT && mode != ADSB_FIX_2BIT)) return ADSB_ERR_INVALID;
     if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
     // (the one copy of the mode: the host replay scores with c->crc, and every pass built after this takes
     // ScanParams::fix from it)

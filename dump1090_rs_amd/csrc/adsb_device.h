@@ -140,7 +140,9 @@ constexpr int kTabF = 0, kTabX56 = 3, kTabCount = 6;
 // after them in the same buffer: R16 (16 u32, adsb_tables.h) and the field table (300 u32)
 constexpr int kTabR16Off = kTabCount * 256, kTabFieldOff = kTabR16Off + 16, kTabBitsOff = kTabFieldOff + 300,
               kTabFixOff = kTabBitsOff + 168,  // + per-bit residual constants (build_bit_residuals)
-              kTabWords = kTabFixOff + kFixSlots + 1;  // + the single-bit repair table and its multiplier (build_fix_table)
+              // + the single-bit repair table and its multiplier (build_fix_table), then the two-bit table, 16-byte aligned
+              kTabFix2Off = (kTabFixOff + kFixSlots + 1 + 3) & ~3,
+              kTabWords = kTabFix2Off + kFix2Words;  // (build_fix2_table: its multipliers, then its buckets)
 
 // Device-side scoring of a pass whose hits are in (buffer, j, try_phase) order: the sequential part
 // of demodulate2400 (src/mode_s/mod.rs:34-139 scores read AND write the ICAO filter,

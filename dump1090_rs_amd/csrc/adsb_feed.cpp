@@ -4,10 +4,11 @@
 // reference, main.rs:46) so that downstream tools (adsb_deku's radar, anything that speaks
 // the dump1090 raw format) can consume it.
 //
-//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit] [--buffers K]
+//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K]
 //             [--latency-ms T] [--readers R] <capture.iq | ->
 //
-// --fix 1bit repairs DF17/18 frames with one flipped bit from aircraft already heard (adsb_set_error_correction);
+// --fix 1bit repairs DF17/18 frames with one flipped bit from aircraft already heard, --fix 2bit with one or two
+// (adsb_set_error_correction);
 // none, the default, is the reference's output.
 //
 // Input is the reference's capture format (src/utils.rs:8-20, save_test_data): little-endian
@@ -298,6 +299,7 @@ int main(int argc, char **argv)
         else if (a == "--fix" && i + 1 < argc) {
             const std::string f = argv[++i];
             if (f == "1bit") fix = ADSB_FIX_1BIT;
+            else if (f == "2bit") fix = ADSB_FIX_2BIT;
             else if (f == "none") fix = ADSB_FIX_NONE;
             else path = nullptr, i = argc;
         }
@@ -305,7 +307,7 @@ int main(int argc, char **argv)
         else path = argv[i];
     }
     if (!path || buffers < 1) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->\n");
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);

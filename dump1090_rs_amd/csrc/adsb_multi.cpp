@@ -1304,7 +1304,7 @@ int adsb_multi_selftest_fail(adsb_multi *m, uint32_t captures_from_now, int shar
 
 int adsb_multi_set_error_correction(adsb_multi *m, int mode)
 {
-    if (!m || (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT)) return ADSB_ERR_INVALID;
+    if (!m || (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT && mode != ADSB_FIX_2BIT)) return ADSB_ERR_INVALID;
     if (m->submitted != m->collected) return ADSB_ERR_BUSY;
     // the device contexts' scans (k_scan_fix, host-scored shards) and the collector's replay; the learned-address
     // exchange is the same in both modes (a repaired trial never adds to the filter)

@@ -126,7 +126,7 @@ void replay_in_order(Filter &filter, const Crc24 &crc, size_t n, uint64_t chunk_
         if (!best || best_score.value < 0) continue;
         adsb_msg m{};
         std::memcpy(m.msg, best->msg, 14);
-        if (best_score.fix_bit >= 0) m.msg[best_score.fix_bit >> 3] ^= (uint8_t)(0x80u >> (best_score.fix_bit & 7));   // the repaired bytes
+        apply_fix(best_score, m.msg);   // the repaired bytes
         m.len = (uint8_t)best_score.len;
         m.score = best_score.value;
         m.try_phase = (uint8_t)(best->j_tp >> 24);
@@ -480,7 +480,7 @@ int adsb_replay_records_fix(uint32_t *filter_table, adsb_trial *records, size_t 
                             size_t cap, size_t *n_out)
 try {
     if (!filter_table || (!records && n) || (!out && cap)) return ADSB_ERR_INVALID;
-    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT) return ADSB_ERR_INVALID;
+    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT && mode != ADSB_FIX_2BIT) return ADSB_ERR_INVALID;
     Crc24 crc;
     crc.set_fix(mode);
     IcaoFilter filter;
@@ -560,7 +560,7 @@ int adsb_selftest_parallel_replay_fix(uint32_t *filter_table, const adsb_trial *
                                       int threads, int mode, adsb_msg *out, size_t cap, size_t *n_out, int *went_parallel)
 try {
     if (!filter_table || (!records && n) || (!out && cap) || runs < 1 || parts < 1 || threads < 1) return ADSB_ERR_INVALID;
-    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT) return ADSB_ERR_INVALID;
+    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT && mode != ADSB_FIX_2BIT) return ADSB_ERR_INVALID;
     Crc24 crc;
     crc.set_fix(mode);
     IcaoFilter filter;
@@ -642,6 +642,19 @@ int adsb_selftest_fix_hash(uint32_t *mult, uint32_t *table, size_t cap)
     if (cap < (size_t)kFixSlots) return ADSB_ERR_CAPACITY;
     const std::vector<uint32_t> t = build_fix_table(mult);
     std::memcpy(table, t.data(), t.size() * sizeof(uint32_t));
+    return ADSB_OK;
+}
+
+int adsb_selftest_fix2_table(uint32_t *params4, uint32_t *buckets, size_t cap)
+{
+    if (!params4 || (!buckets && cap)) return ADSB_ERR_INVALID;
+    if (cap < (size_t)(4 * kFix2Buckets)) return ADSB_ERR_CAPACITY;
+    const std::vector<uint32_t> t = build_fix2_table();   // (what every context uploads: adsb_context.cpp)
+    params4[0] = t[0];
+    params4[1] = t[1];
+    params4[2] = (uint32_t)kFix2Lg;
+    params4[3] = (uint32_t)kFix2Probes;
+    std::memcpy(buckets, t.data() + 4, 4 * (size_t)kFix2Buckets * sizeof(uint32_t));
     return ADSB_OK;
 }
 

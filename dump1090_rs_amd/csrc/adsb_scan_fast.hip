@@ -256,15 +256,19 @@ struct Trial {
     uint32_t code;   // try_phase - 4, + 5 for 112-bit messages
     uint32_t cslot;
     uint32_t fixbit;            // FIX: the message bit a repairable DF17/18 trial has flipped (is_hit && h != 0)
+    uint32_t fixres;            // FIX2: the residual proper of a two-bit repair, syn(a) ^ syn(b) (0: none)
     bool is_ap, is_hit, learn;  // address/parity trial; self-validating hit; hit that adds its address
 };
 
 // FIX (adsb_set_error_correction): a DF17/18 trial with h != 0 whose h is the syndrome of one flipped bit in 5..111
 // is a hit too (never a learner): `fixt` is the kFixSlots-entry table in LDS, `fix_mult` its multiplier
 // (adsb_tables.h: build_fix_table).  One multiply, one LDS read and one compare, on the lanes of such trials only.
-template <bool FIX = false>
+// FIX2 (ADSB_FIX_2BIT): on the lanes that missed there, the pair table in global memory (`fix2`: its buckets,
+// `m0`, `m1`: its multipliers; adsb_tables.h: build_fix2_table) -- two independent 16-byte loads, four compares.
+template <bool FIX = false, bool FIX2 = false>
 __device__ __forceinline__ void trial_eval(const FastLds &s, uint32_t ce, uint32_t tpi, Trial &o, const uint32_t *fixt = nullptr,
-                                           uint32_t fix_mult = 0)
+                                           uint32_t fix_mult = 0, const uint4 *fix2 = nullptr, uint32_t m0 = 0,
+                                           uint32_t m1 = 0)
 {
     const uint32_t qs = (ce >> 13) & 0x3FFu, rs = ce >> 23;
     o.cslot = ce & 0x1FFFu;
@@ -314,10 +318,22 @@ __device__ __forceinline__ void trial_eval(const FastLds &s, uint32_t ce, uint32
     if constexpr (FIX) {
         bool fixable = false;
         o.fixbit = 0;
+        if constexpr (FIX2) o.fixres = 0;
         if (d1718 && !z) {
             const uint32_t e = fixt[(h * fix_mult) >> (32 - kFixLg)];
             fixable = (e & 0xFFFFFFu) == h;
             o.fixbit = e >> 24;
+            if constexpr (FIX2) {
+                if (!fixable) {
+                    const uint4 q0 = fix2[(h * m0) >> (32 - kFix2Lg)], q1 = fix2[(h * m1) >> (32 - kFix2Lg)];
+                    uint32_t r = (q0.x & 0xFFFFFFu) == h ? q0.y : 0u;
+                    r = (q0.z & 0xFFFFFFu) == h ? q0.w : r;
+                    r = (q1.x & 0xFFFFFFu) == h ? q1.y : r;
+                    r = (q1.z & 0xFFFFFFu) == h ? q1.w : r;
+                    o.fixres = r & 0xFFFFFFu;   // (never 0 for a pair: the residuals are distinct)
+                    fixable = r != 0u;
+                }
+            }
         }
         o.is_hit = o.is_hit || fixable;
     }
@@ -713,22 +729,24 @@ __device__ __forceinline__ void gate_pass(const ScanParams &p, const FastLds &s,
 }
 
 // One 64-lane pass of the trials: lane = (candidate entry ce, try_phase 4 + tpi).
-template <bool FUSED, bool FIELDS, bool FIX = false>
+template <bool FUSED, bool FIELDS, bool FIX = false, bool FIX2 = false>
 __device__ __forceinline__ void trial_pass(const ScanParams &p, FastLds &s, HitFieldLds<FIELDS, FUSED> &hf, uint32_t ce, uint32_t tpi,
                                            bool live, int jbase, uint32_t chunk, uint64_t *seg, uint32_t seg_cap,
                                            uint32_t &ap_count, int lane, uint32_t par, const uint32_t *fixt = nullptr,
-                                           uint32_t fix_mult = 0)
+                                           uint32_t fix_mult = 0, const uint4 *fix2 = nullptr, uint32_t m0 = 0, uint32_t m1 = 0)
 {
     Trial tr;
-    trial_eval<FIX>(s, ce, tpi, tr, fixt, fix_mult);
+    trial_eval<FIX, FIX2>(s, ce, tpi, tr, fixt, fix_mult, fix2, m0, m1);
     const bool is_ap = live && tr.is_ap, is_hit = live && tr.is_hit, learn = live && tr.learn;
     // entry = value24 | code << 24 | j << 28 | chunk << 45   (adsb_device.h)
     const uint32_t j = (uint32_t)(jbase - kPad) + tr.cslot;
     uint32_t value = tr.h;
     if constexpr (FIX) {
         // a repaired trial's hit carries its residual proper, x^(111 - b) (what the record builders and the host
-        // replay take a hit's value for: a clean hit's H' is its residual, 0), not H'
-        if (is_hit && tr.h != 0u && (tr.code >= 5u)) value = p.tables[kTabBitsOff + tr.fixbit];
+        // replay take a hit's value for: a clean hit's H' is its residual, 0), not H'.  A two-bit repair brings its
+        // residual along from the pair table.
+        if (is_hit && tr.h != 0u && (tr.code >= 5u))
+            value = FIX2 && tr.fixres != 0u ? tr.fixres : p.tables[kTabBitsOff + tr.fixbit];
     }
     const uint64_t entry = ((uint64_t)((j >> 4) | (chunk << 13)) << 32) | (value | (tr.code << 24) | (j << 28));
     // AP entries: straight into this wave's own segment of the list (no atomic, no shared
@@ -865,7 +883,7 @@ __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIG
     __shared__ FastLds s;
     __shared__ FusedLds<FUSED> fs;
     __shared__ HitFieldLds<FIELDS, FUSED> hf;
-    constexpr bool FIX = false;
+    constexpr bool FIX = false, FIX2 = false;
     uint32_t *const fixt = nullptr;
 #include "adsb_scan_fast_body.inc"
 }
@@ -880,7 +898,21 @@ __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIG
     __shared__ FusedLds<FUSED> fs;
     __shared__ HitFieldLds<FIELDS, FUSED> hf;
     __shared__ uint32_t fixt[kFixSlots];
-    constexpr bool SELFTEST = false, FIX = true;
+    constexpr bool SELFTEST = false, FIX = true, FIX2 = false;
+#include "adsb_scan_fast_body.inc"
+}
+
+// ... with two-bit repair as well (ADSB_FIX_2BIT): a DF17/18 trial that misses the single-bit table in LDS looks its
+// residual up in the pair table in global memory (adsb_tables.h: build_fix2_table).  The LDS of k_scan_fix, so its
+// occupancy too.  A kernel of its own, so that k_scan_fix stays what it is.
+template <bool FROM_MAG, bool FUSED = false, bool FIELDS = false, bool U8 = false>
+__global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIGNED void k_scan_fix2(ScanParams p)
+{
+    __shared__ FastLds s;
+    __shared__ FusedLds<FUSED> fs;
+    __shared__ HitFieldLds<FIELDS, FUSED> hf;
+    __shared__ uint32_t fixt[kFixSlots];
+    constexpr bool SELFTEST = false, FIX = true, FIX2 = true;
 #include "adsb_scan_fast_body.inc"
 }
 
@@ -917,12 +949,18 @@ int scan_resident_blocks()
 
 namespace {
 
-// k_scan_fast, or its k_scan_fix twin for a pass that repairs single-bit errors (ScanParams::fix); `ev`: the launch
-// carries the pass's events (hipExtLaunchKernelGGL)
+// k_scan_fast, or its k_scan_fix twin for a pass that repairs single-bit errors (ScanParams::fix), or k_scan_fix2 for
+// one that repairs two (fix == 3); `ev`: the launch carries the pass's events (hipExtLaunchKernelGGL)
 template <bool FROM_MAG, bool FUSED = false, bool FIELDS = false, bool U8 = false>
 void launch_fast(const ScanParams &p, uint32_t blocks, hipStream_t st, bool ev)
 {
-    if (p.fix) {
+    if (p.fix == 3u) {
+        if (ev)
+            hipExtLaunchKernelGGL((k_scan_fix2<FROM_MAG, FUSED, FIELDS, U8>), dim3(blocks), dim3(kThreads), 0, st,
+                                  (hipEvent_t)p.ev_start, (hipEvent_t)p.ev_stop, 0, p);
+        else
+            hipLaunchKernelGGL((k_scan_fix2<FROM_MAG, FUSED, FIELDS, U8>), dim3(blocks), dim3(kThreads), 0, st, p);
+    } else if (p.fix) {
         if (ev)
             hipExtLaunchKernelGGL((k_scan_fix<FROM_MAG, FUSED, FIELDS, U8>), dim3(blocks), dim3(kThreads), 0, st,
                                   (hipEvent_t)p.ev_start, (hipEvent_t)p.ev_stop, 0, p);

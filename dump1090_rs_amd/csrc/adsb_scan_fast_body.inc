@@ -1,7 +1,7 @@
-// adsb_scan_fast_body.inc -- the body of the fast scan's kernels, k_scan_fast and k_scan_fix (adsb_scan_fast.hip),
-// included into each of them; not a header.  In scope: the kernel's template parameters FROM_MAG, SELFTEST, FUSED,
-// FIELDS, U8, its `p` and LDS (s, fs, hf), the constexpr flag FIX and `fixt` (the single-bit repair table in LDS when
-// FIX, else null).
+// adsb_scan_fast_body.inc -- the body of the fast scan's kernels, k_scan_fast, k_scan_fix and k_scan_fix2
+// (adsb_scan_fast.hip), included into each of them; not a header.  In scope: the kernel's template parameters FROM_MAG,
+// SELFTEST, FUSED, FIELDS, U8, its `p` and LDS (s, fs, hf), the constexpr flags FIX and FIX2 and `fixt` (the
+// single-bit repair table in LDS when FIX, else null).
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const uint32_t n_tiles = p.n_chunks * kTilesPerChunk;
@@ -46,6 +46,14 @@
     if constexpr (FIX) {   // (read by the trials, behind the first tile's barriers)
         for (int i = tid; i < kFixSlots; i += kThreads) fixt[i] = p.tables[kTabFixOff + i];
         fix_mult = p.tables[kTabFixOff + kFixSlots];
+    }
+    // FIX2: the pair table stays in global memory (L2); only its two multipliers are read here
+    const uint4 *fix2 = nullptr;
+    uint32_t fix2_m0 = 0, fix2_m1 = 0;
+    if constexpr (FIX2) {
+        fix2_m0 = p.tables[kTabFix2Off];
+        fix2_m1 = p.tables[kTabFix2Off + 1];
+        fix2 = (const uint4 *)(p.tables + kTabFix2Off + 4);
     }
     if constexpr (U8) {   // the widening table, read by P1 of the first tile already
         for (int i = tid; i < 256; i += kThreads) u8_table_lds()[i] = (float)(int16_t)p.u8_table[i];
@@ -413,8 +421,8 @@
                 const uint32_t t5 = tb + (uint32_t)lane;
                 uint32_t c, tpi;
                 split5(min(t5, ntrial - 1u), c, tpi);
-                trial_pass<FUSED, FIELDS, FIX>(p, s, hf, cand_entry(wcand[c]), tpi, t5 < ntrial, jbase, chunk, seg, seg_cap, ap_count,
-                                               lane, par, fixt, fix_mult);
+                trial_pass<FUSED, FIELDS, FIX, FIX2>(p, s, hf, cand_entry(wcand[c]), tpi, t5 < ntrial, jbase, chunk, seg, seg_cap,
+                                                     ap_count, lane, par, fixt, fix_mult, fix2, fix2_m0, fix2_m1);
             }
             wave_lds_fence();  // wcand is reused by the next passes of the gates
         }

@@ -57,8 +57,9 @@ __device__ __forceinline__ void load_tile(const ScanParams &p, uint64_t chunk, i
 
 // FIX: single-bit repair of DF17/18 (ScanParams::fix): a residual that is the syndrome of one bit in 5..111 --
 // x^(111-b), the per-bit residual constants of adsb_tables.h -- makes a hit too (found by a plain walk: this kernel
-// is the cold path)
-template <bool FROM_MAG, bool FIX>
+// is the cold path).  FIX2 (fix == 3): on a miss, the residual c goes into the scan's domain, H' = x^-56 c (56 steps),
+// and is looked up in the pair table (adsb_tables.h: build_fix2_table) -- two buckets, as in k_scan_fix2.
+template <bool FROM_MAG, bool FIX, bool FIX2 = false>
 __device__ __forceinline__ void scan_simple_tile(const ScanParams &p, uint32_t chunk, int jbase,
                                                  int jn, int len, uint16_t *smag, uint32_t *scrc,
                                                  uint16_t *scand, uint32_t *sncand)
@@ -111,6 +112,15 @@ __device__ __forceinline__ void scan_simple_tile(const ScanParams &p, uint32_t c
                         if (df == 17) bitmap_set(p.bitmap, p.bitmap_lg, addr);
                     } else if (FIX) {   // (a repaired trial adds nothing)
                         for (int b = kFixFirstBit; b < 112 && !is_hit; b++) is_hit = p.tables[kTabBitsOff + b] == c;
+                        if (FIX2 && !is_hit) {
+                            uint32_t h = c;
+                            for (int e = 0; e < 56; e++) h = (h & 1u) ? ((h ^ 0xFFF409u) >> 1) | 0x800000u : h >> 1;
+                            const uint32_t *t = p.tables + kTabFix2Off;
+                            for (int i = 0; i < 2 && !is_hit; i++) {
+                                const uint32_t *bk = t + 4 + 4 * ((h * t[i]) >> (32 - kFix2Lg));
+                                is_hit = (bk[0] & 0xFFFFFFu) == h || (bk[2] & 0xFFFFFFu) == h;
+                            }
+                        }
                         if (is_hit) entry = pack_entry(c, code, j, chunk);
                     }
                 } else if (df == 0 || df == 4 || df == 5) {  // :56-72
@@ -144,6 +154,22 @@ __global__ __launch_bounds__(256) void k_scan_simple(ScanParams p)
                                &sncand);
 }
 
+// ... with two-bit repair (ScanParams::fix == 3): a kernel of its own, so that the others stay as they are
+template <bool FROM_MAG>
+__global__ __launch_bounds__(256) void k_scan_simple_fix2(ScanParams p)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t smag[kSlots];
+    __shared__ uint32_t scrc[256];
+    __shared__ uint16_t scand[kTile];
+    __shared__ uint32_t sncand;
+
+    const uint32_t chunk = blockIdx.x / kTilesPerChunk;
+    const int jbase = (int)(blockIdx.x % kTilesPerChunk) * kTile;
+    const int len = FROM_MAG ? (int)p.n_samples : chunk_len(p.n_samples, chunk);
+    if (jbase >= len) return;
+    scan_simple_tile<FROM_MAG, true, true>(p, chunk, jbase, min(kTile, len - jbase), len, smag, scrc, scand, &sncand);
+}
+
 inline int hip_ok(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 // hipGetLastError is sticky across unrelated calls (the caller's too): start every launch clean
 inline void hip_clear() { (void)hipGetLastError(); }
@@ -157,7 +183,10 @@ int launch_scan_simple(const ScanParams &p, SrcFormat fmt, void *stream)
     if (fmt == SrcFormat::kCu8) return (int)hipErrorInvalidValue;
     const uint32_t blocks = p.n_chunks * kTilesPerChunk;
     if (blocks == 0) return 0;
-    if (fmt == SrcFormat::kMag && p.fix)
+    if (p.fix == 3u)
+        hipLaunchKernelGGL(fmt == SrcFormat::kMag ? k_scan_simple_fix2<true> : k_scan_simple_fix2<false>, dim3(blocks), dim3(256), 0,
+                           (hipStream_t)stream, p);
+    else if (fmt == SrcFormat::kMag && p.fix)
         hipLaunchKernelGGL((k_scan_simple<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     else if (fmt == SrcFormat::kMag)
         hipLaunchKernelGGL(k_scan_simple<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);

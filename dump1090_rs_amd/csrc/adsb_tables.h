@@ -141,6 +141,77 @@ inline std::vector<uint32_t> build_fix_table(uint32_t *mult_out)
     }
 }
 
+// Two-bit repair of DF17/18 (ADSB_FIX_2BIT) on the device: the 5671 pairs 5 <= a < b <= 111, keyed in the same
+// domain, H'(a) ^ H'(b) = x^(55-a) + x^(55-b) (distinct, non-zero, and never a single bit's key: tests/test_fix2_cpu.py).
+// Too many for LDS at the scan's occupancy, so the table lives in global memory (128 KB, which stays in L2) as a
+// two-choice cuckoo hash: kFix2Buckets buckets of two 8-byte entries, one 16-byte load each; a key sits in bucket
+// (key * mult_i) >> (32 - kFix2Lg) for i = 0 or 1.  A lookup is therefore exactly two independent 16-byte loads and
+// four compares -- the probe bound kFix2Probes, no loop.  Entry = {key | a << 24, residual | b << 24}, the residual
+// being syn(a) ^ syn(b) = x^(111-a) + x^(111-b), the value a repaired hit carries; {0, 0}: empty (no key is 0).
+// Words: mult_0, mult_1, 0, 0 (16-byte alignment), then the buckets.  Deterministic: the multipliers are the first
+// pair of a fixed xorshift sequence under which the insertions (in (a, b) order, evicting by a fixed rule) settle.
+constexpr int kFix2Lg = 13, kFix2Buckets = 1 << kFix2Lg, kFix2Ways = 2, kFix2Probes = 2 * kFix2Ways, kFix2Pairs = 5671;
+constexpr int kFix2Words = 4 + 4 * kFix2Buckets;
+
+inline uint32_t fix2_bucket(uint32_t key, uint32_t mult) { return (key * mult) >> (32 - kFix2Lg); }
+
+inline std::vector<uint32_t> build_fix2_table()
+{
+    std::vector<uint64_t> items;   // (key | a << 24) | (residual | b << 24) << 32
+    items.reserve(kFix2Pairs);
+    {
+        uint32_t key[112], res[112];
+        const std::vector<uint32_t> bits = build_bit_residuals();
+        for (int b = kFixFirstBit; b < 112; b++) key[b] = fix_key(b), res[b] = bits[b];
+        for (int a = kFixFirstBit; a < 112; a++)
+            for (int b = a + 1; b < 112; b++)
+                items.push_back((uint64_t)((key[a] ^ key[b]) | (uint32_t)a << 24) |
+                                (uint64_t)((res[a] ^ res[b]) | (uint32_t)b << 24) << 32);
+    }
+    uint32_t x = 0x9E3779B9u;
+    const auto next = [&x] {
+        x ^= x << 13;
+        x ^= x >> 17;
+        x ^= x << 5;
+        return x | 1u;
+    };
+    std::vector<uint64_t> slot((size_t)kFix2Buckets * kFix2Ways);
+    for (;;) {
+        const uint32_t m0 = next(), m1 = next();
+        std::fill(slot.begin(), slot.end(), 0ull);
+        bool ok = true;
+        for (size_t i = 0; i < items.size() && ok; i++) {
+            uint64_t cur = items[i];
+            uint32_t at = fix2_bucket((uint32_t)cur & 0xFFFFFFu, m0);
+            for (int kick = 0;; kick++) {
+                int w = 0;
+                while (w < kFix2Ways && slot[(size_t)at * kFix2Ways + w]) w++;
+                if (w < kFix2Ways) {
+                    slot[(size_t)at * kFix2Ways + w] = cur;
+                    break;
+                }
+                if (kick == 500) {
+                    ok = false;
+                    break;
+                }
+                // full: the entry in way (kick % ways) moves to its other bucket
+                std::swap(cur, slot[(size_t)at * kFix2Ways + kick % kFix2Ways]);
+                const uint32_t k = (uint32_t)cur & 0xFFFFFFu, b0 = fix2_bucket(k, m0);
+                at = b0 == at ? fix2_bucket(k, m1) : b0;
+            }
+        }
+        if (!ok) continue;
+        std::vector<uint32_t> t(kFix2Words, 0u);
+        t[0] = m0;
+        t[1] = m1;
+        for (size_t s = 0; s < slot.size(); s++) {
+            t[4 + 2 * s] = (uint32_t)slot[s];
+            t[4 + 2 * s + 1] = (uint32_t)(slot[s] >> 32);
+        }
+        return t;
+    }
+}
+
 // Field addressing of the fast scan's trial phase.  Message bit n = 5k + r of trial phase
 // tp = 4 + tpi at a preamble whose LDS slot is 12*qs + rs sits in sign plane
 // (ph, res), bit qs + carry + k, with

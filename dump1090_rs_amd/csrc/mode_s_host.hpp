@@ -7,9 +7,11 @@
 // Semantics follow src/icao_filter.rs, src/crc.rs and src/mode_s/mod.rs; the state
 // is per-context instead of process-global.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 namespace adsb {
 
@@ -99,8 +101,8 @@ struct Crc24 {
         return rem ^ (uint32_t(m[nbytes - 3]) << 16 | uint32_t(m[nbytes - 2]) << 8 | m[nbytes - 1]);
     }
 
-    // Single-bit error correction of DF17/18 (adsb_set_error_correction): off (0, the reference) or 1 (ADSB_FIX_1BIT).
-    // The one scoring option there is; it rides along with the table because every replay is handed both.
+    // Error correction of DF17/18 (adsb_set_error_correction): off (0, the reference), 1 (ADSB_FIX_1BIT) or 3
+    // (ADSB_FIX_2BIT).  The one scoring option there is; it rides along with the table because every replay is handed both.
     int fix = 0;
     // syn112[b]: the residual of the 112-bit message with only bit b set (bit 0 = MSB of byte 0)
     uint32_t syn112[112];
@@ -113,13 +115,30 @@ struct Crc24 {
             e[b >> 3] = uint8_t(0x80u >> (b & 7));
             syn112[b] = residual(e, 14);
         }
+        // ADSB_FIX_2BIT: syn(a) ^ syn(b) << 16 | a << 8 | b for 5 <= a < b <= 111, sorted (the 5671 values are distinct,
+        // non-zero and none is a single bit's: tests/test_fix2_cpu.py), built once here
+        pairs.clear();
+        if (mode == 3) {
+            pairs.reserve(5671);
+            for (int a = 5; a < 112; a++)
+                for (int b = a + 1; b < 112; b++)
+                    pairs.push_back(uint64_t(syn112[a] ^ syn112[b]) << 16 | uint64_t(a) << 8 | uint64_t(b));
+            std::sort(pairs.begin(), pairs.end());
+        }
     }
+    std::vector<uint64_t> pairs;
     // the bit in 5..111 whose syndrome `c` is (they are distinct: tests/test_fix_cpu.py), else -1; bits 0..4 are the DF
     int fix_bit(uint32_t c) const
     {
         for (int b = 5; b < 112; b++)
             if (syn112[b] == c) return b;
         return -1;
+    }
+    // the bits a < b in 5..111 whose syndromes XOR to `c` (mode 3 only), as a << 8 | b; else -1
+    int fix_pair(uint32_t c) const
+    {
+        const auto it = std::lower_bound(pairs.begin(), pairs.end(), uint64_t(c) << 16);
+        return it != pairs.end() && (*it >> 16) == c ? int(*it & 0xFFFFu) : -1;
     }
 };
 
@@ -128,7 +147,15 @@ struct Score {
     int len;      // 7 | 14
     int32_t value;
     int fix_bit = -1;   // >= 0: a DF17/18 repaired by flipping this message bit (ADSB_FIX_1BIT, scored 1200 or -1)
+    int fix_bit2 = -1;  // >= 0: ... and this one too (ADSB_FIX_2BIT, scored 1100 or -1)
 };
+
+// a repaired message's bytes: the bits a Score flipped, flipped back
+inline void apply_fix(const Score &s, uint8_t msg[14])
+{
+    if (s.fix_bit >= 0) msg[s.fix_bit >> 3] ^= (uint8_t)(0x80u >> (s.fix_bit & 7));
+    if (s.fix_bit2 >= 0) msg[s.fix_bit2 >> 3] ^= (uint8_t)(0x80u >> (s.fix_bit2 & 7));
+}
 
 // src/mode_s/mod.rs:34-139 on a 14-byte trial message whose CRC residual (over its own length:
 // 14 bytes for DF >= 16, else 7) is already known.
@@ -180,10 +207,19 @@ inline Score score_modes_message(Filter &filter, uint32_t residual, const uint8_
             // ADSB_FIX_1BIT: a residual that is the syndrome of one bit in 5..111 is that bit flipped.  The repaired
             // address is tested (DF18 too, with the plain address) and never added; `hash` is the damaged
             // address's, so it is not used.
-            const int b = fixer && fixer->fix == 1 ? fixer->fix_bit(c) : -1;
+            const int b = fixer && (fixer->fix & 1) ? fixer->fix_bit(c) : -1;
             if (b >= 0) {
                 const uint32_t fixed = (b >= 8 && b < 32) ? addr ^ (1u << (31 - b)) : addr;
                 return {true, len, filter.test(fixed, IcaoFilter::hash(fixed)) ? 1200 : -1, b};
+            }
+            // ADSB_FIX_2BIT: ... else a residual that is syn(a) ^ syn(b), 5 <= a < b <= 111, is those two bits
+            // flipped (no residual names both a single bit and a pair), tested the same way, scored 1100
+            const int ab = b < 0 && fixer && fixer->fix == 3 ? fixer->fix_pair(c) : -1;
+            if (ab >= 0) {
+                uint32_t fixed = addr;
+                for (const int k : {ab >> 8, ab & 0xFF})
+                    if (k >= 8 && k < 32) fixed ^= 1u << (31 - k);
+                return {true, len, filter.test(fixed, IcaoFilter::hash(fixed)) ? 1100 : -1, ab >> 8, ab & 0xFF};
             }
         } else if (filter.test(addr, h)) {
             v = 1800;

@@ -173,7 +173,8 @@ class MultiContext:
         self._check(self._L.adsb_multi_set_timeout_ms(self._h, int(ms)), "adsb_multi_set_timeout_ms")
 
     def set_error_correction(self, mode: int) -> None:
-        """adsb_multi_set_error_correction: the mode of every device context and of the collector's replay."""
+        """adsb_multi_set_error_correction: the mode of every device context and of the collector's replay
+        (_lib.ADSB_FIX_NONE, _lib.ADSB_FIX_1BIT or _lib.ADSB_FIX_2BIT, as Context.set_error_correction)."""
         self._check(self._L.adsb_multi_set_error_correction(self._h, int(mode)), "adsb_multi_set_error_correction")
 
     def selftest_fail(self, captures_from_now: int, shard: int, kind: int) -> None:

@@ -313,6 +313,17 @@ int adsb_set_carry_over(adsb_ctx *ctx, int enabled);
 #define ADSB_FIX_NONE 0
 #define ADSB_FIX_1BIT 1
 #define ADSB_SCORE_FIXED_1BIT 1200
+/* ADSB_FIX_2BIT repairs one OR two flipped bits (1 | 2: a superset of ADSB_FIX_1BIT; the value 2 is ADSB_ERR_INVALID
+ * everywhere), as upstream C dump1090's --aggressive does.  It changes the same branch, DF 17 / 18 with c != 0:
+ *   if c == syn(b) for b in 5..111, the trial is scored exactly as under ADSB_FIX_1BIT (1200 or -1);
+ *   else if c == syn(a) ^ syn(b) for 5 <= a < b <= 111, m' = msg ^ e_a ^ e_b, addr' = bits 9..32 of m', and the trial
+ *   scores ADSB_SCORE_FIXED_2BIT if icao_filter_test(addr') (DF18 too, with the plain address), else -1, and adds
+ *   nothing to the filter; any other c still scores -2.
+ * The 5671 pair syndromes are distinct, non-zero and none is a single bit's, so c names at most one repair.  1100 sits
+ * below a single-bit repair (1200), above address/parity (1000), and occurs nowhere in the reference or mode 1; the
+ * msg of a 1100 message holds the corrected bytes.  It reaches every entry point ADSB_FIX_1BIT does. */
+#define ADSB_FIX_2BIT 3
+#define ADSB_SCORE_FIXED_2BIT 1100
 int adsb_set_error_correction(adsb_ctx *ctx, int mode);
 int adsb_get_error_correction(const adsb_ctx *ctx);
 
@@ -484,6 +495,12 @@ int adsb_selftest_fix_table(uint32_t *syn112);
  * holds a 112-bit trial's residual), slot = (H' * *mult) >> 23 of 512 (`cap` >= 512), entry = H' | b << 24, 0 empty.
  * Host only, no context: for the test that it is collision-free and complete. */
 int adsb_selftest_fix_hash(uint32_t *mult, uint32_t *table, size_t cap);
+/* ... and the pair table of ADSB_FIX_2BIT, which the scan kernels look up in global memory: keyed by
+ * H'(a) ^ H'(b) = x^(55-a) + x^(55-b), 2^params4[2] buckets of two entries {key | a << 24, (syn(a) ^ syn(b)) | b << 24}
+ * (4 u32 a bucket, {0, 0} empty); a key sits in bucket (key * params4[i]) >> (32 - params4[2]) for i = 0 or 1, so a
+ * lookup reads params4[3] = 4 entries at most.  `buckets` gets 4 << params4[2] u32 (`cap` >= 32768).  Host only, no
+ * context: for the test that it is complete and that no key sits outside its buckets. */
+int adsb_selftest_fix2_table(uint32_t *params4, uint32_t *buckets, size_t cap);
 
 /* Device self-test: digest of the magnitude tail (sqrt, *65535+0.5, saturating
  * cast; src/utils.rs:54-55) over `count` consecutive f32 bit patterns of

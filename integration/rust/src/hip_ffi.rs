@@ -21,6 +21,8 @@ pub const ADSB_ERR_POISONED: c_int = -8;
 pub const ADSB_FIX_NONE: i32 = 0;
 pub const ADSB_FIX_1BIT: i32 = 1;
 pub const ADSB_SCORE_FIXED_1BIT: i32 = 1200;
+pub const ADSB_FIX_2BIT: i32 = 3;
+pub const ADSB_SCORE_FIXED_2BIT: i32 = 1100;
 
 /// `adsb_msg`: `ModeSMessage` (src/demod_2400.rs:92-102) + provenance.  40 bytes.
 #[repr(C)]
@@ -106,7 +108,7 @@ unsafe extern "C" {
     pub fn adsb_set_stream(ctx: *mut AdsbCtx, hip_stream: *mut c_void) -> c_int;
     pub fn adsb_set_profiling(ctx: *mut AdsbCtx, level: c_int) -> c_int;
     pub fn adsb_set_carry_over(ctx: *mut AdsbCtx, enabled: c_int) -> c_int; // opt-in, not the reference's semantics
-    pub fn adsb_set_error_correction(ctx: *mut AdsbCtx, mode: c_int) -> c_int; // opt-in: ADSB_FIX_1BIT
+    pub fn adsb_set_error_correction(ctx: *mut AdsbCtx, mode: c_int) -> c_int; // opt-in: ADSB_FIX_1BIT, ADSB_FIX_2BIT
     pub fn adsb_get_error_correction(ctx: *const AdsbCtx) -> c_int;
     pub fn adsb_icao_flush(ctx: *mut AdsbCtx) -> c_int;
     pub fn adsb_to_mag(ctx: *mut AdsbCtx, iq_re_im: *const i16, n: usize, data_out: *mut u16, length_out: *mut usize) -> c_int;
@@ -157,6 +159,7 @@ unsafe extern "C" {
     pub fn adsb_replay_records_fix(filter_table: *mut u32, records: *mut AdsbTrial, n: usize, mode: c_int, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_selftest_fix_table(syn112: *mut u32) -> c_int;
     pub fn adsb_selftest_fix_hash(mult: *mut u32, table: *mut u32, cap: usize) -> c_int;
+    pub fn adsb_selftest_fix2_table(params4: *mut u32, buckets: *mut u32, cap: usize) -> c_int;
     pub fn adsb_format_raw(msg: *const AdsbMsg, out: *mut c_char, out_size: usize) -> c_int;
     pub fn adsb_read_test_data(path: *const c_char, iq_re_im: *mut i16, max_samples: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_selftest_mag_digest(ctx: *mut AdsbCtx, first_bits: u32, count: u32, sum_out: *mut u64, xor_out: *mut u64) -> c_int;

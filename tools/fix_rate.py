@@ -1,14 +1,17 @@
-"""Single-bit repair (ADSB_FIX_1BIT) against no repair on the same samples, each result checked against the CPU
-restatement of its mode (tests/fix_restatement.c over the oracle).
+"""Single-bit (ADSB_FIX_1BIT) and two-bit (ADSB_FIX_2BIT) repair against no repair on the same samples, each result
+checked against the CPU restatement of its mode (tests/fix_restatement.c, tests/fix2_restatement.c over the oracle).
 
-    python tools/fix_rate.py [--out DIR] [--rounds R] [--seconds S]
+    python tools/fix_rate.py [--out DIR] [--rounds R] [--seconds S] [--noise-only]
 
-Shapes, each run with correction off and on in the same process, alternating round by round (R rounds, the median
-reported, the spread kept):
+Shapes, each run with correction off, 1bit and 2bit in the same process, alternating round by round (R rounds, the
+median reported, the spread kept):
   resident  BASELINE config 2's step: icao_flush + one blocking pass over 512 device-resident buffers, sparse (64
             bursts) and busy (5000 bursts); ms per step;
   config1   adsb_demod_iq of the one 131072-sample capture of config 1 from host memory, blocking; us per call;
   ring      a pinned CS16 ring of 16 buffers per slot, filled once, submitted and collected for S seconds; Gsample/s.
+  noise     (2bit only) 64 buffers of noise: the trials the device turned into two-bit hits per buffer (records of
+            mode 3 minus those of mode 1) next to the expectation, 5671 / 2^24 of the failed DF17/18 trials, and the
+            exact count (the oracle's trials whose residual is a pair syndrome).
 One JSON line per shape and mode goes to stdout and, with --out, is appended to DIR/fix_rate.jsonl.
 """
 from __future__ import annotations
@@ -23,6 +26,8 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 CHUNK = 131072
+MODES = (0, 1, 3)
+NAMES = {0: "none", 1: "1bit", 3: "2bit"}
 
 
 def keys(msgs):
@@ -30,8 +35,8 @@ def keys(msgs):
 
 
 def parity(iq, mode, got) -> bool:
-    from tests import fix_support as fs
-    return keys(got) == fs.Restated(mode).demod_iq(iq)
+    from tests import fix2_support as f2
+    return keys(got) == f2.Restated(mode).demod_iq(iq)
 
 
 def resident(torch, rounds, n_bursts):
@@ -43,13 +48,13 @@ def resident(torch, rounds, n_bursts):
     out = {}
     with Context(0, 512) as c:
         ok = {}
-        for mode in (0, 1):
+        for mode in MODES:
             c.set_error_correction(mode)
             c.icao_flush()
             ok[mode] = parity(iq, mode, c.demod_iq_device(d.data_ptr(), n, cap=1 << 20))
-        t = {0: [], 1: []}
+        t = {m: [] for m in MODES}
         for r in range(rounds):
-            for mode in (0, 1):
+            for mode in MODES:
                 c.set_error_correction(mode)
                 c.icao_flush()
                 c.demod_iq_device(d.data_ptr(), n, cap=1 << 20)   # warm-up: the stream's density
@@ -58,7 +63,7 @@ def resident(torch, rounds, n_bursts):
                     c.icao_flush()
                     c.demod_iq_device(d.data_ptr(), n, cap=1 << 20)
                 t[mode].append((time.perf_counter() - t0) / 10 * 1e3)
-        for mode in (0, 1):
+        for mode in MODES:
             out[mode] = {"ms_per_step": statistics.median(t[mode]), "spread": [min(t[mode]), max(t[mode])], "parity": ok[mode]}
     return out
 
@@ -70,20 +75,20 @@ def config1(rounds):
     out = {}
     with Context(0, 1) as c:
         ok = {}
-        for mode in (0, 1):
+        for mode in MODES:
             c.set_error_correction(mode)
             c.icao_flush()
             ok[mode] = parity(iq, mode, c.demod_iq(iq))
-        t = {0: [], 1: []}
+        t = {m: [] for m in MODES}
         for r in range(rounds):
-            for mode in (0, 1):
+            for mode in MODES:
                 c.set_error_correction(mode)
                 t0 = time.perf_counter()
                 for _ in range(200):
                     c.icao_flush()
                     c.demod_iq(iq)
                 t[mode].append((time.perf_counter() - t0) / 200 * 1e6)
-        for mode in (0, 1):
+        for mode in MODES:
             out[mode] = {"us_per_call": statistics.median(t[mode]), "spread": [min(t[mode]), max(t[mode])], "parity": ok[mode]}
     return out
 
@@ -97,7 +102,7 @@ def ring(rounds, seconds):
         c.ring_create(per * CHUNK)
         depth = c.max_in_flight()
         ok = {}
-        for mode in (0, 1):   # (every slot gets the capture once: the timed loop below submits it as it stands)
+        for mode in MODES:   # (every slot gets the capture once: the timed loop below submits it as it stands)
             c.set_error_correction(mode)
             for _ in range(depth):
                 c.icao_flush()
@@ -105,9 +110,9 @@ def ring(rounds, seconds):
                 buf[:] = iq
                 c.ring_submit(len(iq))
                 ok[mode] = parity(iq, mode, c.collect()) and ok.get(mode, True)
-        rate = {0: [], 1: []}
+        rate = {m: [] for m in MODES}
         for r in range(rounds):
-            for mode in (0, 1):
+            for mode in MODES:
                 c.set_error_correction(mode)
                 c.icao_flush()
                 done, t0 = 0, time.perf_counter()
@@ -121,10 +126,45 @@ def ring(rounds, seconds):
                     c.collect()
                     done += 1
                 rate[mode].append(done * len(iq) / (time.perf_counter() - t0) / 1e9)
-        for mode in (0, 1):
+        for mode in MODES:
             out[mode] = {"gsample_per_s": statistics.median(rate[mode]), "spread": [min(rate[mode]), max(rate[mode])],
                          "parity": ok[mode]}
     return out
+
+
+def noise(torch, n_buffers=64):
+    import numpy as np
+    from dump1090_rs_amd import Context, synth
+    from oracle import binding
+    from tests import fix2_support as f2
+    iq = np.concatenate([synth.noise_numpy(CHUNK, 9000 + k) for k in range(n_buffers)])
+    d = torch.from_numpy(iq).cuda()
+    torch.cuda.synchronize()
+    recs, ok = {}, True
+    with Context(0, n_buffers) as c:
+        for mode in (1, 3):
+            c.set_error_correction(mode)
+            c.icao_flush()
+            got = c.demod_iq_device(d.data_ptr(), len(iq), cap=1 << 20)
+            recs[mode] = c.stats()["n_records"]   # (adsb_stats: the counters of this call alone)
+            ok = parity(iq, mode, got) and ok
+    import ctypes as C
+    pairs = (C.c_uint32 * 5671)()
+    f2.restatement().fix2_pair_syndromes(pairs)
+    pair_set = set(pairs)
+    O = binding.lib()
+    failed = exact = 0
+    for k in range(n_buffers):
+        _, tr = binding.all_trials(np.ascontiguousarray(iq[k * CHUNK:(k + 1) * CHUNK]), k)
+        for m in tr["msg"]:
+            if (m[0] >> 3) in (17, 18):
+                r = O.orc_modes_checksum(bytes(m), 112)
+                failed += r != 0
+                exact += r in pair_set
+    return {"two_bit_hits_per_buffer": (recs[3] - recs[1]) / n_buffers, "exact_per_buffer": exact / n_buffers,
+            "two_bit_hits": recs[3] - recs[1], "exact": exact,
+            "failed_df1718_per_buffer": failed / n_buffers, "expected_per_buffer": failed * 5671 / 2 ** 24 / n_buffers,
+            "parity": ok}
 
 
 def main():
@@ -132,13 +172,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--noise-only", action="store_true", help="only the noise leg")
     a = ap.parse_args()
     import torch
     lines = []
-    for shape, res in (("resident_sparse", resident(torch, a.rounds, 64)), ("resident_5000", resident(torch, a.rounds, 5000)),
-                       ("config1", config1(a.rounds)), ("ring16", ring(a.rounds, a.seconds))):
-        for mode in (0, 1):
-            lines.append({"shape": shape, "fix": ["none", "1bit"][mode], **res[mode]})
+    shapes = () if a.noise_only else (("resident_sparse", lambda: resident(torch, a.rounds, 64)),
+                                      ("resident_5000", lambda: resident(torch, a.rounds, 5000)),
+                                      ("config1", lambda: config1(a.rounds)), ("ring16", lambda: ring(a.rounds, a.seconds)))
+    for shape, run in shapes:
+        res = run()
+        for mode in MODES:
+            lines.append({"shape": shape, "fix": NAMES[mode], **res[mode]})
+    lines.append({"shape": "noise64", "fix": "2bit", **noise(torch)})
     for ln in lines:
         print(json.dumps(ln))
     if a.out:
