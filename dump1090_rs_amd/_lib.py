@@ -160,6 +160,8 @@ def lib() -> C.CDLL:
     L.adsb_selftest_fix_hash.restype = C.c_int
     L.adsb_selftest_fix2_table.argtypes = [vp, vp, sz]
     L.adsb_selftest_fix2_table.restype = C.c_int
+    L.adsb_selftest_fix_lookup.argtypes = [vp, vp, sz, C.c_int, vp]
+    L.adsb_selftest_fix_lookup.restype = C.c_int
     L.adsb_selftest_parallel_replay_fix.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, C.POINTER(sz),
                                                     C.POINTER(C.c_int)]
     L.adsb_selftest_parallel_replay_fix.restype = C.c_int

@@ -303,6 +303,15 @@ class Context:
             self._check(st, "adsb_selftest_stage_lists")
             return cand[: nc.value].copy(), ap[: na.value].copy()
 
+    def selftest_fix_lookup(self, residuals, mode: int) -> np.ndarray:
+        """adsb_selftest_fix_lookup: per CRC residual the repair the scoring kernels find under `mode`, as a | b << 8
+        (0xFF | b << 8: the single bit b; 0xFFFF: none)."""
+        r = np.ascontiguousarray(residuals, dtype=np.uint32)
+        out = np.zeros(r.shape[0], dtype=np.uint32)
+        self._check(self._L.adsb_selftest_fix_lookup(self._h, r.ctypes.data, r.shape[0], int(mode), out.ctypes.data),
+                    "adsb_selftest_fix_lookup")
+        return out
+
     def selftest_gate_stages(self, device_ptr: int, n_samples: int):
         """adsb_selftest_gate_stages: (positions where check_preamble returns Some, those that also pass
         the 3.5 dB test), both as buffer << 32 | j, ascending u64 arrays."""

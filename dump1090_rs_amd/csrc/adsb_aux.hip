@@ -6,6 +6,7 @@
 #include "adsb_dev_common.h"
 #include "adsb_scan_geometry.h"
 #include "adsb_tail_dev.h"
+#include "adsb_fix_dev.h"
 
 namespace adsb {
 
@@ -253,8 +254,30 @@ __device__ __forceinline__ bool score_in_filter(const ScoreDev &sd, uint32_t v, 
     return score_hash_first(sd, v) < i;
 }
 
+// A trial the record builder left unclassified (kSkOther) in a pass that repairs (ScanParams::fix, include/adsb_hip.h:
+// adsb_set_error_correction): a DF17/18 whose residual c -- bits 40..63 of its record's `power` -- names one flipped bit,
+// or (mode 3) two, scores 1200 / 1100 when the REPAIRED address is in the filter at that moment (DF18 too, with the
+// plain address), else -1; it adds nothing and is no adder in the hash.  `damaged`: the address field as sliced.
+// Everything else stays -2.  Only such trials come here: the common kinds never see the lookup.
+// *repair: the bits found, a | b << 8 (k_emit flips them; it gets them through ScoreDev::flag and looks nothing up).
+__device__ __forceinline__ int score_repair(const ScoreDev &sd, uint32_t i, uint32_t damaged, const uint32_t *tables, uint32_t fix,
+                                            uint32_t *repair)
+{
+    const TrialRecord &r = sd.rec[i];
+    const uint32_t df = (uint32_t)r.msg[0] >> 3;
+    if (df != 17u && df != 18u) return -2;
+    const uint32_t ab = fix_lookup(tables, (uint32_t)(r.power >> 40), fix);
+    if (ab == kFixNoRepair) return -2;
+    *repair = ab;
+    const uint32_t a = ab & 0xFFu, b = ab >> 8;
+    const uint32_t addr = damaged ^ fix_addr_mask(a) ^ fix_addr_mask(b);
+    if (!score_in_filter(sd, addr, i)) return -1;
+    return a == kFixNoBit ? ADSB_SCORE_FIXED_1BIT : ADSB_SCORE_FIXED_2BIT;
+}
+
 // src/mode_s/mod.rs:56-135 for trial i; *adds: the value this trial hands to icao_filter_add (or 0)
-__device__ __forceinline__ int score_trial(const ScoreDev &sd, uint32_t i, uint32_t *adds)
+__device__ __forceinline__ int score_trial(const ScoreDev &sd, uint32_t i, uint32_t *adds, const uint32_t *tables, uint32_t fix,
+                                           uint32_t *repair)
 {
     const uint32_t w = sd.si[i], v = w & 0xFFFFFFu, kind = w >> 24;
     *adds = 0;
@@ -275,6 +298,7 @@ __device__ __forceinline__ int score_trial(const ScoreDev &sd, uint32_t i, uint3
         *adds = v | (1u << 25);                       // ICAO_FILTER_ADSB_NT, src/icao_filter.rs:6
         return 1400;
     case kSkNone: return -3;                          // the reference's None: never taken
+    case kSkOther: return fix ? score_repair(sd, i, v, tables, fix, repair) : -2;
     default: return -2;
     }
 }
@@ -295,13 +319,14 @@ __global__ __launch_bounds__(256) void k_score(ScanParams p)
         uint32_t g0 = i;
         while (g0 > 0 && i - g0 < 8 && sd.pos[g0 - 1] == pos) g0--;
         int best = -2, mine = -2;
-        uint32_t win = 0xFFFFFFFFu, my_add = 0;
+        uint32_t win = 0xFFFFFFFFu, my_add = 0, my_fix = kFixNoRepair;
         for (uint32_t k = g0; k < n && k < g0 + 16 && sd.pos[k] == pos; k++) {
-            uint32_t a;
-            const int s = score_trial(sd, k, &a);
+            uint32_t a, fx = kFixNoRepair;
+            const int s = score_trial(sd, k, &a, p.tables, p.fix, &fx);
             if (k == i) {
                 mine = s;
                 my_add = a;
+                my_fix = fx;
             }
             if (s > best) {
                 best = s;
@@ -309,7 +334,10 @@ __global__ __launch_bounds__(256) void k_score(ScanParams p)
             }
         }
         const bool emit = win == i && best >= 0;
-        sd.flag[i] = (emit ? 1u : 0u) | (my_add ? 2u : 0u) | ((uint32_t)(mine + 3) << 8);
+        // (a repaired trial's bits ride along above the score: b in bits 25..31, a -- kFixNoBit & 127 for a single bit,
+        // which its score tells apart -- in bits 19..24 and bit 2; zero for every other trial of a fix pass is never read)
+        const uint32_t fa = my_fix & 0x7Fu, fb = (my_fix >> 8) & 0x7Fu;
+        sd.flag[i] = (emit ? 1u : 0u) | (my_add ? 2u : 0u) | ((uint32_t)(mine + 3) << 8) | (fa >> 6) << 2 | (fa & 63u) << 19 | fb << 25;
         emits += emit;
         addc += my_add != 0;
     }
@@ -389,9 +417,25 @@ __global__ __launch_bounds__(256) void k_emit(ScanParams p)
             if (f & 1u) {
                 adsb_msg m;
                 for (int k = 0; k < 14; k++) m.msg[k] = r.msg[k];
+                m.score = (int32_t)((f >> 8) & 0x7FFu) - 3;
+                // a repaired message carries the corrected bytes (these two scores occur nowhere else; the bits k_score
+                // found are in the flag); the record in memory stays as sliced, with its residual: a host that cannot use
+                // this result repairs it itself
+                if (m.score == ADSB_SCORE_FIXED_1BIT || m.score == ADSB_SCORE_FIXED_2BIT) {
+                    const uint32_t fb = f >> 25, fa = m.score == ADSB_SCORE_FIXED_2BIT ? ((f >> 19) & 63u) | ((f >> 2) & 1u) << 6 : kFixNoBit;
+                    unsigned long long lo = 0, hi = 0;   // message bits 0..63, 64..111 (MSB first) to flip
+                    for (uint32_t k = 0; k < 2; k++) {
+                        const uint32_t bit = k ? fa : fb;
+                        if (bit < 64u) lo |= 1ull << (63u - bit);
+                        else if (bit < 112u) hi |= 1ull << (127u - bit);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; k++) m.msg[k] ^= (uint8_t)(lo >> (56 - 8 * k));
+#pragma unroll
+                    for (int k = 0; k < 6; k++) m.msg[8 + k] ^= (uint8_t)(hi >> (56 - 8 * k));
+                }
                 m.len = (r.msg[0] & 0x80) ? ADSB_MODES_LONG_MSG_BYTES : ADSB_MODES_SHORT_MSG_BYTES;
                 m.try_phase = (uint8_t)(r.j_tp >> 24);
-                m.score = (int32_t)(f >> 8) - 3;
                 m.j = r.j_tp & 0xFFFFFFu;
                 m.chunk = r.chunk;
                 // demod_2400.rs:191-198: the same three divisions, in this order
@@ -558,6 +602,14 @@ __global__ __launch_bounds__(256) void k_mag_digest(uint32_t first_bits, uint32_
     atomicXor(&out[1], h);
 }
 
+// self-test: the lookup k_score / k_emit repair with, over a list of residuals (adsb_selftest_fix_lookup)
+__global__ __launch_bounds__(256) void k_fix_lookup(const uint32_t *__restrict__ tables, const uint32_t *__restrict__ residuals,
+                                                    uint32_t n, uint32_t mode, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = fix_lookup(tables, residuals[i], mode);
+}
+
 inline int hip_ok(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 // hipGetLastError is sticky across unrelated calls (the caller's too): start every launch clean
 inline void hip_clear() { (void)hipGetLastError(); }
@@ -681,6 +733,14 @@ int launch_update_carry(const uint32_t *prev, const void *d_src, uint64_t n_samp
     }
     hipLaunchKernelGGL(k_update_carry, dim3(1), dim3(kCarrySamples), 0, (hipStream_t)stream, prev,
                        (const uint32_t *)d_src, (long long)n_samples, next);
+    return hip_ok(hipGetLastError());
+}
+
+int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream)
+{
+    hip_clear();
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_fix_lookup, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, tables, d_residuals, n, mode, d_out);
     return hip_ok(hipGetLastError());
 }
 

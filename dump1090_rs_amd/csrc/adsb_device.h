@@ -173,7 +173,8 @@ struct ScoreDev {
     uint32_t *si;                  // per hit: value24 | kind << 24
     TrialRecord *rec;              // per hit: the record (device copy)
     unsigned long long *pos;       // per hit: buffer << 24 | j (what groups the five trial phases of a position)
-    uint32_t *flag;                // per hit: bit 0 emit, bit 1 add; bits 8.. : score + 3
+    uint32_t *flag;                // per hit: bit 0 emit, bit 1 add; bits 8..18: score + 3; a repaired trial's flipped bits:
+                                   // b in bits 25..31, a in bits 19..24 and bit 2 (adsb_aux.hip: k_score)
     unsigned long long *hash;      // adders: (value << 32 | first index), ~0 = empty
     uint32_t hash_mask;
     uint32_t *slot;                // per hit: the hash slot its key sits in (adders), else 0xFFFFFFFF
@@ -267,8 +268,9 @@ struct ScanParams {
     // CU8 passes (the U8 instantiations): `src` holds 2 bytes per sample, widened through this int16_t[256] table
     // in device memory (adsb_set_u8_table).  Last, so that the CS16 instantiations see the layout they always had.
     const uint16_t *u8_table;
-    // 1: the pass repairs single-bit errors (adsb_set_error_correction): its scan is a fix instantiation (k_scan_fix,
-    // k_scan_simple<.., true>), whose DF17/18 trials with a repairable residual are hits.  After everything else.
+    // the pass's error-correction mode (adsb_set_error_correction: 0, 1 or 3).  Non-zero: its scan is a fix instantiation
+    // (k_scan_fix / k_scan_fix2, k_scan_simple<.., true> / k_scan_simple_fix2), whose DF17/18 trials with a repairable
+    // residual are hits, and k_score / k_emit score and repair those (adsb_fix_dev.h).  After everything else.
     uint32_t fix;
 };
 
@@ -339,5 +341,7 @@ int launch_set_addresses(const uint32_t *d_addrs, uint32_t n, uint32_t *bitmap, 
 int launch_update_carry(const uint32_t *prev, const void *d_src, uint64_t n_samples, uint32_t *next, void *stream,
                         const uint16_t *u8_table = nullptr);
 int launch_mag_digest(uint32_t first_bits, uint32_t count, unsigned long long *d_out, void *stream);
+// self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
+int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 
 }  // namespace adsb

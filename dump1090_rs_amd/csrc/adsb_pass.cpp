@@ -84,8 +84,8 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
     // scored; a small pass is all launch overhead and a sparse one leaves a few hundred records that
     // the host sorts and scores in no time; the worst-case lists of the fallback are the host's too.
     const bool order_on_device = !force_simple && n_chunks > kInlineTailChunks && sl.hits_cap == c->hits_cap && c->dense_mode;
-    // (k_score knows no repaired trials: a pass that repairs single-bit errors is scored by the host replay)
-    const bool score_on_device = order_on_device && c->score.si && c->crc.fix == ADSB_FIX_NONE;
+    // (in every error-correction mode: k_score / k_emit score and repair a fix pass's DF17/18 trials themselves)
+    const bool score_on_device = order_on_device && c->score.si;
     if (score_on_device && !c->exact_valid) {
         // the device's copy of the filter can only be rebuilt from the host's once every pass in
         // flight has been replayed: finish them now (their results wait for adsb_collect)

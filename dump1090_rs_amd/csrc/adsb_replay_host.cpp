@@ -438,9 +438,11 @@ void learned_addresses(const Crc24 &crc, const TrialRecord *rec, size_t n, std::
     for (size_t i = 0; i < n; i++) {
         const uint8_t *m = rec[i].msg;
         const uint32_t df = m[0] >> 3;
-        // (under ADSB_FIX_1BIT a repairable DF17 with a residual is listed too: it adds nothing, and the list only has
-        // to hold every address the replay can add -- the address bits it sets are a superset, matched exactly later)
-        const bool adds = df == 17 || (df == 11 && crc.residual(m, 7) == 0);
+        // (without error correction every DF17 that reaches a record is a clean one.  Under a fix mode the repairable ones
+        // are records too, and they add nothing: their damaged addresses stay out, because these lists are also what a
+        // device-scored shard takes for "in the filter" -- ScoreDev::earlier of the shards behind this one, and the
+        // capture's additions committed to the exact bitmap -- where a superset would know aircraft never heard)
+        const bool adds = (df == 17 && (crc.fix == 0 || record_residual(crc, rec[i]) == 0)) || (df == 11 && crc.residual(m, 7) == 0);
         if (adds) addrs.push_back(uint32_t(m[1]) << 16 | uint32_t(m[2]) << 8 | m[3]);
     }
 }

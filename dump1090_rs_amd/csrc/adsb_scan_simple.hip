@@ -8,6 +8,7 @@
 // input so dense that the fast scan's lists overflow: its lists hold the worst case of a
 // chunk (every position sliced).  Both input kinds: IQ, or a caller-supplied MagnitudeBuffer.
 #include "adsb_dev_common.h"
+#include "adsb_fix_dev.h"
 
 namespace adsb {
 
@@ -58,7 +59,7 @@ __device__ __forceinline__ void load_tile(const ScanParams &p, uint64_t chunk, i
 // FIX: single-bit repair of DF17/18 (ScanParams::fix): a residual that is the syndrome of one bit in 5..111 --
 // x^(111-b), the per-bit residual constants of adsb_tables.h -- makes a hit too (found by a plain walk: this kernel
 // is the cold path).  FIX2 (fix == 3): on a miss, the residual c goes into the scan's domain, H' = x^-56 c (56 steps),
-// and is looked up in the pair table (adsb_tables.h: build_fix2_table) -- two buckets, as in k_scan_fix2.
+// and is looked up in the pair table (adsb_fix_dev.h: fix2_probe) -- two buckets, as in k_scan_fix2.
 template <bool FROM_MAG, bool FIX, bool FIX2 = false>
 __device__ __forceinline__ void scan_simple_tile(const ScanParams &p, uint32_t chunk, int jbase,
                                                  int jn, int len, uint16_t *smag, uint32_t *scrc,
@@ -112,15 +113,7 @@ __device__ __forceinline__ void scan_simple_tile(const ScanParams &p, uint32_t c
                         if (df == 17) bitmap_set(p.bitmap, p.bitmap_lg, addr);
                     } else if (FIX) {   // (a repaired trial adds nothing)
                         for (int b = kFixFirstBit; b < 112 && !is_hit; b++) is_hit = p.tables[kTabBitsOff + b] == c;
-                        if (FIX2 && !is_hit) {
-                            uint32_t h = c;
-                            for (int e = 0; e < 56; e++) h = (h & 1u) ? ((h ^ 0xFFF409u) >> 1) | 0x800000u : h >> 1;
-                            const uint32_t *t = p.tables + kTabFix2Off;
-                            for (int i = 0; i < 2 && !is_hit; i++) {
-                                const uint32_t *bk = t + 4 + 4 * ((h * t[i]) >> (32 - kFix2Lg));
-                                is_hit = (bk[0] & 0xFFFFFFu) == h || (bk[2] & 0xFFFFFFu) == h;
-                            }
-                        }
+                        if (FIX2 && !is_hit) is_hit = fix2_probe(p.tables, fix_key_of_residual(c)) != kFixNoRepair;
                         if (is_hit) entry = pack_entry(c, code, j, chunk);
                     }
                 } else if (df == 0 || df == 4 || df == 5) {  // :56-72

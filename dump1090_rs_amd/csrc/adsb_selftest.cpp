@@ -151,6 +151,28 @@ try {
     return ADSB_OK;
 } ADSB_ABI_CATCH
 
+int adsb_selftest_fix_lookup(adsb_ctx *c, const uint32_t *residuals, size_t n, int mode, uint32_t *out)
+try {
+    if (!c || (!residuals && n) || (!out && n) || n > (size_t(1) << 24)) return ADSB_ERR_INVALID;
+    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT && mode != ADSB_FIX_2BIT) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
+    if (n == 0) return ADSB_OK;
+    ADSB_ON_DEVICE(c);
+    uint32_t *d_buf = nullptr;   // the residuals, then the answers
+    HIP_TRY(c, hipMalloc((void **)&d_buf, 2 * n * sizeof(uint32_t)));
+    const auto body = [&]() -> int {
+        HIP_TRY(c, hipMemcpyAsync(d_buf, residuals, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        if (int e = launch_fix_lookup(c->d_tables, d_buf, (uint32_t)n, (uint32_t)mode, d_buf + n, c->stream))
+            return fail(c, (hipError_t)e, "launch_fix_lookup");
+        HIP_TRY(c, hipMemcpyAsync(out, d_buf + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return ADSB_OK;
+    };
+    const int rc = body();
+    (void)hipFree(d_buf);
+    return rc;
+} ADSB_ABI_CATCH
+
 int adsb_selftest_stage_lists(adsb_ctx *c, const void *d_iq, size_t n_samples, uint64_t *cand, size_t cand_cap,
                               size_t *n_cand, uint64_t *ap, size_t ap_cap, size_t *n_ap)
 try {

@@ -166,8 +166,8 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
             c->shard_device_ordered++;
             // ... and scored on the device: k_score / k_emit behind the second phase's records kernel, against the
             // context's exact bitmap and the additions of the shards before this one (ScoreDev::earlier)
-            // (k_score knows no repaired trials: under ADSB_FIX_1BIT the host replays the shard)
-            if (c->shard_scoring && c->score.si && c->crc.fix == ADSB_FIX_NONE) {
+            // (in every error-correction mode: ScanParams::fix tells k_score / k_emit what to repair)
+            if (c->shard_scoring && c->score.si) {
                 job.scored = true;
                 p.score = sl.score;
                 p.score.exact = job.exact;

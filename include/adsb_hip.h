@@ -502,6 +502,14 @@ int adsb_selftest_fix_hash(uint32_t *mult, uint32_t *table, size_t cap);
  * context: for the test that it is complete and that no key sits outside its buckets. */
 int adsb_selftest_fix2_table(uint32_t *params4, uint32_t *buckets, size_t cap);
 
+/* Device self-test: the repair the scoring kernels find for each of `n` CRC residuals (24 bits) under `mode` (ADSB_FIX_NONE,
+ * ADSB_FIX_1BIT, ADSB_FIX_2BIT) -- the very device function k_score and k_emit repair with, over the context's tables.
+ * out[i] = a | b << 8: 0xFF | b << 8 when residuals[i] == syn(b), b in 5..111 (modes 1 and 3); a | b << 8 when it is
+ * syn(a) ^ syn(b), 5 <= a < b <= 111 (mode 3 only); 0xFFFF ("none") for everything else, zero included.  Lets a test sweep
+ * all 107 + 5671 syndromes and any number of non-syndromes without building IQ for each.  ADSB_ERR_BUSY while passes are
+ * pending; n <= 2^24. */
+int adsb_selftest_fix_lookup(adsb_ctx *ctx, const uint32_t *residuals, size_t n, int mode, uint32_t *out);
+
 /* Device self-test: digest of the magnitude tail (sqrt, *65535+0.5, saturating
  * cast; src/utils.rs:54-55) over `count` consecutive f32 bit patterns of
  * X = im^2 + rn(re^2) starting at `first_bits`.  sum = sum of the u16 outputs,
@@ -594,7 +602,8 @@ uint64_t adsb_host_sorts(const adsb_ctx *ctx);
 /* Diagnostic: how many collected passes the host scored itself (the ordered replay of
  * score_modes_message / best-of-5, src/mode_s/mod.rs:34-139, src/demod_2400.rs:184-207) instead of
  * taking the messages the device scored.  Passes of more than 16 buffers in a steady pipeline are
- * scored on the device against a device-resident copy of the ICAO filter; small passes, fallbacks,
+ * scored on the device against a device-resident copy of the ICAO filter -- in every error-correction mode: the
+ * device repairs the DF17/18 trials of an ADSB_FIX_1BIT / ADSB_FIX_2BIT pass itself --; small passes, fallbacks,
  * a filter close to its 4096 entries and the passes in flight behind any of those are not. */
 uint64_t adsb_host_replays(const adsb_ctx *ctx);
 /* Diagnostic: how many passes of a few buffers were run a second time.  Such a pass is a single launch

@@ -1,7 +1,7 @@
 """Single-bit (ADSB_FIX_1BIT) and two-bit (ADSB_FIX_2BIT) repair against no repair on the same samples, each result
 checked against the CPU restatement of its mode (tests/fix_restatement.c, tests/fix2_restatement.c over the oracle).
 
-    python tools/fix_rate.py [--out DIR] [--rounds R] [--seconds S] [--noise-only]
+    python tools/fix_rate.py [--out DIR] [--rounds R] [--seconds S] [--noise-only] [--pipelined-only] [--label TEXT]
 
 Shapes, each run with correction off, 1bit and 2bit in the same process, alternating round by round (R rounds, the
 median reported, the spread kept):
@@ -12,6 +12,12 @@ median reported, the spread kept):
   noise     (2bit only) 64 buffers of noise: the trials the device turned into two-bit hits per buffer (records of
             mode 3 minus those of mode 1) next to the expectation, 5671 / 2^24 of the failed DF17/18 trials, and the
             exact count (the oracle's trials whose residual is a pair syndrome).
+  pipelined BASELINE config 5's step in a steady pipeline: icao_flush + adsb_submit_iq_device of 512 resident buffers
+            with 5000 bursts, four passes in flight, collected in order through the C ABI into preallocated arrays; blocks
+            of 20 steps between fences, the three modes alternating block by block, at least 200 steps a mode; every
+            collected list compared byte for byte (outside the timed region) with one that equals the restatement; ms per
+            step (median of the blocks, their spread) and how many of the passes the host scored (adsb_host_replays).
+            --label names the build (the commit) in the line, so that two builds run on one box can be told apart.
 One JSON line per shape and mode goes to stdout and, with --out, is appended to DIR/fix_rate.jsonl.
 """
 from __future__ import annotations
@@ -132,6 +138,70 @@ def ring(rounds, seconds):
     return out
 
 
+def pipelined(torch, blocks=11, per_block=20, n_bursts=5000):
+    import ctypes as C
+    from dump1090_rs_amd import Context, synth
+    from dump1090_rs_amd._lib import AdsbMsg
+    from dump1090_rs_amd.context import ModeSMessage
+    n = 512 * CHUNK
+    d = synth.make_iq_torch(n, n_bursts=n_bursts, device="cuda")
+    iq = d.cpu().numpy()
+    torch.cuda.synchronize()
+    cap = 1 << 14
+    outs = [(AdsbMsg * cap)() for _ in range(per_block)]
+    counts = [C.c_size_t() for _ in range(per_block)]
+    out = {}
+    with Context(0, 512) as c:
+        L, h, ptr = c._L, c._h, C.c_void_p(d.data_ptr())
+        depth = c.max_in_flight()
+
+        def block():
+            """per_block steps, `depth` in flight; seconds between the fences"""
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            done = 0
+            for k in range(per_block):
+                if k >= depth:
+                    assert L.adsb_collect(h, outs[done], cap, C.byref(counts[done])) == 0
+                    done += 1
+                assert L.adsb_icao_flush(h) == 0 and L.adsb_submit_iq_device(h, ptr, n) == 0
+            while done < per_block:
+                assert L.adsb_collect(h, outs[done], cap, C.byref(counts[done])) == 0
+                done += 1
+            return time.perf_counter() - t0
+
+        want, ok = {}, {}
+        for mode in MODES:   # what every step of the mode must return: one list that equals the restatement
+            c.set_error_correction(mode)
+            c.icao_flush()
+            got = c.demod_iq_device(d.data_ptr(), n, cap=1 << 20)
+            ok[mode] = parity(iq, mode, got)
+            block()      # (the first pass told the context how dense the stream is: from here on the steady pipeline)
+            want[mode] = C.string_at(outs[per_block - 1], counts[per_block - 1].value * C.sizeof(AdsbMsg))
+            m = outs[per_block - 1]
+            last = [ModeSMessage(bytes(m[i].msg), int(m[i].len), float(m[i].signal_level), int(m[i].score), int(m[i].j),
+                                 int(m[i].try_phase), int(m[i].chunk)) for i in range(counts[per_block - 1].value)]
+            ok[mode] = ok[mode] and keys(last) == keys(got)
+        t = {m: [] for m in MODES}
+        replays = {m: 0 for m in MODES}
+        for b in range(blocks):
+            for mode in MODES:
+                c.set_error_correction(mode)
+                before = int(L.adsb_host_replays(h))
+                dt = block()
+                if b:    # (the first block of a mode: warm-up)
+                    t[mode].append(dt / per_block * 1e3)
+                    replays[mode] += int(L.adsb_host_replays(h)) - before
+                for k in range(per_block):
+                    ok[mode] = ok[mode] and C.string_at(outs[k], counts[k].value * C.sizeof(AdsbMsg)) == want[mode]
+        for mode in MODES:
+            out[mode] = {"ms_per_step": statistics.median(t[mode]), "spread": [min(t[mode]), max(t[mode])],
+                         "blocks": [round(x, 4) for x in t[mode]], "steps": per_block * len(t[mode]), "in_flight": depth,
+                         "host_scored_passes": replays[mode], "frames_per_step": len(want[mode]) // C.sizeof(AdsbMsg),
+                         "parity": ok[mode]}
+    return out
+
+
 def noise(torch, n_buffers=64):
     import numpy as np
     from dump1090_rs_amd import Context, synth
@@ -173,17 +243,23 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--noise-only", action="store_true", help="only the noise leg")
+    ap.add_argument("--pipelined-only", action="store_true", help="only the pipelined dense leg")
+    ap.add_argument("--label", default=None, help="what build this is (its commit), kept in every line")
     a = ap.parse_args()
     import torch
     lines = []
-    shapes = () if a.noise_only else (("resident_sparse", lambda: resident(torch, a.rounds, 64)),
+    shapes = () if a.noise_only else (("pipelined_5000", lambda: pipelined(torch)),) if a.pipelined_only else (("resident_sparse", lambda: resident(torch, a.rounds, 64)),
                                       ("resident_5000", lambda: resident(torch, a.rounds, 5000)),
-                                      ("config1", lambda: config1(a.rounds)), ("ring16", lambda: ring(a.rounds, a.seconds)))
+                                      ("config1", lambda: config1(a.rounds)), ("ring16", lambda: ring(a.rounds, a.seconds)),
+                                      ("pipelined_5000", lambda: pipelined(torch)))
     for shape, run in shapes:
         res = run()
         for mode in MODES:
             lines.append({"shape": shape, "fix": NAMES[mode], **res[mode]})
-    lines.append({"shape": "noise64", "fix": "2bit", **noise(torch)})
+    if not a.pipelined_only:
+        lines.append({"shape": "noise64", "fix": "2bit", **noise(torch)})
+    if a.label:
+        lines = [{**ln, "build": a.label} for ln in lines]
     for ln in lines:
         print(json.dumps(ln))
     if a.out:
