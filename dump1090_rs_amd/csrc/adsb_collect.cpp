@@ -230,10 +230,11 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         HIP_TRY(c, hipStreamSynchronize(c->score_stream));
         const bool keep_flush = c->flush_pending;
         c->flush_pending = false;
+        PassOptions redo;   // three launches, blocking, on the input it already read
+        redo.redo = redo.inline_tail = redo.no_fuse = true;
+        redo.input_done = input_ready_now();
         rc = reseed_bitmap_from_filter(c);
-        if (rc == 0)
-            rc = enqueue_pass(c, sl, sl.src, sl.fmt, sl.n_samples, sl.n_chunks, true, false, false, false,
-                              input_ready_now(), true);
+        if (rc == 0) rc = enqueue_pass(c, sl, sl.src, sl.fmt, sl.n_samples, sl.n_chunks, redo);
         if (rc == 0) rc = finish_pass(c, sl, 0, st, out);
         c->flush_pending = keep_flush;
     }
@@ -248,7 +249,9 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         Slot tmp;
         rc = fallback_slot(c, sl, tmp);
         if (rc == 0) rc = reseed_bitmap_from_filter(c);
-        if (rc == 0) rc = enqueue_pass(c, tmp, sl.src, SrcFormat::kMag, sl.n_samples, 1, false, false, false, true);
+        PassOptions slow;   // the reference-shaped kernel into the worst-case lists
+        slow.redo = slow.force_simple = true;
+        if (rc == 0) rc = enqueue_pass(c, tmp, sl.src, SrcFormat::kMag, sl.n_samples, 1, slow);
         if (rc == 0) rc = finish_pass(c, tmp, 0, st, out);
         c->flush_pending = keep_flush;
     } else if (rc > 0) {
@@ -265,6 +268,9 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         for (uint64_t ch = 0; ch < sl.n_chunks && rc == 0; ch++) {
             const uint64_t off = ch * kChunkSamples;
             const uint64_t n = std::min<uint64_t>(kChunkSamples, sl.n_samples - off);
+            PassOptions slow;
+            slow.redo = slow.force_simple = true;
+            slow.lead_from_src = ch > 0;
             // (carry-over mode: buffers after the first find their lead-in in src itself; the
             // carry for the next call was already taken when the pass was first enqueued)
             // the reference-shaped kernel: its lists hold the worst case of a chunk
@@ -281,9 +287,9 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
                 if (rc == 0)
                     if (hipError_t e = hipStreamSynchronize(c->scan_stream[0])) rc = fail(c, e, "hipStreamSynchronize");
                 if (rc == 0)
-                    rc = enqueue_pass(c, tmp, c->d_widen + lead, SrcFormat::kCs16, n, 1, false, ch > 0, false, true);
+                    rc = enqueue_pass(c, tmp, c->d_widen + lead, SrcFormat::kCs16, n, 1, slow);
             } else {
-                rc = enqueue_pass(c, tmp, (const uint32_t *)sl.src + off, SrcFormat::kCs16, n, 1, false, ch > 0, false, true);
+                rc = enqueue_pass(c, tmp, (const uint32_t *)sl.src + off, SrcFormat::kCs16, n, 1, slow);
             }
             if (rc == 0) rc = finish_pass(c, tmp, ch, st, out);
         }

@@ -3,7 +3,7 @@
 //
 //   adsb_context.cpp   create / destroy, the stream pool, settings, diagnostics
 //   adsb_pass.cpp      one device pass: what is enqueued on which stream, and every cross-stream edge
-//                      (DESIGN.md section 5b lists them), submit, the blocking entry points
+//                      (docs/HISTORY.md section 5b lists them), submit, the blocking entry points
 //   adsb_collect.cpp   waiting for a pass, checksums, the overflow fallback
 //   adsb_replay_host.cpp  the ordered host replay and the other host-only entry points (no HIP: also built by g++ under sanitizers)
 //   adsb_ring.cpp      the pinned streaming ring
@@ -363,21 +363,45 @@ struct HostTimer {
 // adsb_pass.cpp
 int ensure_fallback(adsb_ctx *c);
 int fallback_slot(adsb_ctx *c, const Slot &sl, Slot &tmp);
-// input_done: the event behind which the input is complete; kInputReadyNow: it already is (host-visible
-// pinned memory the caller has filled); null: wherever `stream` stands now.  no_fuse: three launches even
-// for a pass of a few buffers.
 inline hipEvent_t input_ready_now() { return reinterpret_cast<hipEvent_t>(static_cast<uintptr_t>(1)); }
+// How enqueue_pass is asked to run a pass (default: a fresh, pipelined pass whose input is complete where `stream` stands).
+struct PassOptions {
+    bool inline_tail = false;     // the tail stays on the scan stream (a blocking call has nothing to overlap with)
+    bool lead_from_src = false;   // the lead-in is in front of `d_src` itself (ScanParams::lead_from_src)
+    bool redo = false;            // collect_oldest runs the pass again (overflow fallback, rematch): it keeps its number, takes
+                                  // no carry and stays on the first scan stream
+    bool force_simple = false;    // the reference-shaped kernel (worst-case lists: fallback_slot() came first)
+    bool no_fuse = false;         // three launches even for a pass of a few buffers
+    hipEvent_t input_done = nullptr;   // the event behind which the input is complete; input_ready_now(): it already is
+                                       // (host-visible pinned memory the caller has filled); null: wherever `stream` stands now
+};
 bool one_launch_pass(const adsb_ctx *c, uint32_t n_chunks);
 hipStream_t next_scan_stream(const adsb_ctx *c, uint32_t n_chunks);
 int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64_t n_samples, uint32_t n_chunks,
-                 bool inline_tail = false, bool lead_from_src = false, bool advance_carry = true,
-                 bool force_simple = false, hipEvent_t input_done = nullptr, bool no_fuse = false);
+                 const PassOptions &opt);
+// `waiter` continues behind everything `ahead` holds now (no-op when there is no `ahead` or the two are one stream)
+int put_behind(adsb_ctx *c, hipStream_t waiter, hipStream_t ahead);
+// Edge "in": scan stream `ss` (scan_stream[si]) behind its input -- complete at `input_done`, or (null) where `stream` stands
+int order_behind_input(adsb_ctx *c, hipEvent_t input_done, int si, hipStream_t ss);
 int wait_for_tail_of(adsb_ctx *c, hipStream_t waiter, Slot &other);
-// The blocking entry points that launch on `stream` with slot 0's lists and counters without enqueue_pass (shard
-// phases, self-tests): behind the one-launch pass that used the slot last, whose summary reaches the host a
-// moment before its last workgroup has zeroed the counters (edge 0 of DESIGN.md section 5b).
+// Edge 0 of docs/HISTORY.md section 5b: `waiter` is about to use the slot's lists and counters -- behind the one-launch
+// pass that used them last, whose summary reaches the host a moment before its last workgroup has zeroed the counters.
+// (enqueue_pass, the shard phases, and the blocking entry points that launch on `stream` with slot 0's lists.)
 int order_behind_fused(adsb_ctx *c, Slot &sl, hipStream_t waiter);
 inline int order_behind_slot0(adsb_ctx *c) { return order_behind_fused(c, c->slot[0], c->stream); }
+// What the ScanParams of every pass and every shard phase have in common (adsb_pass.cpp):
+// the fields that depend on the context and the slot alone, and the address bitmap -- rotated first when an icao_flush is
+// pending (c->flush_pending stays for the caller to consume).  Full bitmaps: *retired is the one to clean behind the
+// passes still matching against it; folded ones: *clear_next says the new one has to be cleared before its first use.
+void pass_params(adsb_ctx *c, const Slot &sl, ScanParams &p, uint32_t **retired, uint32_t *clear_next);
+// ... the slot's scoring buffers and outputs, against `exact` (`exact_retired`: the exact bitmap a flush retired, or null)
+void wire_score(const Slot &sl, ScanParams &p, uint32_t *exact, uint32_t *exact_retired);
+// ... and a fresh sequence number for the summary the launches about to go out will publish (`scored`: k_emit's too)
+uint32_t next_seq(adsb_ctx *c);
+void stamp_seq(adsb_ctx *c, Slot &sl, ScanParams &p, bool scored = false);
+// the 24-bit addresses in the host's filter table / room for n addresses in c->d_addrs (`alloc` entries when it has to grow)
+std::vector<uint32_t> filter_addresses(const adsb_ctx *c);
+int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc);
 int resync_exact(adsb_ctx *c);
 int reseed_bitmap_from_filter(adsb_ctx *c);
 int submit(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, bool inline_tail = false,

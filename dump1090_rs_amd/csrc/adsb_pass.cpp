@@ -1,5 +1,5 @@
 // adsb_pass.cpp -- one device pass: what is enqueued on which stream (every cross-stream event edge is here;
-// DESIGN.md section 5b is the table to review it against), submit, and the blocking entry points
+// docs/HISTORY.md section 5b is the table to review it against), submit, and the blocking entry points
 // (reference: src/utils.rs:43 to_mag, src/demod_2400.rs:115 demodulate2400, dump1090_rs/src/main.rs:166-167).
 #include "adsb_ctx.h"
 
@@ -33,198 +33,235 @@ int fallback_slot(adsb_ctx *c, const Slot &sl, Slot &tmp)
     return ADSB_OK;
 }
 
+int put_behind(adsb_ctx *c, hipStream_t waiter, hipStream_t ahead)
+{
+    if (!ahead || ahead == waiter) return ADSB_OK;
+    HIP_TRY(c, hipEventRecord(c->lazy_ev, ahead));
+    HIP_TRY(c, hipStreamWaitEvent(waiter, c->lazy_ev, 0));
+    return ADSB_OK;
+}
+
 // `waiter` waits until `other`'s pass is through matching (its records kernel has finished): the event
 // behind a three-launch pass, or -- a one-launch pass records none -- an event put on its stream now.
 int wait_for_tail_of(adsb_ctx *c, hipStream_t waiter, Slot &other)
 {
-    if (other.fused) {
-        HIP_TRY(c, hipEventRecord(c->lazy_ev, other.tail_q));
-        HIP_TRY(c, hipStreamWaitEvent(waiter, c->lazy_ev, 0));
-    } else {
-        HIP_TRY(c, hipStreamWaitEvent(waiter, other.recorded, 0));
-    }
+    if (other.fused) return put_behind(c, waiter, other.tail_q);
+    HIP_TRY(c, hipStreamWaitEvent(waiter, other.recorded, 0));
     return ADSB_OK;
 }
 
 int order_behind_fused(adsb_ctx *c, Slot &sl, hipStream_t waiter)
 {
-    if (sl.fused_q && sl.fused_q != waiter) {
-        HIP_TRY(c, hipEventRecord(c->lazy_ev, sl.fused_q));
-        HIP_TRY(c, hipStreamWaitEvent(waiter, c->lazy_ev, 0));
-    }
+    if (int rc = put_behind(c, waiter, sl.fused_q)) return rc;
     sl.fused_q = nullptr;
     return ADSB_OK;
 }
 
-// Enqueue one device pass over n_chunks chunks starting at d_src into `sl`:
-// reset -> scan -> dense -> match -> records -> D2H of the summary and the first records.
+// The tuning knobs of a pass (tuning builds only: adsb_device.h, tuning_env), each read once, here.
+static bool knob_no_fuse() { static const bool v = tuning_env("ADSB_NO_FUSE") != nullptr; return v; }
+static int knob_fused_streams() { static const int v = tuning_env("ADSB_FUSED_STREAMS") ? std::atoi(tuning_env("ADSB_FUSED_STREAMS")) : kScanStreams; return v; }
+static bool knob_one_scan_stream() { static const bool v = tuning_env("ADSB_ONE_SCAN_STREAM") != nullptr; return v; }
+static bool knob_no_hit_fields() { static const bool v = tuning_env("ADSB_NO_HIT_FIELDS") != nullptr; return v; }
+static bool knob_ext_events() { static const bool v = !tuning_env("ADSB_NO_EXT_EVENTS"); return v; }
+static bool knob_no_trickle() { static const bool v = tuning_env("ADSB_NO_TRICKLE") != nullptr; return v; }
+static bool knob_skip_match() { static const bool v = tuning_env("ADSB_SKIP_MATCH") != nullptr; return v; }   // measurement aid: wrong results
+
 // Whether a plain pass of n_chunks buffers submitted now goes out as one launch.
 bool one_launch_pass(const adsb_ctx *c, uint32_t n_chunks)
 {
-    static const bool never_fuse = tuning_env("ADSB_NO_FUSE") != nullptr;
-    return !never_fuse && c->profiling <= 1 && n_chunks <= (uint32_t)kInlineTailChunks;
+    return !knob_no_fuse() && c->profiling <= 1 && n_chunks <= (uint32_t)kInlineTailChunks;
 }
 
-// The scan stream the next plain IQ pass of n_chunks buffers will run on (enqueue_pass's own rule).
+// The stream rule: consecutive pipelined passes rotate over the scan streams (three-launch passes over the first
+// two, one-launch passes over up to four), unless something orders consecutive passes (the carry hand-off) or the
+// pass is a one-off (a redo, the reference-shaped kernel, caller-supplied magnitudes: not `plain_iq`).
+// (a slot's passes of one kind always land on the same stream: the slot count is a multiple of both periods)
+static int scan_stream_index(const adsb_ctx *c, bool plain_iq, bool carry, bool one_launch, bool redo)
+{
+    if (!plain_iq || carry || redo || knob_one_scan_stream()) return 0;
+    const int period = one_launch ? std::max(1, std::min(knob_fused_streams(), c->n_scan_streams)) : 2;
+    return (int)(c->submitted % (uint64_t)period);
+}
+
+// The scan stream the next plain IQ pass of n_chunks buffers will run on.
 hipStream_t next_scan_stream(const adsb_ctx *c, uint32_t n_chunks)
 {
-    static const int fused_streams = tuning_env("ADSB_FUSED_STREAMS") ? std::atoi(tuning_env("ADSB_FUSED_STREAMS")) : kScanStreams;
-    static const bool one_scan_stream = tuning_env("ADSB_ONE_SCAN_STREAM") != nullptr;
-    if (c->carry_over || one_scan_stream) return c->scan_stream[0];
-    const int period = one_launch_pass(c, n_chunks) ? std::max(1, std::min(fused_streams, c->n_scan_streams)) : 2;
-    return c->scan_stream[c->submitted % (uint64_t)period];
+    return c->scan_stream[scan_stream_index(c, true, c->carry_over, one_launch_pass(c, n_chunks), false)];
 }
 
-int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64_t n_samples,
-                 uint32_t n_chunks, bool inline_tail, bool lead_from_src,
-                 bool advance_carry, bool force_simple, hipEvent_t input_done, bool no_fuse)
+void pass_params(adsb_ctx *c, const Slot &sl, ScanParams &p, uint32_t **retired, uint32_t *clear_next)
 {
-    const bool from_mag = fmt == SrcFormat::kMag;
-    // Passes of many buffers of a dense stream hand their hits over in (buffer, j, try_phase) order and
-    // scored; a small pass is all launch overhead and a sparse one leaves a few hundred records that
-    // the host sorts and scores in no time; the worst-case lists of the fallback are the host's too.
-    const bool order_on_device = !force_simple && n_chunks > kInlineTailChunks && sl.hits_cap == c->hits_cap && c->dense_mode;
+    *retired = nullptr;
+    *clear_next = 0;
+    p.bitmap_lg = c->bitmap_lg;
+    if (c->flush_pending) {  // icao_flush: retire the bitmap in use, continue on the next one
+        // Full bitmaps (2 MiB): the next one IS clean, and the records kernel of this pass (of a shard's second phase)
+        // cleans the retired one behind the passes still matching against it (edge 1).  Folded ones (64 KB, contexts
+        // for passes of a few buffers): the retired one is left as it is and the NEXT one is cleared before this pass
+        // first touches it -- in its own launch (k_scan_fast<FUSED>: bitmap_fresh) or with a reset launch in front of
+        // its scan.  Whoever used that bitmap has been collected (one bitmap more than passes in flight), so the pass
+        // waits for nobody: an icao_flush before every pass, the reference's own benchmark shape
+        // (benches/demod_benchmark.rs:9), used to cost a pipelined one-buffer pass 99 us instead of 5.7
+        // (profiles/r4_v18_hosttime_ring.txt).
+        if (c->bitmap_lg == kFullBitmapLg) *retired = c->d_bitmap[c->cur_bitmap];
+        else *clear_next = 1;
+        c->cur_bitmap = (c->cur_bitmap + 1) % c->n_bitmaps;
+    }
+    p.bitmap = c->d_bitmap[c->cur_bitmap];
+    p.hits = sl.d_hits;
+    p.hits_cap = sl.hits_cap;
+    p.ap = sl.d_ap;
+    p.ap_cap = c->ap_cap;
+    p.seg_cap = c->seg_cap;
+    p.tables = c->d_tables;
+    p.fix = (uint32_t)c->crc.fix;
+    p.ctr = sl.d_ctr;
+    p.summary = sl.h_sum_dev;
+}
+
+void wire_score(const Slot &sl, ScanParams &p, uint32_t *exact, uint32_t *exact_retired)
+{
+    p.score = sl.score;
+    p.score.exact = exact;
+    p.score.exact_retired = exact_retired;
+    p.score.out_msgs = sl.h_msgs_dev;
+    p.score.out_adds = sl.h_adds_dev;
+    p.score.summary = sl.h_ssum_dev;
+}
+
+uint32_t next_seq(adsb_ctx *c)
+{
+    const uint32_t s = c->next_seq++;
+    if (c->next_seq == 0) c->next_seq = 1;
+    return s;
+}
+
+void stamp_seq(adsb_ctx *c, Slot &sl, ScanParams &p, bool scored)
+{
+    sl.seq = next_seq(c);
+    sl.h_sum->seq = 0;  // the records kernel overwrites it, last, with sl.seq
+    p.seq = sl.seq;
+    if (scored) {
+        p.score.seq = sl.seq;
+        sl.h_ssum->seq = 0;
+    }
+}
+
+// ---- one device pass, step by step (docs/HISTORY.md section 5b: the table of the cross-stream edges they name) ----
+// What plan_pass decides about a pass before anything is filled in or enqueued.
+struct PassPlan {
+    bool from_mag = false, fast = false;    // caller-supplied magnitudes / IQ through the fast scan (not the reference-shaped one)
+    bool ordered = false, scored = false;   // the device hands the hits over in (buffer, j, try_phase) order / and scored
+    bool fused = false, classic = false;    // one launch (k_scan_fast<.., FUSED>) / event records around the scan launch
+    bool inline_tail = false;               // the tail stays on the scan stream
+    int prof = 0, si = 0;                   // the profiling level of the pass; its scan stream, as an index and as it is
+    hipStream_t ss = nullptr;
+};
+
+// Step 1 -- what kind of pass this is.  Places no edge; a device-scored pass behind one the host scored itself
+// drains and rebuilds first (row 7 of the table).
+static int plan_pass(adsb_ctx *c, const Slot &sl, SrcFormat fmt, uint32_t n_chunks, const PassOptions &opt, PassPlan &pl)
+{
+    pl.from_mag = fmt == SrcFormat::kMag;
+    pl.fast = !pl.from_mag && !opt.force_simple;
+    // Passes of many buffers of a dense stream hand their hits over in (buffer, j, try_phase) order and scored; a small
+    // pass is all launch overhead and a sparse one leaves a few hundred records that the host sorts and scores in no
+    // time; the worst-case lists of the fallback are the host's too.
+    pl.ordered = !opt.force_simple && n_chunks > kInlineTailChunks && sl.hits_cap == c->hits_cap && c->dense_mode;
     // (in every error-correction mode: k_score / k_emit score and repair a fix pass's DF17/18 trials themselves)
-    const bool score_on_device = order_on_device && c->score.si;
+    const bool score_on_device = pl.ordered && c->score.si;
     if (score_on_device && !c->exact_valid) {
         // the device's copy of the filter can only be rebuilt from the host's once every pass in
         // flight has been replayed: finish them now (their results wait for adsb_collect)
         if (int rc = park_pending(c)) return rc;
         if (int rc = resync_exact(c)) return rc;
     }
-    ScanParams p{};
+    pl.scored = score_on_device && c->exact_valid;
+    pl.prof = c->profiling;   // 1: the scan launch stamps its own begin / end; 2: classic event records between all kernels
+    // A pass of a few buffers is all launch overhead and event traffic: it goes out as ONE launch whose last workgroup
+    // matches, builds the records and publishes the summary, with no event behind it.  (Level 2 wants the kernels apart.)
+    pl.fused = !opt.force_simple && !opt.no_fuse && one_launch_pass(c, n_chunks);
+    pl.classic = !pl.fused && (pl.prof > 1 || (pl.prof == 1 && (!pl.fast || !knob_ext_events())));
+    pl.si = scan_stream_index(c, pl.fast, c->carry_over && !pl.from_mag && sl.d_carry, pl.fused, opt.redo);
+    pl.ss = c->scan_stream[pl.si];
+    // A small pass is all launch overhead: its tail stays on its scan stream too (the scan streams still let
+    // consecutive passes overlap), which saves the cross-stream hand-off.
+    pl.inline_tail = opt.inline_tail || n_chunks <= kInlineTailChunks;
+    return ADSB_OK;
+}
+
+// Step 2 -- the pass's ScanParams and the slot's bookkeeping; consumes a pending icao_flush.  Places no edge.
+static void fill_pass(adsb_ctx *c, Slot &sl, ScanParams &p, const void *d_src, SrcFormat fmt, uint64_t n_samples,
+                      uint32_t n_chunks, const PassOptions &opt, const PassPlan &pl)
+{
     p.src = d_src;
     p.n_samples = n_samples;
     p.n_chunks = n_chunks;
-    p.clean_bitmap = nullptr;
-    p.bitmap_lg = c->bitmap_lg;
-    p.bitmap_fresh = 0;
-    if (c->flush_pending) {  // icao_flush: retire the bitmap in use, continue on the next one
-        // Full bitmaps (2 MiB): the next one IS clean, and this pass's records kernel cleans the retired one behind the
-        // passes still matching against it (edge 1).  Folded ones (64 KB, contexts for passes of a few buffers): the
-        // retired one is left as it is and this pass clears the NEXT one itself before it first touches it -- in its
-        // own launch (k_scan_fast<FUSED>: bitmap_fresh) or with a reset launch in front of its scan.  Whoever used
-        // that bitmap has been collected (one bitmap more than passes in flight), so the pass waits for nobody:
-        // an icao_flush before every pass, the reference's own benchmark shape (benches/demod_benchmark.rs:9), used
-        // to cost a pipelined one-buffer pass 99 us instead of 5.7 (profiles/r4_v18_hosttime_ring.txt).
-        if (c->bitmap_lg == kFullBitmapLg) p.clean_bitmap = c->d_bitmap[c->cur_bitmap];
-        else p.bitmap_fresh = 1;
-        c->cur_bitmap = (c->cur_bitmap + 1) % c->n_bitmaps;
-    }
-    p.bitmap = c->d_bitmap[c->cur_bitmap];
-    p.hits = sl.d_hits;
-    p.hits_cap = sl.hits_cap;
-    // (the slot's own hit list only: the fallback's worst-case list is filled by the reference-shaped kernel)
-    static const bool no_fields = tuning_env("ADSB_NO_HIT_FIELDS") != nullptr;
-    p.hit_fields = nullptr;   // (set below, once it is known whether the pass is a dense stream's or one launch)
-    p.ap = sl.d_ap;
-    p.ap_cap = c->ap_cap;
-    p.seg_cap = c->seg_cap;
+    pass_params(c, sl, p, &p.clean_bitmap, &p.bitmap_fresh);
     p.dap = c->fb.d_dap;  // only the reference-shaped kernel writes it (force_simple: fallback_slot() came first)
     p.dap_cap = c->fb.d_dap ? kWorstPerChunk : 0;
-    p.tables = c->d_tables;
-    p.ctr = sl.d_ctr;
-    p.summary = sl.h_sum_dev;
     p.stagger_ticks = c->stagger_ticks;
     p.debug_stop = c->debug_stop;
     p.timeline = c->d_timeline;
-    p.carry = c->carry_over && !from_mag ? sl.d_carry : nullptr;
+    p.carry = c->carry_over && !pl.from_mag ? sl.d_carry : nullptr;
     p.u8_table = fmt == SrcFormat::kCu8 ? c->d_u8_table : nullptr;
-    p.fix = (uint32_t)c->crc.fix;
-    p.lead_from_src = lead_from_src ? 1u : 0u;
-    p.order_cnt = order_on_device ? sl.d_order_cnt : nullptr;
-    p.order_base = order_on_device ? sl.d_order_base : nullptr;
-    p.order_tmp = order_on_device ? sl.d_order_tmp : nullptr;
-    sl.device_scored = false;
-    if (score_on_device) {
-        if (c->exact_valid) {
-            p.score = sl.score;
-            p.score.exact_retired = nullptr;
-            if (c->flush_pending) {  // icao_flush: this pass starts from the clean bitmap
-                p.score.exact_retired = c->exact_bm[c->cur_exact];
-                c->cur_exact ^= 1;
-            }
-            p.score.exact = c->exact_bm[c->cur_exact];
-            p.score.out_msgs = sl.h_msgs_dev;
-            p.score.out_adds = sl.h_adds_dev;
-            p.score.summary = sl.h_ssum_dev;
-            sl.device_scored = true;
-            sl.score_epoch = c->score_epoch;
+    p.lead_from_src = opt.lead_from_src ? 1u : 0u;
+    p.order_cnt = pl.ordered ? sl.d_order_cnt : nullptr;
+    p.order_base = pl.ordered ? sl.d_order_base : nullptr;
+    p.order_tmp = pl.ordered ? sl.d_order_tmp : nullptr;
+    // the scan hands the bit fields of its self-validating hits to the record builder: where the record builder's
+    // instructions matter (dense streams: it shares the vector pipes with the next scan) and in one-launch passes; a
+    // sparse stream's scan stays the lean instantiation (and the reference-shaped kernel, the fallback's, fills none)
+    p.hit_fields = pl.fused || (pl.ordered && !knob_no_hit_fields()) ? sl.d_hit_fields : nullptr;
+    sl.device_scored = pl.scored;
+    if (pl.scored) {
+        uint32_t *exact_retired = nullptr;
+        if (c->flush_pending) {  // icao_flush: this pass starts from the clean exact bitmap
+            exact_retired = c->exact_bm[c->cur_exact];
+            c->cur_exact ^= 1;
         }
+        wire_score(sl, p, c->exact_bm[c->cur_exact], exact_retired);
+        sl.score_epoch = c->score_epoch;
     }
-
+    p.fused_rec = pl.fused ? sl.h_rec_dev : nullptr;
+    p.order_polls = c->order_polls;
+    p.src_ready = pl.fused && !pl.from_mag ? c->next_src_ready : nullptr;
+    c->next_src_ready = nullptr;
+    p.src_host = pl.fused && !pl.from_mag && c->next_src_host && !knob_no_trickle() ? 1u : 0u;
+    c->next_src_host = false;
     sl.src = d_src;
     sl.fmt = fmt;
     sl.n_samples = n_samples;
     sl.n_chunks = n_chunks;
     sl.flush_before = c->flush_pending;
-    sl.profiled = c->profiling;
-    const int prof = sl.profiled;
-    sl.seq = c->next_seq++;
-    if (c->next_seq == 0) c->next_seq = 1;
-    // A pass collect_oldest runs again (overflow fallback buffer by buffer, rematch: `advance_carry` is false for
-    // exactly those) keeps its number -- a fresh one per buffer would walk through the event ring under the
-    // passes still in flight and move last_new_insert_seq ahead of them -- and times itself with its own pair.
-    sl.redo = !advance_carry;
-    if (!sl.redo) {
-        sl.scan_seq = ++c->scan_counter;
-        sl.ev[0] = c->scan_ev[sl.scan_seq % kScanEvRing][0];
-        sl.ev[1] = c->scan_ev[sl.scan_seq % kScanEvRing][1];
-    } else {
-        sl.ev[0] = c->redo_ev[0];
-        sl.ev[1] = c->redo_ev[1];
-    }
-    sl.h_sum->seq = 0;  // the records kernel overwrites it, last, with sl.seq
-    p.seq = sl.seq;
-    if (sl.device_scored) {
-        p.score.seq = sl.seq;
-        sl.h_ssum->seq = 0;
-    }
-    // level 1: the scan launch stamps its own begin/end (no extra packets on the stream);
-    // level 2: classic event records between all kernels
-    static const bool ext_events = !tuning_env("ADSB_NO_EXT_EVENTS");
-    const bool fast = !from_mag && !force_simple;
-    // A pass of a few buffers is all launch overhead and event traffic: it goes out as ONE launch whose
-    // last workgroup matches, builds the records and publishes the summary (k_scan_fast<.., FUSED>), with
-    // no event behind it.  (Level-2 profiling wants the three kernels apart.)
-    const bool fused = !force_simple && !no_fuse && one_launch_pass(c, n_chunks);
-    sl.fused = fused;
-    sl.unsynced_from = 0;
-    p.fused_rec = fused ? sl.h_rec_dev : nullptr;
-    p.order_polls = c->order_polls;
-    p.src_ready = fused && !from_mag ? c->next_src_ready : nullptr;
-    c->next_src_ready = nullptr;
-    static const bool no_trickle = tuning_env("ADSB_NO_TRICKLE") != nullptr;
-    p.src_host = fused && !from_mag && c->next_src_host && !no_trickle ? 1u : 0u;
-    c->next_src_host = false;
-    // the scan hands the bit fields of its self-validating hits to the record builder: where the record
-    // builder's instructions matter (dense streams: it shares the vector pipes with the next scan) and in
-    // one-launch passes; a sparse stream's scan stays the lean instantiation
-    if (fused || (order_on_device && !no_fields)) p.hit_fields = sl.d_hit_fields;
-    // (a one-launch pass times itself on the device's wall clock and reports it with its summary)
-    p.ev_start = ext_events && prof == 1 && fast && !fused ? sl.ev[0] : nullptr;
-    p.ev_stop = ext_events && prof == 1 && fast && !fused ? sl.ev[1] : nullptr;
-
     c->flush_pending = false;
-    const bool classic = !fused && (prof > 1 || (prof == 1 && (!fast || !ext_events)));
-    // odd slots scan on the second stream, unless something orders consecutive passes (the
-    // carry hand-off) or the pass is a one-off (fallback, caller-supplied magnitudes)
-    static const bool one_scan_stream = tuning_env("ADSB_ONE_SCAN_STREAM") != nullptr;
-    static const int fused_streams = tuning_env("ADSB_FUSED_STREAMS") ? std::atoi(tuning_env("ADSB_FUSED_STREAMS")) : kScanStreams;
-    const bool rotate = fast && !p.carry && advance_carry && !one_scan_stream;
-    // (a slot's passes of one kind always land on the same stream: the slot count is a multiple of both periods)
-    const int si = !rotate ? 0 : (int)(c->submitted % (uint64_t)(fused ? std::max(1, std::min(fused_streams, c->n_scan_streams)) : 2));
-    hipStream_t ss = c->scan_stream[si];
-    // the input is complete at `input_done` (the ring's copy), already (input_ready_now: pinned memory the
-    // host has filled), or where `stream` stands now
+    sl.profiled = pl.prof;
+    sl.fused = pl.fused;
+    sl.unsynced_from = 0;
+    stamp_seq(c, sl, p, sl.device_scored);
+    // A pass collect_oldest runs again keeps its number -- a fresh one per buffer would walk through the event ring
+    // under the passes still in flight and move last_new_insert_seq ahead of them -- and times itself with its own pair.
+    sl.redo = opt.redo;
+    if (!sl.redo) sl.scan_seq = ++c->scan_counter;
+    const hipEvent_t *ev = sl.redo ? c->redo_ev : c->scan_ev[sl.scan_seq % kScanEvRing];
+    sl.ev[0] = ev[0], sl.ev[1] = ev[1];
+    // (a one-launch pass times itself on the device's wall clock and reports it with its summary)
+    const bool stamps = knob_ext_events() && pl.prof == 1 && pl.fast && !pl.fused;
+    p.ev_start = stamps ? sl.ev[0] : nullptr;
+    p.ev_stop = stamps ? sl.ev[1] : nullptr;
+}
+
+// Step 3 -- edge "in": the scan stream behind the pass's input, which is complete at `input_done` (the caller's
+// event), already (input_ready_now: pinned memory the host has filled), or where `stream` stands now.
+int order_behind_input(adsb_ctx *c, hipEvent_t input_done, int si, hipStream_t ss)
+{
     if (input_done != input_ready_now()) {
         HT(c, HT_IN_READY);
         hipEvent_t ready = input_done;
-        // No event at all when `stream` is the context's own and the library has put nothing on it that this
-        // pass could depend on (own_stream_dirty: the copies of the host-pointer entry points): the record +
-        // wait pair is two thirds of what a one-launch pass costs the submitting thread.  (hipStreamQuery is
-        // no substitute: on a stream that has seen work it took ~25 us, measured.)  A caller's stream
-        // (adsb_set_stream) is always waited for.
+        // No event at all when `stream` is the context's own and the library has put nothing on it that this pass could
+        // depend on (own_stream_dirty: the copies of the host-pointer entry points): the record + wait pair is two thirds
+        // of what a one-launch pass costs the submitting thread.  (hipStreamQuery is no substitute: on a stream that has
+        // seen work it took ~25 us, measured.)  A caller's stream (adsb_set_stream) is always waited for.
         const bool nothing_to_wait_for = !ready && c->stream == c->own_stream && !c->own_stream_dirty;
         if (!ready && !nothing_to_wait_for) {
             ready = c->input_ready[si];
@@ -233,37 +270,34 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
         }
         if (ready) HIP_TRY(c, hipStreamWaitEvent(ss, ready, 0));
     }
-    // (a ring slot's copy was queued on the stream adsb_ring_submit expected this pass to take -- the same rule as
-    // above, in next_scan_stream(); should the two ever disagree, the pass waits for that stream)
-    if (c->input_on_stream && c->input_on_stream != ss) {
-        HIP_TRY(c, hipEventRecord(c->lazy_ev, c->input_on_stream));
-        HIP_TRY(c, hipStreamWaitEvent(ss, c->lazy_ev, 0));
-    }
+    // (a ring slot's copy was queued on next_scan_stream(), which is the rule plan_pass applied: the same stream for
+    // the pass adsb_ring_submit announced.  A pass that is not that one -- a redo, a shard -- waits for the copy.)
+    return put_behind(c, ss, c->input_on_stream);
+}
+
+// Step 4 -- the edges in front of the scan launch: 0, 1'' and, for a one-launch pass, 1, 2 and 3'.
+// (1) A bitmap an icao_flush retired is cleared by this pass (its records kernel, or every workgroup of a one-launch
+//     pass): not before the passes still in flight, whichever stream their tail is on, are through matching against
+//     it.  A tail on this same in-order stream is behind us already.
+// (2) The match must see every address bit the scans of this and of all earlier passes set.  Behind its own scan it
+//     is in stream order or waits for `scanned` (2').  Behind the previous pass's scan it is in order when both
+//     matches run on the tail stream; a match on its own scan stream waits for the previous scan explicitly when that
+//     ran on another one.  (Scans before the previous one are behind this pass's or the previous pass's.)
+// (3) One-launch passes record no event and do not wait for each other across the scan streams: a three-launch pass
+//     that needs one behind it records an event on that stream now (enqueue_tail); a one-launch pass notes from which
+//     pass on its match is unsynchronised (3': Slot::unsynced_from) and the host redoes it if one of those taught
+//     the filter a new address.
+static int edges_before_scan(adsb_ctx *c, Slot &sl, const ScanParams &p, const PassPlan &pl)
+{
+    hipStream_t ss = pl.ss;
     // (0) the slot's lists and counters: a one-launch pass that used them last on another stream may still
     //     be zeroing them (the host goes by its summary, which it writes just before)
-    if (sl.fused_q && sl.fused_q != ss) {
-        HIP_TRY(c, hipEventRecord(c->lazy_ev, sl.fused_q));
-        HIP_TRY(c, hipStreamWaitEvent(ss, c->lazy_ev, 0));
-    }
-    sl.fused_q = fused ? ss : nullptr;
-    if (n_chunks <= kInlineTailChunks) inline_tail = true;
-    // ---- cross-stream edges (DESIGN.md section 5b is the table of them) -------------------------------
-    // (1) A bitmap an icao_flush retired is cleared by this pass (its records kernel, or every workgroup
-    //     of a one-launch pass): not before the passes still in flight, whichever stream their tail is on,
-    //     are through matching against it.  A tail on this same in-order stream is behind us already.
-    // (2) The match must see every address bit the scans of this and of all earlier passes set.  Behind
-    //     its own scan it is in stream order or waits for `scanned`.  Behind the previous pass's scan it is
-    //     in order when both matches run on the tail stream (that pass's match waited for its scan); a pass
-    //     whose match runs on its own scan stream waits for the previous scan explicitly when that ran on
-    //     the other one.  (Scans before the previous one are behind this pass's scan or the previous
-    //     pass's, on the same two streams.)
-    // (3) One-launch passes record no event and do not wait for each other across the two scan streams:
-    //     a three-launch pass that needs one of them behind it records an event on that stream now; a
-    //     one-launch pass notes from which pass on its match is unsynchronised (Slot::unsynced_from) and
-    //     the host redoes it if one of those turns out to have taught the filter a new address.
+    if (int rc = order_behind_fused(c, sl, ss)) return rc;
+    sl.fused_q = pl.fused ? ss : nullptr;
+    // (1'') folded bitmaps: a pass behind the one that opened the filter's epoch shares the bitmap that one clears
     bool behind_fresh = false;   // this launch has been ordered behind the pass that opened the epoch
     if (c->bitmap_lg != kFullBitmapLg) {
-        const long my_slot = &sl - c->slot;
+        const long my_slot = &sl - c->slot;   // (a fallback pass's temporary slot is none of the context's)
         if (p.bitmap_fresh) {   // this pass opens the filter's next epoch and clears its bitmap
             c->fresh_q = ss;
             c->fresh_seq = c->epoch_first_seq = sl.scan_seq;
@@ -271,73 +305,78 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
         } else if (c->fresh_q && c->fresh_q != ss && c->fresh_slot >= 0 && c->fresh_slot != my_slot) {
             const Slot &f = c->slot[c->fresh_slot];
             if (f.busy && f.scan_seq == c->fresh_seq) {   // still in flight: behind it (rare: the first passes after a flush)
-                HIP_TRY(c, hipEventRecord(c->lazy_ev, c->fresh_q));
-                HIP_TRY(c, hipStreamWaitEvent(ss, c->lazy_ev, 0));
+                if (int rc = put_behind(c, ss, c->fresh_q)) return rc;
                 behind_fresh = true;
             }
         }
     }
-    if (fused) {
+    if (pl.fused) {
         HT(c, HT_EV_SCANNED);
+        // (1), one launch
         if (p.clean_bitmap)
             for (Slot &other : c->slot)
                 if (&other != &sl && other.busy && other.tail_q != ss)
                     if (int rc = wait_for_tail_of(c, ss, other)) return rc;
+        // (2), one launch
         bool other_stream_synced = false;
         if (c->prev_scan_stream && c->prev_scan_stream != ss && !c->prev_fused && c->prev_scanned) {
             HIP_TRY(c, hipStreamWaitEvent(ss, c->prev_scanned, 0));
             other_stream_synced = true;   // (in stream order behind it: every earlier pass on that stream)
         }
-        // (every pass in flight whose scan is not in stream order before this launch: not on this stream, and not
-        // on the stream of the three-launch pass just waited for -- that wait covers what ran on ITS stream only)
-        // (... and that belongs to the filter's current epoch: what a pass from before the latest icao_flush taught
-        // the filter is gone when this pass is replayed -- with a flush before every pass, the reference's benchmark
-        // shape, every pass used to be redone because its predecessor had "taught a new address")
+        // (3') every pass in flight whose scan is not in stream order before this launch: not on this stream, and not on
+        // the stream of the three-launch pass just waited for -- that wait covers what ran on ITS stream only -- and that
+        // belongs to the filter's current epoch: what a pass from before the latest icao_flush taught the filter is gone
+        // when this pass is replayed (with a flush before every pass every pass used to be redone for its predecessor's sake)
         for (Slot &other : c->slot)
             if (&other != &sl && other.busy && other.scan_q != ss && other.scan_seq >= c->epoch_first_seq &&
                 !(other_stream_synced && other.scan_q == c->prev_scan_stream) && !(behind_fresh && other.scan_seq == c->fresh_seq))
                 sl.unsynced_from = sl.unsynced_from ? std::min(sl.unsynced_from, other.scan_seq) : other.scan_seq;
     }
     sl.scan_q = ss;
-    if (p.bitmap_fresh && !fused) {
+    return ADSB_OK;
+}
+
+// Step 5 -- the scan launch and what goes with it on the scan stream: the clear of a fresh folded bitmap, the
+// classic event records, the carry hand-off (row 6: stream order on scan[0], no edge).
+static int launch_scan_step(adsb_ctx *c, Slot &sl, ScanParams &p, SrcFormat fmt, const PassOptions &opt, const PassPlan &pl)
+{
+    hipStream_t ss = pl.ss;
+    if (p.bitmap_fresh && !pl.fused) {
         // (three launches in a context of folded bitmaps -- level-2 profiling, a caller's MagnitudeBuffer that
         // overflowed -- : the clear as a launch of its own in front of the scan; the counters it also zeroes are zero)
         if (int e = launch_reset(sl.d_ctr, p.bitmap, p.bitmap_lg, ss)) return fail(c, (hipError_t)e, "launch_reset");
         p.bitmap_fresh = 0;
     }
-    if (classic) HIP_TRY(c, hipEventRecord(sl.ev[0], ss));
-    if (p.carry && advance_carry)  // this pass's lead-in: where the previous submission ended
+    if (pl.classic) HIP_TRY(c, hipEventRecord(sl.ev[0], ss));
+    const bool hand_carry_on = p.carry && !opt.redo;
+    if (hand_carry_on)  // this pass's lead-in: where the previous submission ended
         HIP_TRY(c, hipMemcpyAsync(sl.d_carry, c->d_carry_next, kCarrySamples * sizeof(uint32_t),
                                   hipMemcpyDeviceToDevice, ss));
     {
         HT(c, HT_SCAN_LAUNCH);
-        if (int e = fused ? launch_pass_fused(p, fmt, ss)
-                          : (force_simple ? launch_scan_simple(p, fmt, ss) : launch_scan(p, fmt, ss)))
+        if (int e = pl.fused ? launch_pass_fused(p, fmt, ss)
+                             : (opt.force_simple ? launch_scan_simple(p, fmt, ss) : launch_scan(p, fmt, ss)))
             return fail(c, (hipError_t)e, "launch_scan");
     }
-    if (classic) HIP_TRY(c, hipEventRecord(sl.ev[1], ss));
-    if (p.carry && advance_carry) {
+    if (pl.classic) HIP_TRY(c, hipEventRecord(sl.ev[1], ss));
+    if (hand_carry_on) {
         // the next submission starts from the end of this one's input (taken now: the caller
         // may reuse the buffer as soon as this pass is collected)
-        if (int e = launch_update_carry(sl.d_carry, d_src, n_samples, c->d_carry_next, ss, p.u8_table))
+        if (int e = launch_update_carry(sl.d_carry, p.src, p.n_samples, c->d_carry_next, ss, p.u8_table))
             return fail(c, (hipError_t)e, "launch_update_carry");
     }
-    if (fused) {
-        sl.tail_q = ss;
-        c->prev_scanned = nullptr;
-        c->prev_scan_stream = ss;
-        c->prev_inline = true;
-        c->prev_fused = true;
-        return ADSB_OK;
-    }
-    // the tail runs on its own stream behind the scan: the next pass's scan does not wait
-    // for it (it works on the other slot's lists and counters)
-    // (a blocking call has nothing to overlap with: its tail stays on the scan stream and
-    // saves the cross-stream hand-off)
-    // A small pass is all launch overhead: its tail stays on its scan stream too (the two scan
-    // streams still let consecutive passes overlap), which saves the cross-stream hand-off.
-    hipStream_t ts = inline_tail ? ss : c->tail_stream;
-    if (p.clean_bitmap && fast) {
+    return ADSB_OK;
+}
+
+// Step 6 -- the tail of a three-launch pass: match, order, records, with the edges 1, 2, 2' and 3 in front of them
+// and `recorded` behind them.
+static int enqueue_tail(adsb_ctx *c, Slot &sl, const ScanParams &p, SrcFormat fmt, const PassPlan &pl)
+{
+    hipStream_t ss = pl.ss;
+    // the tail runs on its own stream behind the scan: the next pass's scan does not wait for it (it works on the other
+    // slot's lists and counters); a blocking call's and a small pass's stay on the scan stream (plan_pass)
+    hipStream_t ts = pl.inline_tail ? ss : c->tail_stream;
+    if (p.clean_bitmap && pl.fast) {
         // edge (1): the event behind the other passes' records kernels, not `done`, which device-scored
         // passes record later, on the score stream
         for (Slot &other : c->slot)
@@ -346,40 +385,38 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
     }
     {
         HT(c, HT_EV_SCANNED);
+        // edge (2'): behind its own scan
         HIP_TRY(c, hipEventRecord(sl.scanned, ss));
-        if (!inline_tail) HIP_TRY(c, hipStreamWaitEvent(ts, sl.scanned, 0));
-        // edge (2)
-        if (c->prev_scanned && !c->prev_fused && c->prev_scan_stream != ss && (inline_tail || c->prev_inline))
+        if (!pl.inline_tail) HIP_TRY(c, hipStreamWaitEvent(ts, sl.scanned, 0));
+        // edge (2): behind the previous pass's scan
+        if (c->prev_scanned && !c->prev_fused && c->prev_scan_stream != ss && (pl.inline_tail || c->prev_inline))
             HIP_TRY(c, hipStreamWaitEvent(ts, c->prev_scanned, 0));
         // edge (3): one-launch passes in flight on a stream this match is not behind
         for (hipStream_t q : c->scan_stream) {
-            if (!q || q == ts || (q == ss && !inline_tail)) continue;   // (behind its own scan: behind everything on that stream)
+            if (!q || q == ts || (q == ss && !pl.inline_tail)) continue;   // (behind its own scan: behind everything on that stream)
             bool any = false;
             for (Slot &other : c->slot) any = any || (&other != &sl && other.busy && other.fused && other.tail_q == q);
             if (!any) continue;
-            HIP_TRY(c, hipEventRecord(c->lazy_ev, q));
-            HIP_TRY(c, hipStreamWaitEvent(ts, c->lazy_ev, 0));
+            if (int rc = put_behind(c, ts, q)) return rc;
         }
     }
     c->prev_scanned = sl.scanned;
     c->prev_scan_stream = ss;
-    c->prev_inline = inline_tail;
+    c->prev_inline = pl.inline_tail;
     c->prev_fused = false;
-    if (prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[2], ts));
-    static const bool skip_match = tuning_env("ADSB_SKIP_MATCH") != nullptr;  // measurement aid (tuning build only): wrong results
+    if (pl.prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[2], ts));
     {
         HT(c, HT_MATCH_LAUNCH);
-        if (!skip_match)
+        if (!knob_skip_match())
             if (int e = launch_match(p, ts)) return fail(c, (hipError_t)e, "launch_match");
         if (int e = launch_order_hits(p, ts)) return fail(c, (hipError_t)e, "launch_order_hits");
     }
-    if (prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[3], ts));
+    if (pl.prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[3], ts));
     // the records kernel writes the records and the summary into the slot's mapped host
     // memory with write-through stores; `done` only has to say the kernel has drained
     {
         HT(c, HT_RECORDS_LAUNCH);
-        if (int e = launch_records(p, fmt, sl.h_rec_dev, ts))
-            return fail(c, (hipError_t)e, "launch_records");
+        if (int e = launch_records(p, fmt, sl.h_rec_dev, ts)) return fail(c, (hipError_t)e, "launch_records");
     }
     sl.tail_q = ts;
     // (always: a later pass whose own tail runs on another stream -- a small one behind an icao_flush --
@@ -388,41 +425,83 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
         HT(c, HT_EV_DONE);
         HIP_TRY(c, hipEventRecord(sl.recorded, ts));
     }
+    return ADSB_OK;
+}
+
+// Step 7 -- scoring on the device (edge 4) and the completion event (edge 5).
+static int enqueue_score(adsb_ctx *c, Slot &sl, const ScanParams &p, const PassPlan &pl)
+{
+    hipStream_t ts = sl.tail_q;
     if (sl.device_scored) {
-        // Scoring runs on its own in-order stream behind this pass's records kernel, so that the next
-        // pass's match / order / records (tail stream) overlap it: every kernel beside the persistent
-        // scan is latency, and one chain of eight would be longer than the scan it hides behind.
-        // The score stream's order is the filter's order: k_score(i+1) reads the exact bitmap after
-        // k_emit(i) has committed pass i's additions to it.
+        // Scoring runs on its own in-order stream behind this pass's records kernel, so that the next pass's match /
+        // order / records (tail stream) overlap it: every kernel beside the persistent scan is latency, and one chain of
+        // eight would be longer than the scan it hides behind.  The score stream's order is the filter's order:
+        // k_score(i+1) reads the exact bitmap after k_emit(i) has committed pass i's additions to it.
         hipStream_t qs = c->score_stream;
-        HIP_TRY(c, hipStreamWaitEvent(qs, sl.recorded, 0));
+        HIP_TRY(c, hipStreamWaitEvent(qs, sl.recorded, 0));   // edge (4)
         if (int e = launch_score(p, qs)) return fail(c, (hipError_t)e, "launch_score");
         ts = qs;
     }
-    if (prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[4], ts));
+    if (pl.prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[4], ts));
     {
         HT(c, HT_EV_DONE);
-        HIP_TRY(c, hipEventRecord(sl.done, ts));
+        HIP_TRY(c, hipEventRecord(sl.done, ts));   // edge (5)
     }
+    return ADSB_OK;
+}
+
+// Enqueue one device pass over n_chunks buffers starting at d_src into `sl` and return: either one launch on a scan
+// stream (scan, match and records in it, no event behind it: the host sees the summary land in mapped memory), or
+// [reset ->] scan [-> carry update] there, match -> order -> records on the tail stream (or the scan stream) and, for a
+// dense stream, score / emit on the score stream, `done` behind the last.  All results are written straight into the
+// slot's mapped host memory: there is no copy back.
+int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64_t n_samples, uint32_t n_chunks,
+                 const PassOptions &opt)
+{
+    PassPlan pl;
+    if (int rc = plan_pass(c, sl, fmt, n_chunks, opt, pl)) return rc;
+    ScanParams p{};
+    fill_pass(c, sl, p, d_src, fmt, n_samples, n_chunks, opt, pl);
+    if (int rc = order_behind_input(c, opt.input_done, pl.si, pl.ss)) return rc;   // edge in
+    if (int rc = edges_before_scan(c, sl, p, pl)) return rc;             // edges 0, 1'', one launch: 1, 2, 3'
+    if (int rc = launch_scan_step(c, sl, p, fmt, opt, pl)) return rc;    // (row 6)
+    if (pl.fused) {   // everything is out; what the next pass has to know about this one
+        sl.tail_q = c->prev_scan_stream = pl.ss;
+        c->prev_scanned = nullptr;
+        c->prev_inline = c->prev_fused = true;
+        return ADSB_OK;
+    }
+    if (int rc = enqueue_tail(c, sl, p, fmt, pl)) return rc;             // edges 1, 2, 2', 3
+    return enqueue_score(c, sl, p, pl);                                  // edges 4, 5
+}
+
+std::vector<uint32_t> filter_addresses(const adsb_ctx *c)
+{
+    std::vector<uint32_t> addrs;
+    for (uint32_t a : c->filter.table())
+        if (a != 0 && a <= 0xFFFFFFu) addrs.push_back(a);  // DF18 entries (addr | 1 << 25) match no 24-bit residual
+    return addrs;
+}
+
+int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc)
+{
+    if (n <= c->addrs_cap) return ADSB_OK;
+    if (c->d_addrs) (void)hipFree(c->d_addrs);
+    c->d_addrs = nullptr;
+    c->addrs_cap = 0;
+    HIP_TRY(c, hipMalloc((void **)&c->d_addrs, alloc * sizeof(uint32_t)));
+    c->addrs_cap = alloc;
     return ADSB_OK;
 }
 
 // The exact bitmap rebuilt from the host's filter table (only while nothing is in flight).
 int resync_exact(adsb_ctx *c)
 {
-    std::vector<uint32_t> addrs;
-    for (uint32_t a : c->filter.table())
-        if (a != 0 && a <= 0xFFFFFFu) addrs.push_back(a);
+    const std::vector<uint32_t> addrs = filter_addresses(c);
     hipStream_t ts = c->score_stream;
     for (uint32_t *bm : c->exact_bm) HIP_TRY(c, hipMemsetAsync(bm, 0, kBitmapAllocWords * sizeof(uint32_t), ts));
     if (!addrs.empty()) {
-        if (addrs.size() > c->addrs_cap) {
-            if (c->d_addrs) (void)hipFree(c->d_addrs);
-            c->d_addrs = nullptr;
-            c->addrs_cap = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_addrs, IcaoFilter::kSize * sizeof(uint32_t)));
-            c->addrs_cap = IcaoFilter::kSize;
-        }
+        if (int rc = ensure_addrs(c, addrs.size(), IcaoFilter::kSize)) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->d_addrs, addrs.data(), addrs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ts));
         if (int e = launch_set_addresses(c->d_addrs, (uint32_t)addrs.size(), c->exact_bm[c->cur_exact], kFullBitmapLg, ts))
             return fail(c, (hipError_t)e, "launch_set_addresses");
@@ -439,17 +518,9 @@ int resync_exact(adsb_ctx *c)
 // passes have not been replayed yet), and extra bits only widen the superset for later passes.
 int reseed_bitmap_from_filter(adsb_ctx *c)
 {
-    std::vector<uint32_t> addrs;
-    for (uint32_t a : c->filter.table())
-        if (a != 0 && a <= 0xFFFFFFu) addrs.push_back(a);  // DF18 entries (addr | 1 << 25) match no 24-bit residual
+    const std::vector<uint32_t> addrs = filter_addresses(c);
     if (addrs.empty()) return ADSB_OK;
-    if (addrs.size() > c->addrs_cap) {
-        if (c->d_addrs) (void)hipFree(c->d_addrs);
-        c->d_addrs = nullptr;
-        c->addrs_cap = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->d_addrs, IcaoFilter::kSize * sizeof(uint32_t)));
-        c->addrs_cap = IcaoFilter::kSize;
-    }
+    if (int rc = ensure_addrs(c, addrs.size(), IcaoFilter::kSize)) return rc;
     HIP_TRY(c, hipMemcpy(c->d_addrs, addrs.data(), addrs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (int e = launch_set_addresses(c->d_addrs, (uint32_t)addrs.size(), c->d_bitmap[c->cur_bitmap], c->bitmap_lg, c->scan_stream[0]))
         return fail(c, (hipError_t)e, "launch_set_addresses");
@@ -466,8 +537,10 @@ int submit(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, bo
 #ifdef ADSB_TUNING
     const auto te0 = std::chrono::steady_clock::now();
 #endif
-    int rc = enqueue_pass(c, sl, d_src, fmt, n_samples, (uint32_t)n_chunks, inline_tail, false, true, false,
-                          input_done);
+    PassOptions opt;
+    opt.inline_tail = inline_tail;
+    opt.input_done = input_done;
+    int rc = enqueue_pass(c, sl, d_src, fmt, n_samples, (uint32_t)n_chunks, opt);
 #ifdef ADSB_TUNING
     c->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - te0).count();
 #endif
@@ -487,6 +560,21 @@ int run_sync(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, 
     return collect_next(c, out);
 }
 
+// A long stream goes in pieces: the messages of the piece at sample `off` (chunk = buffer of the stream) and the
+// stats its pass left in the context join the call's.
+static void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, std::vector<adsb_msg> &out, adsb_stats &total)
+{
+    for (auto &m : part) {
+        m.chunk += off / kChunkSamples;
+        out.push_back(m);
+    }
+    const adsb_stats &st = c->stats;
+    total.n_chunks += st.n_chunks, total.n_candidates += st.n_candidates, total.n_ap_entries += st.n_ap_entries;
+    total.n_records += st.n_records, total.ms_scan += st.ms_scan, total.ms_scan_exclusive += st.ms_scan_exclusive;
+    total.ms_match += st.ms_match, total.ms_records += st.ms_records, total.ms_total_device += st.ms_total_device;
+    total.retries += st.retries;
+}
+
 // IQ stream of any length resident on the device.
 int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<adsb_msg> &out, SrcFormat fmt)
 {
@@ -504,21 +592,7 @@ int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<
         std::vector<adsb_msg> part;
         int rc = run_sync(c, (const char *)d_iq + off * src_bytes_per_sample(fmt), fmt, n, part);
         if (rc) return rc;
-        const uint64_t chunk0 = off / kChunkSamples;
-        for (auto &m : part) {
-            m.chunk += chunk0;
-            out.push_back(m);
-        }
-        total.n_chunks += c->stats.n_chunks;
-        total.n_candidates += c->stats.n_candidates;
-        total.n_ap_entries += c->stats.n_ap_entries;
-        total.n_records += c->stats.n_records;
-        total.ms_scan += c->stats.ms_scan;
-        total.ms_scan_exclusive += c->stats.ms_scan_exclusive;
-        total.ms_match += c->stats.ms_match;
-        total.ms_records += c->stats.ms_records;
-        total.ms_total_device += c->stats.ms_total_device;
-        total.retries += c->stats.retries;
+        append_piece(c, part, off, out, total);
     }
     total.n_samples = n_samples;
     c->stats = total;
@@ -673,16 +747,7 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
             std::vector<adsb_msg> part;
             rc = run_sync(c, (const char *)c->h_stage_dev + off * bps, fmt, n, part, input_ready_now());
             if (rc) return rc;
-            const uint64_t chunk0 = off / kChunkSamples;
-            for (auto &m : part) {
-                m.chunk += chunk0;
-                msgs.push_back(m);
-            }
-            const adsb_stats &st = c->stats;
-            total.n_chunks += st.n_chunks, total.n_candidates += st.n_candidates, total.n_ap_entries += st.n_ap_entries;
-            total.n_records += st.n_records, total.ms_scan += st.ms_scan, total.ms_scan_exclusive += st.ms_scan_exclusive;
-            total.ms_match += st.ms_match, total.ms_records += st.ms_records, total.ms_total_device += st.ms_total_device;
-            total.retries += st.retries;
+            append_piece(c, part, off, msgs, total);
         }
         total.n_samples = n_samples;
         c->stats = total;
@@ -695,21 +760,7 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
         std::vector<adsb_msg> part;
         rc = demod_device(c, c->d_stage, n, part, fmt);
         if (rc) return rc;
-        const uint64_t chunk0 = off / kChunkSamples;
-        for (auto &m : part) {
-            m.chunk += chunk0;
-            msgs.push_back(m);
-        }
-        total.n_chunks += c->stats.n_chunks;
-        total.n_candidates += c->stats.n_candidates;
-        total.n_ap_entries += c->stats.n_ap_entries;
-        total.n_records += c->stats.n_records;
-        total.ms_scan += c->stats.ms_scan;
-        total.ms_scan_exclusive += c->stats.ms_scan_exclusive;
-        total.ms_match += c->stats.ms_match;
-        total.ms_records += c->stats.ms_records;
-        total.ms_total_device += c->stats.ms_total_device;
-        total.retries += c->stats.retries;
+        append_piece(c, part, off, msgs, total);
     }
     total.n_samples = n_samples;
     c->stats = total;

@@ -132,7 +132,7 @@ try {
         HT(c, HT_RING_MEMCPY);
         HIP_TRY(c, hipMemcpyAsync(r.d_iq, r.h_iq, n_samples * src_bytes_per_sample(c->ring_fmt), hipMemcpyHostToDevice, q));
     }
-    // (enqueue_pass checks that the pass does land on q, and orders it behind q with an event if it ever does not)
+    // (the stream enqueue_pass gives this pass, by the same rule: the copy sits in front of it in stream order)
     c->input_on_stream = q;
     const int rc = submit(c, r.d_iq, c->ring_fmt, n_samples, false, input_ready_now());
     c->input_on_stream = nullptr;

@@ -30,13 +30,6 @@ using namespace adsb::host;
 
 namespace {
 
-uint32_t next_seq(adsb_ctx *c)
-{
-    const uint32_t s = c->next_seq++;
-    if (c->next_seq == 0) c->next_seq = 1;
-    return s;
-}
-
 // One 131072-sample buffer of a parked shard through the reference-shaped kernel, whose lists
 // hold the worst case of a buffer: scan (+ match) + records, synchronously.  The records land
 // in the fallback's host buffer (c->fb.h_rec) with chunk = 0; *n_out = how many.
@@ -58,9 +51,7 @@ int shard_chunk_pass(adsb_ctx *c, Slot &sl, ScanParams p, uint64_t ch, bool with
     p.order_tmp = nullptr;
     p.hit_fields = nullptr;
     p.score = ScoreDev{};
-    sl.seq = next_seq(c);
-    sl.h_sum->seq = 0;
-    p.seq = sl.seq;
+    stamp_seq(c, sl, p);
     if (int e = launch_scan_simple(p, SrcFormat::kCs16, c->stream)) return fail(c, (hipError_t)e, "launch_scan_simple");
     if (with_match)
         if (int e = launch_match(p, c->stream)) return fail(c, (hipError_t)e, "launch_match");
@@ -115,16 +106,11 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
     p.src = d_iq;
     p.n_samples = n_samples;
     p.n_chunks = (uint32_t)n_chunks;
-    p.clean_bitmap = nullptr;
-    job.retired = nullptr;
-    bool fresh = false;
-    p.bitmap_lg = c->bitmap_lg;
+    // (an icao_flush, full bitmaps: the retired one is cleaned by the second phase's records kernel; folded ones: the
+    // next one is cleared in front of this shard's scan -- pass_params has the argument)
+    uint32_t fresh = 0;
+    pass_params(c, sl, p, &job.retired, &fresh);
     if (c->flush_pending) {
-        // (full bitmaps: the retired one is cleaned by the second phase's records kernel; folded ones: the next one
-        // is cleared in front of this shard's scan -- enqueue_pass has the argument)
-        if (c->bitmap_lg == kFullBitmapLg) job.retired = c->d_bitmap[c->cur_bitmap];
-        else fresh = true;
-        c->cur_bitmap = (c->cur_bitmap + 1) % c->n_bitmaps;
         c->filter.flush();
         c->flush_pending = false;
         // the device-side copy of the filter (exact bitmap, k_score) still holds the addresses from
@@ -139,25 +125,13 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
     if (job.exact_flush) c->cur_exact ^= 1;
     job.exact = fresh_list && c->score.si ? c->exact_bm[c->cur_exact] : nullptr;
     job.scored = job.wait_score = job.result_scored = false;
-    p.bitmap = c->d_bitmap[c->cur_bitmap];
-    p.hits = sl.d_hits;
-    p.hits_cap = sl.hits_cap;
-    p.ap = sl.d_ap;
-    p.ap_cap = c->ap_cap;
-    p.seg_cap = c->seg_cap;
-    p.dap = nullptr;  // the reference-shaped kernel's list: shard_chunk_pass() fills it in
-    p.dap_cap = 0;
-    p.tables = c->d_tables;
-    p.fix = (uint32_t)c->crc.fix;
-    p.ctr = sl.d_ctr;
-    p.summary = sl.h_sum_dev;
     p.keep_counters = 1;
     if (fresh_list) {
         p.fresh = job.h_fresh_dev;
         p.fresh_seen = job.d_fresh_seen;
         p.fresh_cap = c->shard_fresh_cap ? std::min<uint32_t>(c->shard_fresh_cap, (uint32_t)kShardAddrCap) : (uint32_t)kShardAddrCap;
         // a dense stream's shards: hits straight into their buffers' buckets, the second phase's records in replay
-        // order (enqueue_pass has the rules; only where phase 1 has no records kernel of its own to disturb the buckets)
+        // order (plan_pass has the rule; only where phase 1 has no records kernel of its own to disturb the buckets)
         if (c->shard_dense && n_chunks > kInlineTailChunks && sl.hits_cap == c->hits_cap) {
             p.order_cnt = sl.d_order_cnt;
             p.order_base = sl.d_order_base;
@@ -169,19 +143,12 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
             // (in every error-correction mode: ScanParams::fix tells k_score / k_emit what to repair)
             if (c->shard_scoring && c->score.si) {
                 job.scored = true;
-                p.score = sl.score;
-                p.score.exact = job.exact;
-                p.score.exact_retired = nullptr;
+                wire_score(sl, p, job.exact, nullptr);
                 p.score.earlier = job.d_fresh_seen;
-                p.score.out_msgs = sl.h_msgs_dev;
-                p.score.out_adds = sl.h_adds_dev;
-                p.score.summary = sl.h_ssum_dev;
             }
         }
     }
-    sl.seq = next_seq(c);
-    sl.h_sum->seq = 0;
-    p.seq = sl.seq;
+    stamp_seq(c, sl, p);
     job.p = p;
     job.by_chunk = false;
     job.chunk_records.clear();
@@ -199,14 +166,8 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
     // consecutive shards' scans alternate between the first two scan streams, like consecutive passes
     hipStream_t ss = c->scan_stream[c->shard_jobs++ % 2];
     job.scan_q = ss;
-    // the caller's samples are complete where `stream` stands now (nothing to wait for on the context's own,
-    // idle stream: see enqueue_pass)
-    if (!(c->stream == c->own_stream && !c->own_stream_dirty)) {
-        hipEvent_t ready = c->input_ready[ss == c->scan_stream[0] ? 0 : 1];
-        HIP_TRY(c, hipEventRecord(ready, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(ss, ready, 0));
-        c->own_stream_dirty = false;
-    }
+    // the caller's samples are complete where `stream` stands now
+    if (int rc = order_behind_input(c, nullptr, ss == c->scan_stream[0] ? 0 : 1, ss)) return rc;
     if (int rc = order_behind_fused(c, sl, ss)) return rc;
     // Phase 1 stays on its scan stream, no event: the tail stream is in order, and the first-phase records of the
     // NEXT shards (enqueued microseconds after this one's, each waiting for its own scan) would sit in front of
@@ -358,9 +319,7 @@ int shard_learned(adsb_ctx *c, int k, std::vector<uint32_t> &addrs)
             // more aircraft than the list holds: the records of the self-validating hits after all, behind the scan, and
             // the addresses out of those
             c->shard_fresh_fallbacks++;
-            sl.seq = next_seq(c);
-            sl.h_sum->seq = 0;
-            job.p.seq = sl.seq;
+            stamp_seq(c, sl, job.p);
             ScanParams q1 = job.p;
             q1.score = ScoreDev{};   // (the first phase's records go to the host, whoever scores the second's)
             if (int e = launch_order_hits(q1, job.scan_q)) return fail(c, (hipError_t)e, "launch_order_hits");   // (device-ordered: the buckets' places)
@@ -427,13 +386,7 @@ int shard_match(adsb_ctx *c, int k, const uint32_t *extra, size_t n_extra, const
             return fail(c, (hipError_t)e, "launch_set_addresses");
     } else if (n_extra) {
         // (more than a capture can teach: a caller's own union through adsb_shard_finish -- a device buffer, blocking)
-        if (n_extra > c->addrs_cap) {
-            if (c->d_addrs) (void)hipFree(c->d_addrs);
-            c->d_addrs = nullptr;
-            c->addrs_cap = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_addrs, n_extra * sizeof(uint32_t)));
-            c->addrs_cap = n_extra;
-        }
+        if (int rc = ensure_addrs(c, n_extra, n_extra)) return rc;
         HIP_TRY(c, hipStreamSynchronize(ts));   // (d_addrs may still be read by an earlier shard's launches)
         HIP_TRY(c, hipStreamSynchronize(qs));
         HIP_TRY(c, hipMemcpy(c->d_addrs, extra, n_extra * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -485,9 +438,7 @@ int shard_match(adsb_ctx *c, int k, const uint32_t *extra, size_t n_extra, const
         return ADSB_OK;
     }
     if (!job.by_chunk) {
-        sl.seq = next_seq(c);
-        sl.h_sum->seq = 0;
-        p.seq = sl.seq;
+        stamp_seq(c, sl, p);
         // (the first phase's records kernel published its summary a moment before it retired: it resets the
         // block counter this phase's records kernel counts in)
         HIP_TRY(c, hipStreamWaitEvent(ts, sl.scanned, 0));
