@@ -88,6 +88,32 @@ class AdsbMultiStats(C.Structure):
     ]
 
 
+class AdsbSignalStats(C.Structure):
+    """adsb_signal_stats (include/adsb_hip.h, "Signal statistics"): one buffer's integer record.  272 bytes."""
+    _fields_ = [
+        ("chunk", C.c_uint64),
+        ("sum_power", C.c_uint64),
+        ("n_samples", C.c_uint32),
+        ("peak", C.c_uint32),
+        ("n_strong", C.c_uint32),
+        ("n_clipped", C.c_uint32),
+        ("hist", C.c_uint32 * 60),
+    ]
+
+
+class AdsbSignalSummary(C.Structure):
+    """adsb_signal_summary_t: what adsb_signal_summary makes of any number of records."""
+    _fields_ = [
+        ("n_buffers", C.c_uint64),
+        ("n_samples", C.c_uint64),
+        ("mean_power_dbfs", C.c_double),
+        ("peak_dbfs", C.c_double),
+        ("median_dbfs", C.c_double),
+        ("clipped_fraction", C.c_double),
+        ("strong_fraction", C.c_double),
+    ]
+
+
 class AdsbError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
         self.status = status
@@ -152,6 +178,18 @@ def lib() -> C.CDLL:
     L.adsb_set_error_correction.restype = C.c_int
     L.adsb_get_error_correction.argtypes = [vp]
     L.adsb_get_error_correction.restype = C.c_int
+    L.adsb_set_signal_stats.argtypes = [vp, C.c_int]
+    L.adsb_set_signal_stats.restype = C.c_int
+    L.adsb_get_signal_stats.argtypes = [vp]
+    L.adsb_get_signal_stats.restype = C.c_int
+    L.adsb_fetch_signal_stats.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    L.adsb_fetch_signal_stats.restype = C.c_int
+    L.adsb_signal_bin.argtypes = [C.c_uint16]
+    L.adsb_signal_bin.restype = C.c_int
+    L.adsb_signal_summary.argtypes = [vp, sz, C.POINTER(AdsbSignalSummary)]
+    L.adsb_signal_summary.restype = C.c_int
+    L.adsb_selftest_signal_launches.argtypes = [vp]
+    L.adsb_selftest_signal_launches.restype = C.c_uint64
     L.adsb_replay_records_fix.argtypes = [vp, vp, sz, C.c_int, vp, sz, C.POINTER(sz)]
     L.adsb_replay_records_fix.restype = C.c_int
     L.adsb_selftest_fix_table.argtypes = [vp]

@@ -90,6 +90,23 @@ def _as_cu8(iq) -> np.ndarray:
 TRIAL_DTYPE = np.dtype([("power", "<u8"), ("chunk", "<u4"), ("j_tp", "<u4"), ("msg", "u1", (14,)), ("pad", "<u2")])
 
 
+# adsb_signal_stats as a numpy record (272 bytes)
+SIGNAL_STATS_DTYPE = np.dtype([("chunk", "<u8"), ("sum_power", "<u8"), ("n_samples", "<u4"), ("peak", "<u4"),
+                               ("n_strong", "<u4"), ("n_clipped", "<u4"), ("hist", "<u4", (60,))])
+assert SIGNAL_STATS_DTYPE.itemsize == C.sizeof(_lib.AdsbSignalStats) == 272
+
+
+def signal_summary(records: np.ndarray) -> dict:
+    """adsb_signal_summary over any number of signal records (host only): buffers, samples, mean power, peak and
+    median (the noise floor) in dBFS, and the clipped and strong fractions."""
+    rec = np.ascontiguousarray(records, dtype=SIGNAL_STATS_DTYPE)
+    out = _lib.AdsbSignalSummary()
+    st = _lib.lib().adsb_signal_summary(rec.ctypes.data if rec.size else None, rec.size, C.byref(out))
+    if st != _lib.ADSB_OK:
+        raise AdsbError(st, "adsb_signal_summary")
+    return {name: getattr(out, name) for name, _ in _lib.AdsbSignalSummary._fields_}
+
+
 def replay_records(records: np.ndarray, filter_table: Optional[np.ndarray] = None, cap: Optional[int] = None,
                    mode: int = 0) -> List["ModeSMessage"]:
     """adsb_replay_records: the ordered host replay (scoring + best-of-5 + ICAO filter) over raw
@@ -406,6 +423,23 @@ class Context:
         repair of DF17/18 from known aircraft, score _lib.ADSB_SCORE_FIXED_1BIT) or _lib.ADSB_FIX_2BIT (one or two
         flipped bits; a two-bit repair scores _lib.ADSB_SCORE_FIXED_2BIT); for the passes submitted after it."""
         self._check(self._L.adsb_set_error_correction(self._h, int(mode)), "adsb_set_error_correction")
+
+    def set_signal_stats(self, enabled: bool) -> None:
+        """adsb_set_signal_stats: opt-in; the passes submitted after it also deliver one integer record per
+        131072-sample buffer (signal_stats())."""
+        self._check(self._L.adsb_set_signal_stats(self._h, 1 if enabled else 0), "adsb_set_signal_stats")
+
+    def signal_stats(self) -> np.ndarray:
+        """adsb_fetch_signal_stats: the records of the pass collected last (or of the blocking call returned last),
+        one per buffer in buffer order, as a structured array with the layout of adsb_signal_stats; empty when
+        that pass ran with the mode off."""
+        n = C.c_size_t()
+        st = self._L.adsb_fetch_signal_stats(self._h, None, 0, C.byref(n))
+        out = np.zeros(n.value, dtype=SIGNAL_STATS_DTYPE)
+        if n.value:
+            st = self._L.adsb_fetch_signal_stats(self._h, out.ctypes.data, n.value, C.byref(n))
+        self._check(st, "adsb_fetch_signal_stats")
+        return out
 
     @property
     def error_correction(self) -> int:

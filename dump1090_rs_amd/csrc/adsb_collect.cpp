@@ -75,6 +75,38 @@ bool summary_landed(const Summary *s, uint32_t seq)
     return w[7] == seq && summary_check(w) == w[9];
 }
 
+// The signal records of the pass in `sl` (adsb_set_signal_stats) out of the slot's mapped memory into c->sig_out.  They
+// were written by a kernel in front of the pass's scan on the scan's own stream, so they are there when the pass's summary
+// is: one look, no waiting.  That look is a real check all the same: the records were overwritten with ones when the pass
+// was enqueued, and no 8-byte word of a record can be all ones (a buffer index below 2^19, a sum below 2^49, counts of at
+// most 131072) -- so a record with such a word, with another buffer's index or sample count, or whose histogram does not
+// add up to its samples is not this pass's whole record, and the pass fails loudly instead of reporting it.
+int take_signal_records(adsb_ctx *c, const Slot &sl)
+{
+    c->sig_out.resize(sl.n_chunks);
+    for (uint32_t i = 0; i < sl.n_chunks; i++) {
+        const uint64_t left = sl.n_samples - (uint64_t)i * kChunkSamples;
+        const uint32_t want_n = (uint32_t)std::min<uint64_t>(left, kChunkSamples);
+        adsb_signal_stats r;
+        const uint64_t *w = reinterpret_cast<const uint64_t *>(&sl.h_sig[i]);
+        uint64_t *d = reinterpret_cast<uint64_t *>(&r);
+        bool whole = true;
+        for (size_t k = 0; k < sizeof(r) / 8; k++) {
+            d[k] = __atomic_load_n(&w[k], __ATOMIC_RELAXED);
+            whole = whole && d[k] != ~0ull;
+        }
+        uint64_t in_bins = 0;
+        for (uint32_t h : r.hist) in_bins += h;
+        if (!whole || r.chunk != i || r.n_samples != want_n || in_bins != want_n) {
+            c->sig_out.clear();
+            c->last_error = "signal records in host memory are not the whole records of the pass that wrote them";
+            return ADSB_ERR_HIP;
+        }
+        c->sig_out[i] = r;
+    }
+    return ADSB_OK;
+}
+
 // Wait for the pass in `sl` and replay it.  Returns 1 when a device list overflowed
 // (caller re-runs in smaller pieces), 0 on success, < 0 on error.
 int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, std::vector<adsb_msg> &out)
@@ -295,6 +327,9 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         }
         c->flush_pending = keep_flush;
     }
+    // (a pass the fallback or the rematch ran again launched no second k_signal_stats: the records are the first enqueue's)
+    c->sig_out.clear();
+    if (rc == 0 && sl.sig_on) rc = take_signal_records(c, sl);
     sl.busy = false;
     c->collected++;
     if (rc > 0) {
@@ -309,13 +344,18 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
 // Finish every pass in flight now; the caller still gets them from adsb_collect, in order.
 int park_pending(adsb_ctx *c)
 {
+    std::vector<adsb_signal_stats> callers;   // (what adsb_fetch_signal_stats hands out is the caller's last collect's)
+    callers.swap(c->sig_out);
     while (c->collected < c->submitted) {
         Slot &sl = c->slot[c->collected % (uint64_t)c->n_slots];
         sl.parked_msgs.clear();
         sl.park_rc = collect_oldest(c, sl.parked_msgs);
         sl.parked_stats = c->stats;
+        sl.parked_sig.clear();
+        sl.parked_sig.swap(c->sig_out);
         sl.parked = true;
     }
+    c->sig_out.swap(callers);
     return ADSB_OK;
 }
 
@@ -327,6 +367,8 @@ int collect_next(adsb_ctx *c, std::vector<adsb_msg> &out)
         out.swap(sl.parked_msgs);
         sl.parked_msgs.clear();
         c->stats = sl.parked_stats;
+        c->sig_out.swap(sl.parked_sig);
+        sl.parked_sig.clear();
         sl.parked = false;
         c->delivered++;
         return sl.park_rc;

@@ -345,6 +345,40 @@ try {
     return ADSB_OK;
 } ADSB_ABI_CATCH
 
+}  // extern "C"
+
+namespace adsb {
+namespace host {
+
+// Signal statistics: per pass in flight max_chunks records in mapped host memory (written once each by k_signal_stats)
+// and as many partials plus a ticket per buffer in device memory, zero between passes.  Reserved the first time the mode
+// is enabled, so that a context that never enables it keeps the footprint include/adsb_hip.h documents.
+int ensure_signal_stats(adsb_ctx *c)
+{
+    if (c->h_sig_block && c->d_sig_block) return ADSB_OK;
+    const size_t rec_bytes = (c->max_chunks * sizeof(adsb_signal_stats) + 255) & ~(size_t)255;
+    const size_t part_words = c->max_chunks * (size_t)kSigRecordWords, slot_words = (part_words + c->max_chunks + 63) & ~(size_t)63;
+    char *h_dev = nullptr;
+    if (!c->h_sig_block)
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_sig_block, rec_bytes * (size_t)c->n_slots, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(c, hipHostGetDevicePointer((void **)&h_dev, c->h_sig_block, 0));
+    if (!c->d_sig_block) HIP_TRY(c, hipMalloc((void **)&c->d_sig_block, slot_words * (size_t)c->n_slots * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(c->d_sig_block, 0, slot_words * (size_t)c->n_slots * sizeof(uint32_t)));
+    for (int si = 0; si < c->n_slots; si++) {
+        Slot &sl = c->slot[si];
+        sl.h_sig = reinterpret_cast<adsb_signal_stats *>(c->h_sig_block + rec_bytes * (size_t)si);
+        sl.h_sig_dev = reinterpret_cast<adsb_signal_stats *>(h_dev + rec_bytes * (size_t)si);
+        sl.d_sig_part = c->d_sig_block + slot_words * (size_t)si;
+        sl.d_sig_ticket = sl.d_sig_part + part_words;
+    }
+    return ADSB_OK;
+}
+
+}  // namespace host
+}  // namespace adsb
+
+extern "C" {
+
 void adsb_destroy(adsb_ctx *c)
 {
     if (!c) return;
@@ -398,6 +432,8 @@ void adsb_destroy(adsb_ctx *c)
     if (c->lazy_ev) (void)hipEventDestroy(c->lazy_ev);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_block) (void)hipHostFree(c->h_block);
+    if (c->h_sig_block) (void)hipHostFree(c->h_sig_block);
+    if (c->d_sig_block) (void)hipFree(c->d_sig_block);
     if (c->tail_stream) (void)hipStreamSynchronize(c->tail_stream);
     for (Slot &sl : c->slot) {
         for (void *q : {(void *)sl.score.si, (void *)sl.score.rec, (void *)sl.score.flag, (void *)sl.score.slot, (void *)sl.score.pos,
@@ -581,6 +617,30 @@ try {
 
 int adsb_get_error_correction(const adsb_ctx *c) { return c ? c->crc.fix : ADSB_ERR_INVALID; }
 
+int adsb_set_signal_stats(adsb_ctx *c, int enabled)
+try {
+    if (!c) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    if (enabled) {
+        ADSB_ON_DEVICE(c);
+        if (int rc = ensure_signal_stats(c)) return rc;
+    }
+    c->signal_stats = enabled != 0;
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_get_signal_stats(const adsb_ctx *c) { return c ? (c->signal_stats ? 1 : 0) : ADSB_ERR_INVALID; }
+uint64_t adsb_selftest_signal_launches(const adsb_ctx *c) { return c ? c->sig_launches : 0; }
+
+int adsb_fetch_signal_stats(adsb_ctx *c, adsb_signal_stats *out, size_t cap, size_t *n_out)
+try {
+    if (!c || (!out && cap)) return ADSB_ERR_INVALID;
+    const size_t n = std::min(cap, c->sig_out.size());
+    if (n) std::memcpy(out, c->sig_out.data(), n * sizeof(adsb_signal_stats));
+    if (n_out) *n_out = c->sig_out.size();
+    return c->sig_out.size() > cap ? ADSB_ERR_CAPACITY : ADSB_OK;
+} ADSB_ABI_CATCH
+
 int adsb_set_u8_table(adsb_ctx *c, const int16_t *table256)
 try {
     if (!c) return ADSB_ERR_INVALID;
@@ -631,6 +691,6 @@ int adsb_get_stats(const adsb_ctx *c, adsb_stats *out)
 
 const char *adsb_last_error(const adsb_ctx *c) { return c ? c->last_error.c_str() : ""; }
 
-const char *adsb_version(void) { return "adsb_hip 0.21 gfx950 scan=v9-tile-buckets tail=v7-folded-supersets multi=v3-bounded-waits streams=v2-own-queues"; }
+const char *adsb_version(void) { return "adsb_hip 0.22 gfx950 scan=v9-tile-buckets tail=v7-folded-supersets multi=v3-bounded-waits streams=v2-own-queues stats=v1"; }
 
 }  // extern "C"

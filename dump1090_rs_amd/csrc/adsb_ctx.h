@@ -90,6 +90,13 @@ struct Slot {
     int profiled = 0;  // profiling level the pass was enqueued with
     bool redo = false;  // enqueued by collect_oldest (overflow fallback, rematch): keeps the pass's number, times itself with
                         // the context's redo events, and stays out of ms_scan_exclusive's frontier
+    // signal statistics (adsb_set_signal_stats): whether this pass counts them; the slot's records in the context's mapped
+    // block and its partials and tickets in device memory (all null until the mode is first enabled); and the records of a
+    // pass park_pending finished ahead of the caller
+    bool sig_on = false;
+    adsb_signal_stats *h_sig = nullptr, *h_sig_dev = nullptr;
+    uint32_t *d_sig_part = nullptr, *d_sig_ticket = nullptr;
+    std::vector<adsb_signal_stats> parked_sig;
 };
 
 // Passes in flight: 4 and the device never waits for the host between large passes (3 do for sparse
@@ -284,6 +291,14 @@ struct adsb_ctx {
 #endif
     std::vector<adsb_msg> undelivered;
     bool has_undelivered = false;
+    // signal statistics (adsb_set_signal_stats): the mode of the passes submitted from now on; every slot's records
+    // (one mapped pinned block) and partials + tickets (one device block), reserved when the mode is first enabled;
+    // the records of the pass collected last / the blocking call returned last (adsb_fetch_signal_stats)
+    bool signal_stats = false;
+    char *h_sig_block = nullptr;
+    uint32_t *d_sig_block = nullptr;
+    std::vector<adsb_signal_stats> sig_out;
+    uint64_t sig_launches = 0;   // k_signal_stats launches so far (adsb_selftest_signal_launches)
 };
 
 namespace adsb {
@@ -414,6 +429,9 @@ int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<
 void soapy_u8_table(int16_t *out256);
 int ensure_stage(adsb_ctx *c, size_t bytes);
 int ensure_host_stage(adsb_ctx *c, size_t bytes);
+
+// adsb_context.cpp: the signal-statistics storage of every slot, on first enable
+int ensure_signal_stats(adsb_ctx *c);
 
 // adsb_collect.cpp
 int verify_records(adsb_ctx *c, const Summary *sum, const TrialRecord *rec, size_t n);

@@ -341,6 +341,25 @@ int launch_set_addresses(const uint32_t *d_addrs, uint32_t n, uint32_t *bitmap, 
 int launch_update_carry(const uint32_t *prev, const void *d_src, uint64_t n_samples, uint32_t *next, void *stream,
                         const uint16_t *u8_table = nullptr);
 int launch_mag_digest(uint32_t first_bits, uint32_t count, unsigned long long *d_out, void *stream);
+
+// Signal statistics (adsb_set_signal_stats; adsb_stats.hip: k_signal_stats): one adsb_signal_stats per buffer of a
+// pass.  A kernel of its own beside the scan, with parameters of its own -- ScanParams and the scan's instantiations
+// stay as they are.
+constexpr int kSigHistBins = 60;
+constexpr int kSigRecordWords = 68;      // sizeof(adsb_signal_stats) / 4
+constexpr int kSigMaxWgPerChunk = 64;    // workgroups a buffer is cut into at most (a power of two)
+struct SigParams {
+    const void *src;          // the pass's IQ: CS16 dwords or CU8 byte pairs, 16-byte aligned
+    uint64_t n_samples;
+    uint32_t n_chunks;
+    uint32_t wg_per_chunk;    // signal_stats_wg_per_chunk(n_chunks)
+    const uint16_t *u8_table; // CU8: the widening table (device memory), else null
+    uint32_t *partial;        // device memory, kSigRecordWords per buffer, laid out as the record: all zero between passes
+    uint32_t *ticket;         // device memory, one per buffer: workgroups of the buffer that have finished; zero between passes
+    void *records;            // mapped host memory: adsb_signal_stats[n_chunks], each written once by its buffer's last workgroup
+};
+uint32_t signal_stats_wg_per_chunk(uint32_t n_chunks);
+int launch_signal_stats(const SigParams &p, SrcFormat fmt, void *stream);
 // self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
 int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 

@@ -5,7 +5,13 @@
 // the dump1090 raw format) can consume it.
 //
 //   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K]
-//             [--latency-ms T] [--readers R] <capture.iq | ->
+//             [--latency-ms T] [--readers R] [--stats [SECONDS]] <capture.iq | ->
+//
+// --stats turns the signal statistics on (adsb_set_signal_stats) and prints what a receiver's gain is tuned by to
+// STDERR, every SECONDS (default 1) over the buffers since the last line and once more, as the last line, over the
+// whole input: the number of buffers, the noise floor (the median magnitude), the mean power and the peak in dBFS, and
+// the shares of clipped and of strong (above -3 dBFS) samples.  stdout and the TCP stream are byte for byte what they
+// are without the flag.
 //
 // --fix 1bit repairs DF17/18 frames with one flipped bit from aircraft already heard, --fix 2bit with one or two
 // (adsb_set_error_correction);
@@ -126,6 +132,30 @@ struct Clients {
     {
         for (int s : socks) ::close(s);
         if (listener >= 0) ::close(listener);
+    }
+};
+
+// --stats: signal records folded together (sums; the peak is a maximum) -- adsb_signal_summary takes any number of
+// records, so a run of any length is a handful of them: a new one is begun before a 32-bit count could wrap.
+struct SignalFold {
+    std::vector<adsb_signal_stats> folded;
+    unsigned long long buffers = 0;
+    void add(const adsb_signal_stats &r)
+    {
+        if (folded.empty() || (unsigned long long)folded.back().n_samples + r.n_samples > 0x7FFFFFFFull) folded.push_back(adsb_signal_stats{});
+        adsb_signal_stats &f = folded.back();
+        f.sum_power += r.sum_power, f.n_samples += r.n_samples, f.n_strong += r.n_strong, f.n_clipped += r.n_clipped;
+        if (r.peak > f.peak) f.peak = r.peak;
+        for (int b = 0; b < ADSB_SIGNAL_BINS; b++) f.hist[b] += r.hist[b];
+        buffers++;
+    }
+    void clear() { folded.clear(), buffers = 0; }
+    void print(const char *scope) const
+    {
+        adsb_signal_summary_t s{};
+        if (adsb_signal_summary(folded.data(), folded.size(), &s) != ADSB_OK) return;
+        std::fprintf(stderr, "adsb_feed: stats (%s): buffers %llu, floor %.3f dBFS, mean %.3f dBFS, peak %.3f dBFS, clipped %.6f %%, strong %.6f %%\n",
+                     scope, buffers, s.median_dbfs, s.mean_power_dbfs, s.peak_dbfs, 100.0 * s.clipped_fraction, 100.0 * s.strong_fraction);
     }
 };
 
@@ -277,7 +307,8 @@ private:
 int main(int argc, char **argv)
 {
     int device = 0, port = 0, buffers = 64, latency_ms = 100, out_cap = 0, readers = 4;
-    bool quiet = false, mem_order = false, cu8 = false;
+    bool quiet = false, mem_order = false, cu8 = false, stats = false;
+    double stats_seconds = 1.0;
     int fix = ADSB_FIX_NONE;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
@@ -288,6 +319,12 @@ int main(int argc, char **argv)
         else if (a == "--latency-ms" && i + 1 < argc) latency_ms = std::atoi(argv[++i]);
         else if (a == "--readers" && i + 1 < argc) readers = std::atoi(argv[++i]);
         else if (a == "--out-cap" && i + 1 < argc) out_cap = std::atoi(argv[++i]);  // frames the output array starts with (it grows)
+        else if (a == "--stats") {
+            stats = true;
+            char *end = nullptr;   // SECONDS is optional: taken when the next argument is a positive number and nothing else
+            const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 < argc && end != argv[i + 1] && *end == 0 && v > 0) stats_seconds = v, i++;
+        }
         else if (a == "--quiet") quiet = true;
         else if (a == "--mem-order") mem_order = true;
         else if (a == "--format" && i + 1 < argc) {
@@ -307,7 +344,7 @@ int main(int argc, char **argv)
         else path = argv[i];
     }
     if (!path || buffers < 1) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] <capture.iq | ->\n");
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -326,6 +363,7 @@ int main(int argc, char **argv)
     int st = adsb_create(&ctx, device, (size_t)buffers);
     if (st != ADSB_OK) return die(nullptr, "adsb_create", st);
     if ((st = adsb_set_error_correction(ctx, fix)) != ADSB_OK) return die(ctx, "adsb_set_error_correction", st);
+    if (stats && (st = adsb_set_signal_stats(ctx, 1)) != ADSB_OK) return die(ctx, "adsb_set_signal_stats", st);
     const size_t slot_samples = (size_t)buffers * ADSB_MODES_MAG_BUF_SAMPLES;
     if ((st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
         return die(ctx, "adsb_ring_create", st);
@@ -335,6 +373,9 @@ int main(int argc, char **argv)
     // positions can each emit one, so leave an order of magnitude of room
     std::vector<adsb_msg> out(out_cap > 0 ? (size_t)out_cap : (size_t)buffers * 4096);
     unsigned long long total_samples = 0, total_frames = 0;
+    SignalFold sig_interval, sig_total;
+    std::vector<adsb_signal_stats> sig((size_t)buffers);
+    auto t_stats = std::chrono::steady_clock::now();
     auto drain_one = [&]() -> int {
         size_t n = 0;
         int rc = adsb_collect(ctx, out.data(), out.size(), &n);
@@ -343,6 +384,17 @@ int main(int argc, char **argv)
             rc = adsb_fetch_messages(ctx, out.data(), out.size(), &n);
         }
         if (rc != ADSB_OK) return rc;
+        if (stats) {   // the pass's signal records: one per buffer (a pass never holds more than `buffers`)
+            size_t n_sig = 0;
+            if ((rc = adsb_fetch_signal_stats(ctx, sig.data(), sig.size(), &n_sig)) != ADSB_OK) return rc;
+            for (size_t i = 0; i < n_sig; i++) sig_interval.add(sig[i]), sig_total.add(sig[i]);
+            const auto now = std::chrono::steady_clock::now();
+            if (std::chrono::duration<double>(now - t_stats).count() >= stats_seconds) {
+                sig_interval.print("interval");
+                sig_interval.clear();
+                t_stats = now;
+            }
+        }
         std::string lines;
         char line[40];
         for (size_t i = 0; i < n; i++) {
@@ -442,6 +494,7 @@ int main(int argc, char **argv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     std::fprintf(stderr, "adsb_feed: %llu samples, %llu frames in %.3f s (%.1f Msamples/s); %llu short passes, %llu clients dropped\n",
                  total_samples, total_frames, secs, secs > 0 ? total_samples / secs / 1e6 : 0.0, short_passes, clients.dropped);
+    if (stats) sig_total.print("whole input");
     if (in != 0) ::close(in);
     adsb_destroy(ctx);
     return 0;

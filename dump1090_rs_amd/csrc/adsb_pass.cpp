@@ -428,6 +428,35 @@ static int enqueue_tail(adsb_ctx *c, Slot &sl, const ScanParams &p, SrcFormat fm
     return ADSB_OK;
 }
 
+// Step 6b -- the pass's signal statistics (adsb_set_signal_stats), only when the mode is on: k_signal_stats over the
+// pass's input, one record per buffer into the slot's part of the context's mapped block.  It obeys the stream rule the
+// scan obeys -- it goes out on the scan stream plan_pass chose, in front of the scan launch, behind the same input edge
+// and edge 0 (the slot's partials are the slot's lists' kin) -- and places no edge of its own: the scan, and behind it the
+// tail or the one launch's last workgroup, which publish the pass's summary, are in stream order behind it, so the
+// summary never lands before the records have.  A pass that is run again (overflow fallback, rematch) and the reference-
+// shaped kernel's passes launch none: the records of the first enqueue stand, computed once.
+static int enqueue_signal_stats(adsb_ctx *c, Slot &sl, const ScanParams &p, SrcFormat fmt, const PassOptions &opt, const PassPlan &pl)
+{
+    if (opt.redo) return ADSB_OK;   // (sl.sig_on stays what the pass's first enqueue made it)
+    sl.sig_on = c->signal_stats && pl.fast && sl.h_sig != nullptr;
+    if (!sl.sig_on) return ADSB_OK;
+    SigParams sp{};
+    sp.src = p.src;
+    sp.n_samples = p.n_samples;
+    sp.n_chunks = p.n_chunks;
+    sp.wg_per_chunk = signal_stats_wg_per_chunk(p.n_chunks);
+    sp.u8_table = p.u8_table;
+    sp.partial = sl.d_sig_part;
+    sp.ticket = sl.d_sig_ticket;
+    sp.records = sl.h_sig_dev;
+    // (what take_signal_records checks every 8-byte word of every record against: no word of a record is ever all ones,
+    // so a piece of the slot's previous pass cannot pass for this one's)
+    std::memset(sl.h_sig, 0xFF, (size_t)p.n_chunks * sizeof(adsb_signal_stats));
+    if (int e = launch_signal_stats(sp, fmt, pl.ss)) return fail(c, (hipError_t)e, "launch_signal_stats");
+    c->sig_launches++;
+    return ADSB_OK;
+}
+
 // Step 7 -- scoring on the device (edge 4) and the completion event (edge 5).
 static int enqueue_score(adsb_ctx *c, Slot &sl, const ScanParams &p, const PassPlan &pl)
 {
@@ -464,6 +493,7 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
     fill_pass(c, sl, p, d_src, fmt, n_samples, n_chunks, opt, pl);
     if (int rc = order_behind_input(c, opt.input_done, pl.si, pl.ss)) return rc;   // edge in
     if (int rc = edges_before_scan(c, sl, p, pl)) return rc;             // edges 0, 1'', one launch: 1, 2, 3'
+    if (int rc = enqueue_signal_stats(c, sl, p, fmt, opt, pl)) return rc;  // (no edge: stream order on the scan stream)
     if (int rc = launch_scan_step(c, sl, p, fmt, opt, pl)) return rc;    // (row 6)
     if (pl.fused) {   // everything is out; what the next pass has to know about this one
         sl.tail_q = c->prev_scan_stream = pl.ss;
@@ -562,11 +592,16 @@ int run_sync(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, 
 
 // A long stream goes in pieces: the messages of the piece at sample `off` (chunk = buffer of the stream) and the
 // stats its pass left in the context join the call's.
-static void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, std::vector<adsb_msg> &out, adsb_stats &total)
+static void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, std::vector<adsb_msg> &out, adsb_stats &total,
+                         std::vector<adsb_signal_stats> &sig)
 {
     for (auto &m : part) {
         m.chunk += off / kChunkSamples;
         out.push_back(m);
+    }
+    for (adsb_signal_stats r : c->sig_out) {   // (the piece's signal records, when the mode is on)
+        r.chunk += off / kChunkSamples;
+        sig.push_back(r);
     }
     const adsb_stats &st = c->stats;
     total.n_chunks += st.n_chunks, total.n_candidates += st.n_candidates, total.n_ap_entries += st.n_ap_entries;
@@ -580,9 +615,11 @@ int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<
 {
     if (n_samples == 0) {
         c->stats = adsb_stats{};
+        c->sig_out.clear();
         return ADSB_OK;
     }
     adsb_stats total{};
+    std::vector<adsb_signal_stats> sig;
     // a device pass takes at most max_chunks buffers (what the context's lists were sized for;
     // never more than kMaxChunks: entry packing): longer streams go in pieces, which is what
     // consecutive calls would be -- buffers are independent but for the filter
@@ -592,10 +629,11 @@ int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<
         std::vector<adsb_msg> part;
         int rc = run_sync(c, (const char *)d_iq + off * src_bytes_per_sample(fmt), fmt, n, part);
         if (rc) return rc;
-        append_piece(c, part, off, out, total);
+        append_piece(c, part, off, out, total, sig);
     }
     total.n_samples = n_samples;
     c->stats = total;
+    c->sig_out.swap(sig);
     return ADSB_OK;
 }
 
@@ -691,6 +729,8 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
     // stage through the device in pieces of at most max_chunks chunks
     std::vector<adsb_msg> msgs;
     adsb_stats total{};
+    std::vector<adsb_signal_stats> sig;
+    if (c->submitted == c->delivered) c->sig_out.clear();   // (a call of no samples runs no pass: no records)
     const size_t piece = c->max_chunks * (size_t)kChunkSamples;
     // A call of a few buffers (the reference's own call shape, benches/demod_benchmark.rs:10-11: one
     // 131072-sample buffer) is one launch that reads the samples in place from pinned host memory: one
@@ -713,7 +753,8 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
     int rc = in_place ? ensure_host_stage(c, std::max<size_t>(n_samples, 1) * bps + 512)   // (+ the progress word)
                       : ensure_stage(c, std::min(piece, std::max<size_t>(n_samples, 1)) * bps);
     if (rc) return rc;
-    if (in_place && n_samples && n_samples <= piece &&
+    // (not with signal statistics on: k_signal_stats goes out in front of the scan and waits for no progress word)
+    if (in_place && n_samples && n_samples <= piece && !c->signal_stats &&
         one_launch_pass(c, (uint32_t)((n_samples + kChunkSamples - 1) / kChunkSamples))) {
         // One pass of one launch: launch it FIRST and copy the samples into the pinned buffer while the launch is on its way
         // (dispatch latency ~5 us, the copy ~10): each workgroup waits for the host's progress word to pass the
@@ -747,10 +788,11 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
             std::vector<adsb_msg> part;
             rc = run_sync(c, (const char *)c->h_stage_dev + off * bps, fmt, n, part, input_ready_now());
             if (rc) return rc;
-            append_piece(c, part, off, msgs, total);
+            append_piece(c, part, off, msgs, total, sig);
         }
         total.n_samples = n_samples;
         c->stats = total;
+        c->sig_out.swap(sig);
         return deliver(c, msgs, out, cap, n_out);
     }
     for (size_t off = 0; off < n_samples; off += piece) {
@@ -760,10 +802,11 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
         std::vector<adsb_msg> part;
         rc = demod_device(c, c->d_stage, n, part, fmt);
         if (rc) return rc;
-        append_piece(c, part, off, msgs, total);
+        append_piece(c, part, off, msgs, total, sig);
     }
     total.n_samples = n_samples;
     c->stats = total;
+    c->sig_out.swap(sig);
     return deliver(c, msgs, out, cap, n_out);
 }
 }  // namespace
@@ -793,6 +836,7 @@ try {
     c->stats = adsb_stats{};
     c->stats.n_samples = length;
     c->stats.n_chunks = 1;
+    c->sig_out.clear();   // (the caller's magnitudes: no signal records)
     std::vector<adsb_msg> msgs;
     if (length) {
         // the caller's MagnitudeBuffer into pinned memory; the pass (one launch) reads it in place

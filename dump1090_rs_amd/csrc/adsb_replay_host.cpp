@@ -14,7 +14,9 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <cmath>
 #include <iterator>
+#include <limits>
 
 using namespace adsb;
 
@@ -665,6 +667,47 @@ int adsb_selftest_crc_table(uint32_t *out256)
     if (!out256) return ADSB_ERR_INVALID;
     static const Crc24 crc;  // the table the host replay scores with (mode_s_host.hpp)
     std::memcpy(out256, crc.t, sizeof(crc.t));
+    return ADSB_OK;
+}
+
+// Signal statistics, the host-only part (include/adsb_hip.h, "Signal statistics").
+int adsb_signal_bin(uint16_t m)
+{
+    if (m < 8) return m;
+    int e = 3;
+    while ((m >> (e + 1)) != 0) e++;   // floor(log2 m), 3..15
+    return 8 + 4 * (e - 3) + ((m >> (e - 2)) & 3);
+}
+
+int adsb_signal_summary(const adsb_signal_stats *s, size_t n, adsb_signal_summary_t *out)
+{
+    if (!out || (!s && n)) return ADSB_ERR_INVALID;
+    const double minus_inf = -std::numeric_limits<double>::infinity(), full = 65535.0;
+    uint64_t samples = 0, power = 0, clipped = 0, strong = 0, hist[ADSB_SIGNAL_BINS] = {};
+    uint32_t peak = 0;
+    for (size_t i = 0; i < n; i++) {
+        samples += s[i].n_samples, power += s[i].sum_power, clipped += s[i].n_clipped, strong += s[i].n_strong;
+        peak = std::max(peak, s[i].peak);
+        for (int b = 0; b < ADSB_SIGNAL_BINS; b++) hist[b] += s[i].hist[b];
+    }
+    // the lower edge of the bin that holds the (samples + 1) / 2-th smallest magnitude
+    uint32_t edge = 0;
+    const uint64_t rank = (samples + 1) / 2;
+    uint64_t below = 0;
+    for (int b = 0; b < ADSB_SIGNAL_BINS && samples; b++) {
+        below += hist[b];
+        if (below >= rank) {
+            edge = b < 8 ? (uint32_t)b : (uint32_t)(4 + (b - 8) % 4) << ((b - 8) / 4 + 1);
+            break;
+        }
+    }
+    out->n_buffers = n;
+    out->n_samples = samples;
+    out->mean_power_dbfs = samples && power ? 10.0 * std::log10((double)power / (double)samples / (full * full)) : minus_inf;
+    out->peak_dbfs = peak ? 20.0 * std::log10((double)peak / full) : minus_inf;
+    out->median_dbfs = edge ? 20.0 * std::log10((double)edge / full) : minus_inf;
+    out->clipped_fraction = samples ? (double)clipped / (double)samples : 0.0;
+    out->strong_fraction = samples ? (double)strong / (double)samples : 0.0;
     return ADSB_OK;
 }
 

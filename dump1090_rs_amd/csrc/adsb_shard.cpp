@@ -577,6 +577,7 @@ try {
     if (c->submitted != c->delivered || c->shard_active || c->shard[0].active) return ADSB_ERR_BUSY;
     if (n_addrs) *n_addrs = 0;
     if ((uintptr_t)device_iq % 16) return ADSB_ERR_INVALID;
+    c->sig_out.clear();   // (a shard delivers no signal records: adsb_fetch_signal_stats has none of an earlier pass's either)
     // (the caller may be a worker thread whose current device is not this context's: sharding.ShardPipeline)
     ADSB_ON_DEVICE(c);
     if (int rc = shard_begin(c, 0, device_iq, n_samples)) return rc;

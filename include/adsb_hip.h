@@ -327,6 +327,74 @@ int adsb_set_carry_over(adsb_ctx *ctx, int enabled);
 int adsb_set_error_correction(adsb_ctx *ctx, int mode);
 int adsb_get_error_correction(const adsb_ctx *ctx);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Signal statistics -- opt-in, off by default; with the mode off nothing observable changes (the same frames, the
+ * same kernels launched, the same footprint).  With it on every pass also delivers one small integer record per
+ * 131072-sample buffer: what a receiver's gain is tuned by -- where the noise floor sits, how hot the loudest samples
+ * are, how much of the stream hits the ADC rails.  The magnitudes never exist in memory on the IQ path, so they are
+ * counted on the device, by a kernel of its own beside the scan that reads the pass's input once more.
+ *
+ * Buffer c of a call has n valid samples; its magnitudes are m[k] = to_mag(iq)[k], the u16 values adsb_to_mag returns
+ * and the scan computes (the same device function; _u8 input is first widened through the context's table).  The
+ * zero lead-in, the zero tail and the samples carried over from the previous buffer under adsb_set_carry_over are
+ * NOT counted.  Every field is an exact integer: it equals the plain restatement, whatever order the device adds in. */
+#define ADSB_SIGNAL_BINS 60
+typedef struct adsb_signal_stats {
+    uint64_t chunk;      /* index of the buffer inside the call, as adsb_msg.chunk */
+    uint64_t sum_power;  /* sum of m[k]^2  (< 2^49) */
+    uint32_t n_samples;  /* n */
+    uint32_t peak;       /* max m[k], 0 for an empty buffer */
+    uint32_t n_strong;   /* samples with 2*m^2 >= 65535^2  (above -3 dBFS) */
+    uint32_t n_clipped;  /* samples with a component at a rail: CS16 re or im in {-32768, 32767};
+                            CU8 a byte in {0, 255} (on the bytes, before widening) */
+    uint32_t hist[60];   /* hist[adsb_signal_bin(m[k])]++  (ADSB_SIGNAL_BINS of them) */
+} adsb_signal_stats;     /* 272 bytes */
+
+/* What a gain display shows, over any number of records (adsb_signal_summary). */
+typedef struct adsb_signal_summary_t {
+    uint64_t n_buffers;
+    uint64_t n_samples;
+    double mean_power_dbfs;  /* 10 log10(sum of sum_power / n_samples / 65535^2) */
+    double peak_dbfs;        /* 20 log10(max peak / 65535) */
+    double median_dbfs;      /* the noise floor, which aircraft bursts do not move: 20 log10(e / 65535), e the lower edge
+                                of the bin that holds the (n_samples + 1) / 2-th smallest magnitude */
+    double clipped_fraction; /* sum of n_clipped / n_samples (0 when there are no samples) */
+    double strong_fraction;  /* sum of n_strong / n_samples */
+} adsb_signal_summary_t;
+
+#if defined(__GNUC__)
+#define ADSB_MUST_CHECK __attribute__((warn_unused_result))
+#else
+#define ADSB_MUST_CHECK
+#endif
+
+/* adsb_set_signal_stats: the mode of the passes submitted after the call (ADSB_ERR_BUSY while passes are pending).  It
+ * applies to every IQ entry point of the context -- adsb_demod_iq, adsb_demod_iq_device, submit / collect with 4 or 8
+ * passes in flight, the ring in both formats, and all the _u8 twins; adsb_to_mag and adsb_demodulate2400, the caller's
+ * magnitudes, are left alone, and adsb_shard_* / adsb_multi_* do not deliver records (out of scope: after adsb_shard_scan
+ * adsb_fetch_signal_stats has none).  A pass that takes
+ * the buffer-by-buffer overflow fallback, or that is redone through the three launches (adsb_host_rematches), still
+ * delivers its records, computed once.  The first enable reserves 272 B x max_chunks of mapped host memory and as
+ * much device memory (plus 4 B x max_chunks) per pass in flight; a context that never enables the mode keeps the
+ * footprint documented at adsb_create.  Known cost: a ring slot of one or two buffers, which its pass reads in place
+ * over the link, is read over the link a second time.
+ * adsb_get_signal_stats: 1 / 0, or ADSB_ERR_INVALID for a null context. */
+int adsb_set_signal_stats(adsb_ctx *ctx, int enabled);
+int adsb_get_signal_stats(const adsb_ctx *ctx);
+/* The records of the pass most recently collected (adsb_collect), or of the blocking call most recently returned: one
+ * per buffer, in buffer order.  Like adsb_fetch_messages: *n_out is the full count even when `cap` is smaller (then the
+ * first `cap` are written and the status is ADSB_ERR_CAPACITY); *n_out is 0, status ADSB_OK, when that pass ran with the
+ * mode off or held no samples. */
+ADSB_MUST_CHECK int adsb_fetch_signal_stats(adsb_ctx *ctx, adsb_signal_stats *out, size_t cap, size_t *n_out);
+/* Quarter-octave bins of about 1.5 dB: m itself for m < 8; otherwise, with e = floor(log2 m) in 3..15,
+ * 8 + 4 (e - 3) + ((m >> (e - 2)) & 3), at most 59.  Host only. */
+int adsb_signal_bin(uint16_t m);
+/* Sums n records into *out.  A logarithm of zero comes back as -inf (an all-zero capture, no samples at all), never
+ * NaN.  Host only.  ADSB_ERR_INVALID for a null `out`, or a null `s` with n > 0. */
+ADSB_MUST_CHECK int adsb_signal_summary(const adsb_signal_stats *s, size_t n, adsb_signal_summary_t *out);
+/* Diagnostic: how many k_signal_stats launches this context has made (a pass with the mode off makes none). */
+uint64_t adsb_selftest_signal_launches(const adsb_ctx *ctx);
+
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167
  * is one stream with one process-global filter, src/icao_filter.rs:8-9).  Shards run

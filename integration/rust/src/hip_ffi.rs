@@ -89,6 +89,32 @@ pub struct AdsbMultiStats {
     pub reserved: f32,
 }
 
+/// `adsb_signal_stats`: one 131072-sample buffer's signal record (opt-in, `adsb_set_signal_stats`).  272 bytes.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct AdsbSignalStats {
+    pub chunk: u64,
+    pub sum_power: u64,
+    pub n_samples: u32,
+    pub peak: u32,
+    pub n_strong: u32,
+    pub n_clipped: u32,
+    pub hist: [u32; 60],
+}
+
+/// `adsb_signal_summary_t`: what `adsb_signal_summary` makes of any number of records.  56 bytes.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct AdsbSignalSummary {
+    pub n_buffers: u64,
+    pub n_samples: u64,
+    pub mean_power_dbfs: f64,
+    pub peak_dbfs: f64,
+    pub median_dbfs: f64,
+    pub clipped_fraction: f64,
+    pub strong_fraction: f64,
+}
+
 #[repr(C)]
 pub struct AdsbCtx {
     _private: [u8; 0],
@@ -110,6 +136,10 @@ unsafe extern "C" {
     pub fn adsb_set_carry_over(ctx: *mut AdsbCtx, enabled: c_int) -> c_int; // opt-in, not the reference's semantics
     pub fn adsb_set_error_correction(ctx: *mut AdsbCtx, mode: c_int) -> c_int; // opt-in: ADSB_FIX_1BIT, ADSB_FIX_2BIT
     pub fn adsb_get_error_correction(ctx: *const AdsbCtx) -> c_int;
+    pub fn adsb_set_signal_stats(ctx: *mut AdsbCtx, enabled: c_int) -> c_int; // opt-in: one AdsbSignalStats per buffer
+    pub fn adsb_get_signal_stats(ctx: *const AdsbCtx) -> c_int;
+    pub fn adsb_signal_bin(m: u16) -> c_int;
+    pub fn adsb_selftest_signal_launches(ctx: *const AdsbCtx) -> u64;
     pub fn adsb_icao_flush(ctx: *mut AdsbCtx) -> c_int;
     pub fn adsb_to_mag(ctx: *mut AdsbCtx, iq_re_im: *const i16, n: usize, data_out: *mut u16, length_out: *mut usize) -> c_int;
     pub fn adsb_demodulate2400(ctx: *mut AdsbCtx, data: *const u16, length: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
@@ -183,4 +213,12 @@ unsafe extern "C" {
     pub fn adsb_strerror(status: c_int) -> *const c_char;
     pub fn adsb_last_error(ctx: *const AdsbCtx) -> *const c_char;
     pub fn adsb_version() -> *const c_char;
+}
+
+// The two calls that take the signal records by pointer (the header marks them ADSB_MUST_CHECK); compared with the
+// header by tests/test_signal_stats_cpu.py.
+#[link(name = "adsb_hip")]
+unsafe extern "C" {
+    pub fn adsb_fetch_signal_stats(ctx: *mut AdsbCtx, out: *mut AdsbSignalStats, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_signal_summary(s: *const AdsbSignalStats, n: usize, out: *mut AdsbSignalSummary) -> c_int;
 }
