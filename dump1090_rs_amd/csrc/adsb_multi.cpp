@@ -2,16 +2,16 @@
 //
 // The reference is one process, one loop, one process-global ICAO filter (dump1090_rs/src/main.rs:154-167,
 // src/icao_filter.rs:8-9).  The multi-GPU form keeps exactly that shape for its caller: one handle, one filter,
-// one ordered message list -- and inside, one context and one host thread per device:
+// one ordered message list -- and inside, one context and one host thread (DeviceWorker::run) per device:
 //
 //   submit    the capture is cut into contiguous buffer ranges, one per device; every device thread enqueues
 //             phase 1 of its shard (adsb_shard.cpp: scan + the records of the self-validating hits) and goes
 //             on polling -- nothing blocks, the shards of the next capture can be enqueued behind it;
 //   exchange  the device thread that sees the LAST phase 1 of a capture land forms the union of the shards'
 //             learned addresses in memory (minus what every device has been given since the last flush)
-//             and hands every device thread phase 2 (set those addresses, match, records) -- captures in order;
+//             and hands every device thread phase 2 (set those addresses, match, records) -- captures in order (dispatch_ready);
 //   collect   the caller's thread waits for the last phase 2 of the oldest capture and replays the shards'
-//             records, device by device = in global (buffer, j, try_phase) order, through the ONE filter.
+//             records, device by device = in global (buffer, j, try_phase) order, through the ONE filter (collect_capture, replay_capture).
 //
 // No torch, no process group, no collective: the exchange is a few hundred u32 between threads of one process.
 // Consecutive captures overlap (up to ADSB_MAX_IN_FLIGHT in flight: a slot of each context per capture), so the
@@ -43,11 +43,17 @@ using namespace adsb::host;
 namespace {
 
 constexpr int kMultiSteps = ADSB_MAX_IN_FLIGHT;   // captures in flight (a slot of every context each)
+constexpr int kMaxDevices = 64;                    // devices (shards) of one adsb_multi
 
 double now_s()
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+#ifdef ADSB_TUNING
+constexpr bool kTuning = true;    // the host-side timing below (ADSB_HOST_TIMES=1 prints it) is compiled into a tuning build only:
+#else
+constexpr bool kTuning = false;   // `if (kTuning)` is dead code in any other
+#endif
 
 struct Cmd {
     enum Kind { kPhase1, kPhase2, kFetch, kReset, kStop } kind;
@@ -263,7 +269,6 @@ struct adsb_multi {
     uint64_t parallel_scored = 0, scored_shards_used = 0, scored_shards_refused = 0;
     size_t parallel_min = kParallelReplayMin;
     int score_mode = 0;   // 0: dense shards are scored on their devices; 1: never; 2: scored, and the result refused (tests)
-    size_t held_before = 0;   // (collect_capture: values in the filter table when the capture's replay began)
     // a capture failed: see the head of this file
     bool poisoned = false;
     std::string poison_error;
@@ -274,9 +279,7 @@ struct adsb_multi {
     // adsb_multi_selftest_fail: capture number, shard, kind (0: none)
     std::atomic<uint64_t> fault_capture{~0ull};
     std::atomic<int> fault_shard{-1}, fault_kind{0};
-#ifdef ADSB_TUNING
-    double t_stage[5] = {};   // plan, scan, merge, score, finish (ADSB_HOST_TIMES=1: printed at destroy)
-#endif
+    double t_stage[5] = {};   // the parallel replay's plan, scan, merge, score, finish (tuning build, ADSB_HOST_TIMES=1: printed at destroy)
 };
 
 namespace {
@@ -352,187 +355,188 @@ void shard_failed(adsb_multi::Dev *d, StepDev &sd, int rc, const char *what = nu
     }
 }
 
-void device_thread(adsb_multi *m, adsb_multi::Dev *d) noexcept
+// a result for whoever waits on done_cv: stored under done_mu (a waiter between its look at the flag and its sleep cannot miss it), the wake-up after the unlock
+void answer(adsb_multi *m, std::atomic<int> &flag, int value = 1)
 {
-    (void)hipSetDevice(d->device);
-    pin_to_device_numa(d->device);
-    adsb_ctx *c = d->ctx;
-    StepFifo w1, w2;   // captures whose phase 1 / phase 2 is out on this device, oldest first
-    uint32_t seen = 0;
-#ifdef ADSB_TUNING
-    // where this thread's time goes, printed when it ends (ADSB_HOST_TIMES=1): issuing the phases, reading the learned
-    // addresses out of phase 1's records, taking phase 2's records (checksum), putting them in order
-    struct Spent {
-        double issue1 = 0, issue2 = 0, learned = 0, records = 0, sort = 0;
-        uint64_t captures = 0, n_rec = 0;
-        int index;
-        ~Spent()
-        {
-            if (tuning_env("ADSB_HOST_TIMES") && captures)
-                std::fprintf(stderr, "adsb_multi device thread %d: %llu captures, %.1f records each; us per capture: issue phase 1 %.1f, learned %.1f, "
-                             "issue phase 2 %.1f, records %.1f, order %.1f\n", index, (unsigned long long)captures, (double)n_rec / captures,
-                             issue1 / captures * 1e6, learned / captures * 1e6, issue2 / captures * 1e6, records / captures * 1e6, sort / captures * 1e6);
-        }
-    } spent;
-    spent.index = d->index;
-#define SPENT(field, expr) do { const double t_ = now_s(); expr; spent.field += now_s() - t_; } while (0)
-#else
-#define SPENT(field, expr) do { expr; } while (0)
-#endif
-    // phase 1 of a shard: its samples (copied to this capture's staging buffer first, in the host-pointer form) and its scan
-    auto issue1 = [&](uint64_t id) {
-        Step &s = m->step[id % kMultiSteps];
-        StepDev &sd = s.dev[d->index];
-        const int k = (int)(id % kMultiSteps);
+    std::unique_lock<std::mutex> lk(m->done_mu);
+    flag.store(value, std::memory_order_release);
+    lk.unlock();
+    m->done_cv.notify_all();
+}
+
+// where a device thread's time goes (tuning build, ADSB_HOST_TIMES=1: printed when it ends); learned: reading phase 1's learned addresses, order: sorting phase 2's records
+enum Bucket { kIssue1, kLearned, kIssue2, kRecords, kOrder, kBuckets };
+struct Spent {
+    double t[kBuckets] = {};
+    uint64_t captures = 0, n_rec = 0;
+    int index = 0;
+    template <class F> void timed(Bucket b, F &&f)
+    {
+        const double t0 = kTuning ? now_s() : 0;
+        f();
+        if (kTuning) t[b] += now_s() - t0;
+    }
+    ~Spent()
+    {
+        if (tuning_env("ADSB_HOST_TIMES") && captures)
+            std::fprintf(stderr, "adsb_multi device thread %d: %llu captures, %.1f records each; us per capture: issue phase 1 %.1f, learned %.1f, "
+                         "issue phase 2 %.1f, records %.1f, order %.1f\n", index, (unsigned long long)captures, (double)n_rec / captures,
+                         t[kIssue1] / captures * 1e6, t[kLearned] / captures * 1e6, t[kIssue2] / captures * 1e6, t[kRecords] / captures * 1e6, t[kOrder] / captures * 1e6);
+    }
+};
+
+// One device's host thread (device_thread below): it takes the commands of its ring, enqueues the two phases of its shards, sees them land -- the last to
+// land a capture's phase 1 runs the exchange, the last to land its phase 2 wakes the collector -- and answers the collector's requests.
+struct DeviceWorker {
+    adsb_multi *m;
+    adsb_multi::Dev *d;
+    adsb_ctx *c;         // d's context: this thread's alone while captures are in flight
+    StepFifo w1, w2;     // captures whose phase 1 / phase 2 is out on this device, oldest first
+    uint32_t seen = 0;   // commands taken so far (of Dev::q_count)
+    double last_check = 0, last_progress = now_s();
+    Spent spent;
+    DeviceWorker(adsb_multi *multi, adsb_multi::Dev *dev) : m(multi), d(dev), c(dev->ctx) { spent.index = dev->index; }
+    static int slot(uint64_t id) { return (int)(id % kMultiSteps); }       // capture `id`'s slot in every context
+    StepDev &mine(uint64_t id) const { return m->step[slot(id)].dev[d->index]; }   // ... and this device's share of it
+    // the status of a call into the context: anything but ADSB_OK fails the shard (with the context's last_error)
+    int check(StepDev &sd, int rc) { if (rc != ADSB_OK) shard_failed(d, sd, rc); return rc; }
+    template <class F> int call(StepDev &sd, Bucket b, F &&f)   // ... of a call whose time is counted
+    {
+        int rc = ADSB_OK;
+        spent.timed(b, [&] { rc = f(); });
+        return check(sd, rc);
+    }
+    // phase 1 of a shard: its samples (staged first, in the host-pointer form) and its scan
+    void issue1(uint64_t id)
+    {
+        StepDev &sd = mine(id);
+        const int k = slot(id);
         sd.t_p1_issue = now_s();
         try {
-            const int fault = fault_for(m, id, d->index);
             if (d->dead.load(std::memory_order_relaxed)) {
                 shard_failed(d, sd, ADSB_ERR_HIP, "the device stopped answering earlier (a shard phase timed out): destroy the adsb_multi");
-            } else if (fault == ADSB_FAULT_PHASE1) {
+            } else if (fault_for(m, id, d->index) == ADSB_FAULT_PHASE1) {
                 shard_failed(d, sd, ADSB_ERR_HIP, "injected: phase 1 failed (adsb_multi_selftest_fail)");
             } else {
-                c->flush_pending = s.flush_before;   // (set either way: a shard that failed before it began must not leave its flush to the next capture)
+                c->flush_pending = m->step[k].flush_before;   // (set either way: a shard that failed before it began must not leave its flush to the next capture)
                 const void *src = sd.src;
                 if (sd.host_src && sd.n_samples) {
-                    // the host-pointer form: the shard's samples into this capture's staging buffer, on the stream its scan
-                    // will run on (shard_begin's own rule), in front of it.  The buffer holds the largest shard the
-                    // context takes and is made once (hipFree would wait for everything in flight on the device)
-                    const size_t bytes = sd.n_samples * 4;
+                    // the host-pointer form: the shard's samples into this capture's staging buffer, on the stream its scan will run on (shard_begin's own
+                    // rule), in front of it.  The buffer holds the largest shard the context takes and is made once (hipFree would wait for everything in flight)
                     if (!d->d_stage[k] && hipMalloc(&d->d_stage[k], m->max_chunks * (size_t)kChunkSamples * 4) != hipSuccess) {
                         (void)hipGetLastError();
                         d->d_stage[k] = nullptr;
                         shard_failed(d, sd, ADSB_ERR_NOMEM, "hipMalloc of a staging buffer for host samples failed");
-                    } else if (hipMemcpyAsync(d->d_stage[k], sd.host_src, bytes, hipMemcpyHostToDevice, c->scan_stream[c->shard_jobs % 2]) != hipSuccess) {
+                    } else if (hipMemcpyAsync(d->d_stage[k], sd.host_src, sd.n_samples * 4, hipMemcpyHostToDevice, c->scan_stream[c->shard_jobs % 2]) != hipSuccess) {
                         (void)hipGetLastError();
                         shard_failed(d, sd, ADSB_ERR_HIP, "hipMemcpyAsync of a shard's host samples failed");
-                    } else {
-                        src = d->d_stage[k];
                     }
+                    src = d->d_stage[k];   // (not looked at where one of the two failed)
                 }
-                if (sd.rc == ADSB_OK) {
-                    int rc = ADSB_OK;
-                    SPENT(issue1, rc = shard_begin(c, k, src, sd.n_samples, true));
-                    if (rc != ADSB_OK) shard_failed(d, sd, rc);
-                }
+                if (sd.rc == ADSB_OK) call(sd, kIssue1, [&] { return shard_begin(c, k, src, sd.n_samples, true); });
             }
         } catch (...) {
             shard_failed(d, sd, ADSB_ERR_NOMEM, "out of memory while a shard's first phase was enqueued");
         }
         w1.push(id);
-    };
-    auto issue2 = [&](uint64_t id) {
-        Step &s = m->step[id % kMultiSteps];
-        StepDev &sd = s.dev[d->index];
-        const int k = (int)(id % kMultiSteps);
+    }
+    // phase 2: the addresses the exchange found new to the devices, and what the shards before this one add
+    void issue2(uint64_t id)
+    {
+        Step &s = m->step[slot(id)];
+        StepDev &sd = mine(id);
         sd.t_p2_issue = now_s();
         try {
             if (s.exchange_rc != ADSB_OK) shard_failed(d, sd, s.exchange_rc, "out of memory in the address exchange");
             else if (sd.rc == ADSB_OK && fault_for(m, id, d->index) == ADSB_FAULT_PHASE2)
                 shard_failed(d, sd, ADSB_ERR_HIP, "injected: phase 2 failed (adsb_multi_selftest_fail)");
-            if (sd.rc == ADSB_OK) {
-                int rc = ADSB_OK;
-                SPENT(issue2, rc = shard_match(c, k, s.fresh.data(), s.fresh.size(), s.earlier[(size_t)d->index].data(), s.earlier[(size_t)d->index].size()));
-                if (rc != ADSB_OK) shard_failed(d, sd, rc);
-            }
+            const std::vector<uint32_t> &earlier = s.earlier[(size_t)d->index];
+            if (sd.rc == ADSB_OK) call(sd, kIssue2, [&] { return shard_match(c, slot(id), s.fresh.data(), s.fresh.size(), earlier.data(), earlier.size()); });
         } catch (...) {
             shard_failed(d, sd, ADSB_ERR_NOMEM, "out of memory while a shard's second phase was enqueued");
         }
         w2.push(id);
-    };
-    // has the phase at the front of `w` landed (true: also when it failed)?  A phase that has been out for a while is
-    // looked into -- its streams' status -- and given up after the handle's timeout.
-    double last_check = 0;
-    auto landed = [&](uint64_t id, double issued_at) -> bool {
-        Step &s = m->step[id % kMultiSteps];
-        StepDev &sd = s.dev[d->index];
-        const int k = (int)(id % kMultiSteps);
-        if (sd.rc != ADSB_OK) return true;
-        if (d->dead.load(std::memory_order_relaxed)) {   // (given up on while this phase was out)
+    }
+    // Has the phase of capture `id` that is out on this device landed (true: also when it failed)?  A phase that has been out for a while is looked
+    // into -- its streams' status -- and given up after the handle's timeout.
+    bool landed(uint64_t id, double issued_at)
+    {
+        StepDev &sd = mine(id);
+        if (sd.rc == ADSB_OK && d->dead.load(std::memory_order_relaxed))   // (given up on while this phase was out)
             shard_failed(d, sd, ADSB_ERR_HIP, "the device stopped answering (an earlier shard phase timed out)");
-            return true;
-        }
+        if (sd.rc != ADSB_OK) return true;
         const bool hang = fault_for(m, id, d->index) == ADSB_FAULT_HANG;   // (the phase lands, the thread pretends it never does)
-        if (!hang && shard_phase_landed(c, k)) return true;
+        if (!hang && shard_phase_landed(c, slot(id))) return true;
         const double t = now_s();
         if (t - issued_at < kCheckAfterS || t - last_check < kCheckAfterS) return false;
         last_check = t;
-        const int st = hang ? 0 : shard_phase_check(c, k);
-        if (st > 0) return true;
-        if (st < 0) {
-            shard_failed(d, sd, st);
-            return true;
-        }
+        const int st = hang ? 0 : shard_phase_check(c, slot(id));
+        if (st < 0) check(sd, st);   // (a stream error)
+        if (st != 0) return true;
         if ((t - issued_at) * 1e3 > (double)m->timeout_ms.load(std::memory_order_relaxed)) {
             d->dead.store(true, std::memory_order_relaxed);
             shard_failed(d, sd, ADSB_ERR_HIP, "a shard phase did not finish within the adsb_multi's timeout: the device is given up");
-            return true;
         }
-        return false;
-    };
-    auto land1 = [&]() {
+        return sd.rc != ADSB_OK;
+    }
+    // the oldest phase 1 has landed: its learned addresses; the last device of the capture to get here runs the exchange
+    void land1()
+    {
         const uint64_t id = w1.front();
-        const int k = (int)(id % kMultiSteps);
-        Step &s = m->step[k];
-        StepDev &sd = s.dev[d->index];
+        StepDev &sd = mine(id);
         try {
-            if (sd.rc == ADSB_OK) {
-                int rc = ADSB_OK;
-                SPENT(learned, rc = shard_learned(c, k, sd.learned));
-                if (rc != ADSB_OK) shard_failed(d, sd, rc);
-            }
+            if (sd.rc == ADSB_OK) call(sd, kLearned, [&] { return shard_learned(c, slot(id), sd.learned); });
         } catch (...) {
             shard_failed(d, sd, ADSB_ERR_NOMEM, "out of memory while a shard's learned addresses were read");
         }
         if (sd.rc != ADSB_OK) sd.learned.clear();
         sd.t_p1_done = now_s();
         w1.pop();
-        if (s.p1_left.fetch_sub(1, std::memory_order_acq_rel) == 1) dispatch_ready(m);
-    };
-    auto land2 = [&]() {
+        if (m->step[slot(id)].p1_left.fetch_sub(1, std::memory_order_acq_rel) == 1) dispatch_ready(m);
+    }
+    // the oldest phase 2 has landed: the shard's records, or the result of a shard the device scored itself; the last device of the capture to get here wakes the collector
+    void land2()
+    {
         const uint64_t id = w2.front();
-        const int k = (int)(id % kMultiSteps);
-        Step &s = m->step[k];
-        StepDev &sd = s.dev[d->index];
+        const int k = slot(id);
+        Step &s = m->step[slot(id)];
+        StepDev &sd = mine(id);
         try {
-            if (sd.rc == ADSB_OK) {
-                int rc = ADSB_OK;
-                SPENT(records, rc = shard_records(c, k, &sd.rec, &sd.n_rec));
-                if (rc == ADSB_OK && fault_for(m, id, d->index) == ADSB_FAULT_RECORDS) {
-                    rc = ADSB_ERR_HIP;
-                    c->last_error = "injected: the shard's records did not add up (adsb_multi_selftest_fail)";
-                }
-                if (rc != ADSB_OK) shard_failed(d, sd, rc);
-            }
+            if (sd.rc == ADSB_OK)
+                call(sd, kRecords, [&] {
+                    int rc = shard_records(c, k, &sd.rec, &sd.n_rec);
+                    if (rc == ADSB_OK && fault_for(m, id, d->index) == ADSB_FAULT_RECORDS) {
+                        rc = ADSB_ERR_HIP;
+                        c->last_error = "injected: the shard's records did not add up (adsb_multi_selftest_fail)";
+                    }
+                    return rc;
+                });
             if (sd.rc == ADSB_OK && c->shard[k].result_scored) {
                 sd.n_hits = c->stats.n_records;
                 if (shard_scored_result(c, k, &sd.msgs, &sd.n_msgs, &sd.adds, &sd.n_adds)) {
                     sd.scored = true;
                     for (size_t i = 0; i < sd.n_msgs; i++) sd.msgs[i].chunk += sd.chunk_base;
                 } else {
-                    int rc = ADSB_OK;
-                    SPENT(records, rc = shard_fetch_records(c, k, &sd.rec, &sd.n_rec));   // (a result that did not add up)
-                    if (rc != ADSB_OK) shard_failed(d, sd, rc);
+                    call(sd, kRecords, [&] { return shard_fetch_records(c, k, &sd.rec, &sd.n_rec); });   // (a result that did not add up)
                 }
             }
-            // (in replay order before they are handed over: the shards' sorts then run side by side, on the device
-            // threads, instead of one after the other on the caller's)
-            if (sd.rc == ADSB_OK && sd.n_rec > 1) SPENT(sort, if (sort_records(sd.rec, sd.n_rec, sd.sorted)) { sd.rec = sd.sorted.data(); m->shards_sorted_on_host.fetch_add(1, std::memory_order_relaxed); });
+            // (in replay order before they are handed over: the shards' sorts then run side by side, on the device threads, not one after the other on the caller's)
+            if (sd.rc == ADSB_OK && sd.n_rec > 1)
+                spent.timed(kOrder, [&] {
+                    if (!sort_records(sd.rec, sd.n_rec, sd.sorted)) return;
+                    sd.rec = sd.sorted.data();
+                    m->shards_sorted_on_host.fetch_add(1, std::memory_order_relaxed);
+                });
             if (sd.rc == ADSB_OK && !sd.scored && sd.n_rec <= kDeviceThreadScanMax) {
-                SPENT(sort, first_adders(c->crc, sd.rec, sd.n_rec, sd.adders));
+                spent.timed(kOrder, [&] { first_adders(c->crc, sd.rec, sd.n_rec, sd.adders); });
                 sd.has_adders = true;
             }
         } catch (...) {
             shard_failed(d, sd, ADSB_ERR_NOMEM, "out of memory while a shard's records were taken");
         }
-#ifdef ADSB_TUNING
-        spent.captures++;
-        spent.n_rec += sd.n_rec;
-#endif
+        if (kTuning) spent.captures++, spent.n_rec += sd.n_rec;
         if (sd.rc != ADSB_OK) {
-            sd.rec = nullptr;
-            sd.n_rec = 0;
-            sd.scored = false;
+            sd.rec = nullptr, sd.n_rec = 0, sd.scored = false;
             c->shard[k].active = c->shard[k].waiting = false;   // the slot is free again whatever happened (shard_reset puts the rest right)
         }
         sd.st = c->stats;
@@ -540,100 +544,99 @@ void device_thread(adsb_multi *m, adsb_multi::Dev *d) noexcept
         w2.pop();
         if (s.p2_left.fetch_sub(1, std::memory_order_acq_rel) == 1) {
             s.t_done = now_s();
-            {
-                std::lock_guard<std::mutex> lk(m->done_mu);
-                s.state.store(kDone, std::memory_order_release);
-            }
-            m->done_cv.notify_all();
+            answer(m, s.state, kDone);
         }
-    };
-    double last_progress = now_s();
-    for (;;) {
-        bool progressed = false;
-        if (d->q_count.load(std::memory_order_acquire) != seen) {
-            Cmd todo[CmdRing::kCap];
-            int n_todo = 0;
-            {
-                std::lock_guard<std::mutex> lk(d->mu);
-                while (!d->q.empty()) todo[n_todo++] = d->q.pop();
-                seen = d->q_count.load(std::memory_order_relaxed);
-            }
-            for (int i = 0; i < n_todo; i++) {
-                const Cmd &cmd = todo[i];
-                if (cmd.kind == Cmd::kStop) return;
-                if (cmd.kind == Cmd::kPhase1) issue1(cmd.step);
-                else if (cmd.kind == Cmd::kPhase2) issue2(cmd.step);
-                else if (cmd.kind == Cmd::kFetch) {
-                    // a scored shard whose result the collector cannot use (a filter table about to fill up): its records
-                    // out of device memory, by this thread -- the context is this thread's while captures are in flight
-                    StepDev &sd = m->step[cmd.step % kMultiSteps].dev[d->index];
-                    try {
-                        sd.fetch_rc = d->dead.load(std::memory_order_relaxed) ? (int)ADSB_ERR_HIP
-                                                                             : shard_fetch_records(c, (int)(cmd.step % kMultiSteps), &sd.rec, &sd.n_rec);
-                        if (sd.fetch_rc != ADSB_OK) shard_failed(d, sd, sd.fetch_rc);
-                    } catch (...) {
-                        sd.fetch_rc = ADSB_ERR_NOMEM;
-                    }
-                    {
-                        std::lock_guard<std::mutex> lk(m->done_mu);
-                        sd.fetched.store(1, std::memory_order_release);
-                    }
-                    m->done_cv.notify_all();
-                } else if (cmd.kind == Cmd::kReset) {
-                    try {
-                        d->reset_rc = d->dead.load(std::memory_order_relaxed) ? (int)ADSB_ERR_HIP : shard_reset(c);
-                    } catch (...) {
-                        d->reset_rc = ADSB_ERR_NOMEM;
-                    }
-                    {
-                        std::lock_guard<std::mutex> lk(m->done_mu);
-                        d->reset_done.store(1, std::memory_order_release);
-                    }
-                    m->done_cv.notify_all();
-                }
-            }
-            progressed = true;
+    }
+    // Cmd::kFetch: a scored shard whose result the collector cannot use (a filter table about to fill up) -- its records out of device memory, by this thread
+    void fetch(uint64_t id)
+    {
+        StepDev &sd = mine(id);
+        try {
+            sd.fetch_rc = check(sd, d->dead.load(std::memory_order_relaxed) ? (int)ADSB_ERR_HIP : shard_fetch_records(c, slot(id), &sd.rec, &sd.n_rec));
+        } catch (...) {
+            sd.fetch_rc = ADSB_ERR_NOMEM;
         }
-        if (!w1.empty() && landed(w1.front(), m->step[w1.front() % kMultiSteps].dev[d->index].t_p1_issue)) {
-            land1();
-            progressed = true;
+        answer(m, sd.fetched);
+    }
+    // Cmd::kReset: the context back to what adsb_create left (the restart of a poisoned handle, nothing in flight)
+    void reset()
+    {
+        try {
+            d->reset_rc = d->dead.load(std::memory_order_relaxed) ? (int)ADSB_ERR_HIP : shard_reset(c);
+        } catch (...) {
+            d->reset_rc = ADSB_ERR_NOMEM;
         }
-        if (!w2.empty() && landed(w2.front(), m->step[w2.front() % kMultiSteps].dev[d->index].t_p2_issue)) {
-            land2();
-            progressed = true;
+        answer(m, d->reset_done);
+    }
+    // every command in the ring, in order; false: told to stop
+    bool drain_commands()
+    {
+        Cmd todo[CmdRing::kCap];
+        int n_todo = 0;
+        {
+            std::lock_guard<std::mutex> lk(d->mu);
+            while (!d->q.empty()) todo[n_todo++] = d->q.pop();
+            seen = d->q_count.load(std::memory_order_relaxed);
         }
-        if (progressed) {
-            last_progress = now_s();
-            continue;
+        for (int i = 0; i < n_todo; i++) {
+            const Cmd &cmd = todo[i];
+            if (cmd.kind == Cmd::kStop) return false;
+            if (cmd.kind == Cmd::kPhase1) issue1(cmd.step);
+            else if (cmd.kind == Cmd::kPhase2) issue2(cmd.step);
+            else if (cmd.kind == Cmd::kFetch) fetch(cmd.step);
+            else if (cmd.kind == Cmd::kReset) reset();
         }
-        const double idle = now_s() - last_progress;
+        return true;
+    }
+    // nothing to do this time round: how the thread waits (adsb_multi_set_wait)
+    void idle()
+    {
+        const double since = now_s() - last_progress;
         const bool block = m->block.load(std::memory_order_relaxed);
+        const auto new_command = [&] { return d->q_count.load(std::memory_order_relaxed) != seen; };
         if (w1.empty() && w2.empty()) {
             // nothing out on the device: stay hot for a moment (the next capture of a pipelined caller is
             // microseconds away; not in the blocking mode), then sleep until a command arrives
-            if (!block && idle < 200e-6) {
-                __builtin_ia32_pause();
-                continue;
-            }
+            if (!block && since < 200e-6) return __builtin_ia32_pause();
             std::unique_lock<std::mutex> lk(d->mu);
             d->sleeping = true;
-            d->cv.wait(lk, [&] { return d->q_count.load(std::memory_order_relaxed) != seen; });
+            d->cv.wait(lk, new_command);
             d->sleeping = false;
             last_progress = now_s();
         } else if (block) {
             // ADSB_WAIT_BLOCK: asleep between looks at the device -- a timed wait on the command queue, so a command
             // still wakes the thread at once.  25 us while a phase is young (a shard's scan is ~100 us), longer as it ages.
-            const auto nap = std::chrono::microseconds(idle < 1e-3 ? 25 : (idle < 5e-3 ? 100 : 1000));
+            const auto nap = std::chrono::microseconds(since < 1e-3 ? 25 : (since < 5e-3 ? 100 : 1000));
             std::unique_lock<std::mutex> lk(d->mu);
             d->sleeping = true;
-            timed_wait(d->cv, lk, nap, [&] { return d->q_count.load(std::memory_order_relaxed) != seen; });
+            timed_wait(d->cv, lk, nap, new_command);
             d->sleeping = false;
-        } else if (idle < 5e-3) {
+        } else if (since < 5e-3) {
             __builtin_ia32_pause();
         } else {
             std::this_thread::sleep_for(std::chrono::microseconds(50));   // a long kernel (or a stuck one): stop burning a core
         }
     }
+    void run()
+    {
+        for (;;) {
+            const bool commands = d->q_count.load(std::memory_order_acquire) != seen;
+            if (commands && !drain_commands()) return;
+            const bool p1 = !w1.empty() && landed(w1.front(), mine(w1.front()).t_p1_issue);
+            if (p1) land1();
+            const bool p2 = !w2.empty() && landed(w2.front(), mine(w2.front()).t_p2_issue);
+            if (p2) land2();
+            if (commands || p1 || p2) last_progress = now_s();
+            else idle();
+        }
+    }
+};
+
+void device_thread(adsb_multi *m, adsb_multi::Dev *d) noexcept
+{
+    (void)hipSetDevice(d->device);
+    pin_to_device_numa(d->device);
+    DeviceWorker(m, d).run();
 }
 
 int refuse_poisoned(adsb_multi *m)
@@ -696,235 +699,238 @@ bool wait_done(adsb_multi *m, Pred ready)
     return timed_wait(m->done_cv, lk, limit, ready);
 }
 
-// the replay of a capture whose shards all arrived (rc == ADSB_OK); may throw (out of memory): the caller poisons the handle then
-void replay_capture(adsb_multi *m, Step &s, adsb_multi_stats &st, bool any_scored, std::vector<adsb_msg> &out, adsb_msg *direct,
-                    size_t direct_cap, size_t *direct_n, bool &direct_done, int &rc)
+// Where a capture's messages go: `out`, or -- a replay that has them all at once, and they fit -- straight into the caller's array (`direct`, of `cap`; `n` of them)
+struct Sink {
+    std::vector<adsb_msg> &out;
+    adsb_msg *direct = nullptr;
+    size_t cap = 0, n = 0;
+    bool direct_done = false;
+    bool takes_direct(size_t n_msgs) const { return direct && out.empty() && n_msgs <= cap; }
+};
+
+// m->last_error = "device N<text>": N is the HIP device of the handle's k-th device
+void device_error(adsb_multi *m, int k, const std::string &text) { m->last_error = "device " + std::to_string(m->dev[(size_t)k]->device) + text; }
+
+// a scored shard as it is: the values its replay handed to icao_filter_add, in order (its messages are the caller's to copy)
+void take_scored(adsb_multi *m, const StepDev &sd)
 {
-    // the shards are contiguous ascending buffer ranges, each in replay order (its device thread saw to that):
-    // device by device IS global (buffer, j, try_phase) order
-    bool done = false;
-    if (any_scored) {
-        // Shards the devices scored themselves (a dense stream's): their messages and additions are taken as they are,
-        // shard by shard in order; a shard that was not scored (sparse, overflowed, empty) is replayed here in its
-        // place.  A scored shard's result stands on the filter being a SET -- k_score asks "was it there, or added
-        // before me" -- which ends where the 4096-slot table could fill up (add() gives up, src/icao_filter.rs:46-62):
-        // then its records are fetched from its device and replayed here like anyone's.
-        size_t held = 0;
-        for (uint32_t v : m->filter.table()) held += v != 0;
-        m->held_before = held;
-        const uint64_t before = m->filter.inserts();
-        // how many slots a shard's additions can take: the list has one entry per add() CALL (a DF18 whose plain address is
-        // unknown re-adds address | NT on every frame and phase), the table one per distinct value -- counted only when the
-        // cheap bound (every call a new value) says the table might fill up
-        std::vector<uint32_t> scratch;
-        auto fits = [&](size_t now_held, const StepDev &sd) {
-            if (now_held + sd.n_adds + 64 < IcaoFilter::kSize) return true;
-            scratch.assign(sd.adds, sd.adds + sd.n_adds);
-            std::sort(scratch.begin(), scratch.end());
-            const size_t distinct = (size_t)(std::unique(scratch.begin(), scratch.end()) - scratch.begin());
-            return now_held + distinct + 64 < IcaoFilter::kSize;
-        };
-        bool all_direct = direct && direct_n && out.empty() && m->score_mode != 2;
-        size_t total = 0;
-        for (int k = 0; k < m->n && all_direct; k++) {
-            const StepDev &sd = s.dev[k];
-            all_direct = sd.scored ? fits(held, sd) : sd.n_rec == 0;
-            total += sd.n_msgs;
-            held += sd.n_adds;   // (the cheap bound again for the shards behind: a capture this close to a full table is rare)
-        }
-        all_direct = all_direct && total <= direct_cap;
-        if (all_direct) {   // every shard scored: straight into the caller's array
-            size_t at = 0;
-            for (int k = 0; k < m->n; k++) {
-                const StepDev &sd = s.dev[k];
-                if (sd.n_msgs) std::memcpy(direct + at, sd.msgs, sd.n_msgs * sizeof(adsb_msg));
-                at += sd.n_msgs;
-                for (size_t i = 0; i < sd.n_adds; i++) m->filter.add(sd.adds[i], IcaoFilter::hash(sd.adds[i] & 0xFFFFFFu));
-            }
-            *direct_n = total;
-            direct_done = true;
-            for (int k = 0; k < m->n; k++) m->scored_shards_used += s.dev[k].scored ? 1u : 0u;
-        } else {
-            for (int k = 0; k < m->n && rc == ADSB_OK; k++) {
-                StepDev &sd = s.dev[k];
-                const size_t now_held = (size_t)(m->filter.inserts() - before) + m->held_before;
-                if (sd.scored && m->score_mode != 2 && fits(now_held, sd)) {
-                    out.insert(out.end(), sd.msgs, sd.msgs + sd.n_msgs);
-                    for (size_t i = 0; i < sd.n_adds; i++) m->filter.add(sd.adds[i], IcaoFilter::hash(sd.adds[i] & 0xFFFFFFu));
-                    m->scored_shards_used++;
-                } else if (sd.scored) {
-                    // (the chunk offsets already put into the messages do not matter: they are dropped.)  The records come
-                    // through the shard's own device thread: its context is that thread's while captures are in flight.
-                    push_cmd(*m->dev[(size_t)k], Cmd{Cmd::kFetch, m->collected});
-                    if (!wait_done(m, [&] { return sd.fetched.load(std::memory_order_acquire) != 0; })) {
-                        rc = ADSB_ERR_HIP;
-                        sd.error = "the device thread did not answer a request for a shard's records";
-                    } else {
-                        rc = sd.fetch_rc;
-                    }
-                    if (rc != ADSB_OK) {
-                        m->last_error = "device " + std::to_string(m->dev[(size_t)k]->device) + ": " + sd.error;
-                        break;
-                    }
-                    if (sd.n_rec) replay(m->filter, m->crc, sd.rec, sd.n_rec, sd.chunk_base, out);
-                    m->scored_shards_refused++;
-                } else if (sd.n_rec) {
-                    replay_sorted(m->filter, m->crc, sd.rec, sd.n_rec, sd.chunk_base, out);
-                }
-            }
-        }
-        done = true;
-    }
-    if (!done && st.n_records >= m->parallel_min) {
-        // a busy sky: tens of thousands of records -- scored by several threads at once, each record against the
-        // filter as it was plus the positions at which the capture's new addresses enter it (adsb_replay_host.h)
-        if (!m->pool) {
-            const unsigned hw = std::thread::hardware_concurrency();
-            std::vector<int> devs;
-            for (auto &d : m->dev) devs.push_back(d->device);
-            // six threads beside the caller, two per device from four devices on (the records to score grow with the
-            // devices that found them), never more than a quarter of the host's cores
-            int workers = (int)std::min<unsigned>(std::max(6u, std::min(16u, 2u * (unsigned)m->dev.size())), std::max(1u, hw / 4));
-            // ... nor more than the CPUs this process may use leave beside the device threads and the caller (a
-            // container's quota: threads beyond it only get the whole process throttled); device threads that block
-            // between looks take next to nothing
-            const bool block = m->block.load(std::memory_order_relaxed);
-            const int room = usable_cpus() - (block ? 0 : (int)m->dev.size()) - 2;
-            workers = std::max(1, std::min(workers, room));
-            if (const char *e = tuning_env("ADSB_POOL_WORKERS")) workers = std::max(1, std::atoi(e));   // (tuning build only)
-            // (worker k on the host cores of devices[k % n]'s NUMA node: the records it reads sit in that node's memory;
-            // a blocking handle's workers do not stay hot between jobs)
-            m->pool.reset(new ReplayPool(workers, [devs](int k) { pin_to_device_numa(devs[(size_t)k % devs.size()]); }, block ? 0 : 1500));
-        }
-        std::vector<RecordRun> runs;
-        std::vector<const ParallelReplay::Adders *> adders;
-        for (int k = 0; k < m->n; k++) {
-            const StepDev &sd = s.dev[k];
-            if (!sd.n_rec) continue;
-            runs.push_back({sd.rec, sd.n_rec, sd.chunk_base});
-            adders.push_back(sd.has_adders ? &sd.adders : nullptr);
-        }
-        ParallelReplay &pr = m->parallel;
-#ifdef ADSB_TUNING
-        double t[6] = {now_s()};
-#define STAGE(k) t[k] = now_s()
-#else
-#define STAGE(k) (void)0
-#endif
-        if (pr.plan(m->filter, m->crc, runs, 4 * m->pool->threads(), true, &adders)) {
-            STAGE(1);
-            if (pr.scan_needed()) m->pool->run(pr, &ParallelReplay::scan_part);
-            STAGE(2);
-            if (pr.merge()) {
-                STAGE(3);
-                m->pool->run(pr, &ParallelReplay::score_part);
-                STAGE(4);
-                const size_t n_msgs = pr.message_count();
-                if (direct && direct_n && out.empty() && n_msgs <= direct_cap) {
-                    pr.copy_to(direct);
-                    m->pool->run(pr, &ParallelReplay::copy_part);
-                    pr.apply_adds(m->filter);
-                    *direct_n = n_msgs;
-                    direct_done = true;
-                } else {
-                    pr.finish(m->filter, out);
-                }
-                STAGE(5);
-                m->parallel_scored++;
-                done = true;
-#ifdef ADSB_TUNING
-                for (int k = 0; k < 5; k++) m->t_stage[k] += t[k + 1] - t[k];
-#endif
-            }
-        }
-#undef STAGE
-    }
-    if (!done)
-        for (int k = 0; k < m->n; k++) {
-            const StepDev &sd = s.dev[k];
-            if (sd.n_rec) replay_sorted(m->filter, m->crc, sd.rec, sd.n_rec, sd.chunk_base, out);
-        }
+    for (size_t i = 0; i < sd.n_adds; i++) m->filter.add(sd.adds[i], IcaoFilter::hash(sd.adds[i] & 0xFFFFFFu));
+    m->scored_shards_used += sd.scored ? 1u : 0u;
 }
 
-// (direct: the caller's own array -- a capture scored by several threads goes straight into it when it fits, *direct_n then
-// says how many messages it got and `out` stays empty)
-int collect_capture(adsb_multi *m, std::vector<adsb_msg> &out, adsb_msg *direct = nullptr, size_t direct_cap = 0, size_t *direct_n = nullptr) noexcept
+// Can a scored shard's additions go into a filter table that holds `now_held` values?  Its list has one entry per add() CALL (a DF18 whose plain address is
+// unknown re-adds address | NT on every frame and phase), the table one per distinct value -- counted only when the cheap bound says the table might fill up.
+bool fits(size_t now_held, const StepDev &sd, std::vector<uint32_t> &scratch)
+{
+    if (now_held + sd.n_adds + 64 < IcaoFilter::kSize) return true;
+    scratch.assign(sd.adds, sd.adds + sd.n_adds);
+    std::sort(scratch.begin(), scratch.end());
+    const size_t distinct = (size_t)(std::unique(scratch.begin(), scratch.end()) - scratch.begin());
+    return now_held + distinct + 64 < IcaoFilter::kSize;
+}
+
+// The records of a scored shard that cannot be taken as it is (the chunk offsets already put into its messages do not matter: they are dropped),
+// through the shard's own device thread: its context is that thread's while captures are in flight.
+int fetch_refused(adsb_multi *m, int k, StepDev &sd)
+{
+    push_cmd(*m->dev[(size_t)k], Cmd{Cmd::kFetch, m->collected});
+    int rc = ADSB_ERR_HIP;
+    if (wait_done(m, [&] { return sd.fetched.load(std::memory_order_acquire) != 0; })) rc = sd.fetch_rc;
+    else sd.error = "the device thread did not answer a request for a shard's records";
+    if (rc != ADSB_OK) device_error(m, k, ": " + sd.error);
+    return rc;
+}
+
+// Shards the devices scored themselves (a dense stream's): their messages and additions are taken as they are, shard by shard in order; a shard
+// that was not scored (sparse, overflowed, empty) is replayed here in its place.  A scored shard's result stands on the filter being a SET -- k_score
+// asks "was it there, or added before me" -- which ends where the 4096-slot table could fill up (add() gives up, src/icao_filter.rs:46-62): then
+// its records are fetched from its device and replayed here like anyone's.
+int replay_scored(adsb_multi *m, Step &s, Sink &to)
+{
+    size_t held_before = 0;   // values in the filter table now
+    for (uint32_t v : m->filter.table()) held_before += v != 0;
+    const uint64_t before = m->filter.inserts();
+    std::vector<uint32_t> scratch;
+    // every shard scored (or empty) and usable, and the caller's array large enough: straight into it
+    bool all_direct = to.direct && to.out.empty() && m->score_mode != 2;
+    size_t total = 0, held = held_before;
+    for (int k = 0; k < m->n && all_direct; k++) {
+        const StepDev &sd = s.dev[k];
+        all_direct = sd.scored ? fits(held, sd, scratch) : sd.n_rec == 0;
+        total += sd.n_msgs;
+        held += sd.n_adds;   // (the cheap bound again for the shards behind: a capture this close to a full table is rare)
+    }
+    if (all_direct && total <= to.cap) {
+        for (int k = 0; k < m->n; k++) {
+            const StepDev &sd = s.dev[k];
+            if (sd.n_msgs) std::memcpy(to.direct + to.n, sd.msgs, sd.n_msgs * sizeof(adsb_msg));
+            to.n += sd.n_msgs;
+            take_scored(m, sd);
+        }
+        to.direct_done = true;
+        return ADSB_OK;
+    }
+    for (int k = 0; k < m->n; k++) {
+        StepDev &sd = s.dev[k];
+        const size_t now_held = (size_t)(m->filter.inserts() - before) + held_before;
+        if (sd.scored && m->score_mode != 2 && fits(now_held, sd, scratch)) {
+            to.out.insert(to.out.end(), sd.msgs, sd.msgs + sd.n_msgs);
+            take_scored(m, sd);
+        } else if (sd.scored) {
+            if (int rc = fetch_refused(m, k, sd)) return rc;
+            if (sd.n_rec) replay(m->filter, m->crc, sd.rec, sd.n_rec, sd.chunk_base, to.out);
+            m->scored_shards_refused++;
+        } else if (sd.n_rec) {
+            replay_sorted(m->filter, m->crc, sd.rec, sd.n_rec, sd.chunk_base, to.out);
+        }
+    }
+    return ADSB_OK;
+}
+
+// The threads a busy capture's replay is fanned out to (made with the first capture that is large enough to want them).
+void make_pool(adsb_multi *m)
+{
+    const unsigned hw = std::thread::hardware_concurrency();
+    std::vector<int> devs;
+    for (auto &d : m->dev) devs.push_back(d->device);
+    // six threads beside the caller, two per device from four devices on (the records to score grow with the devices), never more than a quarter of the cores
+    int workers = (int)std::min<unsigned>(std::max(6u, std::min(16u, 2u * (unsigned)m->dev.size())), std::max(1u, hw / 4));
+    // ... nor more than the CPUs this process may use leave beside the device threads and the caller (a container's quota: threads beyond it only get the
+    // whole process throttled); device threads that block between looks take next to nothing
+    const bool block = m->block.load(std::memory_order_relaxed);
+    const int room = usable_cpus() - (block ? 0 : (int)m->dev.size()) - 2;
+    workers = std::max(1, std::min(workers, room));
+    if (const char *e = tuning_env("ADSB_POOL_WORKERS")) workers = std::max(1, std::atoi(e));   // (tuning build only)
+    // (worker k on the host cores of devices[k % n]'s NUMA node: its records sit in that node's memory; a blocking handle's workers do not stay hot between jobs)
+    m->pool.reset(new ReplayPool(workers, [devs](int k) { pin_to_device_numa(devs[(size_t)k % devs.size()]); }, block ? 0 : 1500));
+}
+
+// A busy sky: tens of thousands of records -- scored by several threads at once, each record against the filter as it was plus the positions at which
+// the capture's new addresses enter it (adsb_replay_host.h).  false: the plan or the merge declined, nothing has been replayed.
+bool replay_parallel(adsb_multi *m, Step &s, Sink &to)
+{
+    if (!m->pool) make_pool(m);
+    std::vector<RecordRun> runs;
+    std::vector<const ParallelReplay::Adders *> adders;
+    for (int k = 0; k < m->n; k++) {
+        const StepDev &sd = s.dev[k];
+        if (!sd.n_rec) continue;
+        runs.push_back({sd.rec, sd.n_rec, sd.chunk_base});
+        adders.push_back(sd.has_adders ? &sd.adders : nullptr);
+    }
+    ParallelReplay &pr = m->parallel;
+    double t[6] = {kTuning ? now_s() : 0};   // (tuning build) when each stage was done: added to the handle's times once a capture went all the way
+    const auto done = [&](int stage) { if (kTuning) t[stage] = now_s(); };
+    if (!pr.plan(m->filter, m->crc, runs, 4 * m->pool->threads(), true, &adders)) return false;
+    done(1);
+    if (pr.scan_needed()) m->pool->run(pr, &ParallelReplay::scan_part);
+    done(2);
+    if (!pr.merge()) return false;
+    done(3);
+    m->pool->run(pr, &ParallelReplay::score_part);
+    done(4);
+    const size_t n_msgs = pr.message_count();
+    if (to.takes_direct(n_msgs)) {
+        pr.copy_to(to.direct);
+        m->pool->run(pr, &ParallelReplay::copy_part);
+        pr.apply_adds(m->filter);
+        to.n = n_msgs, to.direct_done = true;
+    } else {
+        pr.finish(m->filter, to.out);
+    }
+    done(5);
+    m->parallel_scored++;
+    for (int k = 0; kTuning && k < 5; k++) m->t_stage[k] += t[k + 1] - t[k];
+    return true;
+}
+
+void replay_serial(adsb_multi *m, Step &s, std::vector<adsb_msg> &out)   // shard by shard, record by record
+{
+    for (int k = 0; k < m->n; k++)
+        if (s.dev[k].n_rec) replay_sorted(m->filter, m->crc, s.dev[k].rec, s.dev[k].n_rec, s.dev[k].chunk_base, out);
+}
+
+// The replay of a capture whose shards all arrived, through the ONE filter.  The shards are contiguous ascending buffer ranges, each in replay order (its
+// device thread saw to that): device by device IS global (buffer, j, try_phase) order.  May throw (out of memory): the caller poisons the handle then.
+int replay_capture(adsb_multi *m, Step &s, uint64_t n_records, Sink &to)
+{
+    const bool any_scored = std::any_of(&s.dev[0], &s.dev[0] + m->n, [](const StepDev &sd) { return sd.scored; });
+    if (any_scored) return replay_scored(m, s, to);                                  // a dense stream: some shards come scored by their devices
+    if (n_records >= m->parallel_min && replay_parallel(m, s, to)) return ADSB_OK;   // a busy sky: enough records to be worth several threads
+    replay_serial(m, s, to.out);                                                     // anything else, and what the parallel replay declined
+    return ADSB_OK;
+}
+
+// a capture failed (see the head of this file): what the refusals from now on will say
+void poison(adsb_multi *m, const char *why) noexcept
+{
+    m->poisoned = true;
+    try {
+        m->last_error = m->poison_error = why;
+    } catch (...) {
+    }
+}
+
+// the shards' counts and phase times into the capture's; returns the status of the first shard that failed (what failed: last_error)
+int fold_shards(adsb_multi *m, const Step &s, adsb_multi_stats &st)
+{
+    int rc = ADSB_OK;
+    double p1_first = 0, p1_last = 0, p2_first = 0, p2_last = 0, p1_max = 0, p2_max = 0;
+    for (int k = 0; k < m->n; k++) {
+        const StepDev &sd = s.dev[k];
+        if (sd.rc != ADSB_OK && rc == ADSB_OK) {
+            rc = sd.rc;
+            device_error(m, k, " (shard " + std::to_string(k) + "): " + sd.error);
+        }
+        st.n_chunks += sd.st.n_chunks, st.n_candidates += sd.st.n_candidates, st.n_ap_entries += sd.st.n_ap_entries, st.retries += sd.st.retries;
+        st.n_records += sd.scored ? sd.n_hits : sd.n_rec;
+        p1_first = k ? std::min(p1_first, sd.t_p1_issue) : sd.t_p1_issue, p2_first = k ? std::min(p2_first, sd.t_p2_issue) : sd.t_p2_issue;
+        p1_last = std::max(p1_last, sd.t_p1_done), p2_last = std::max(p2_last, sd.t_p2_done);
+        p1_max = std::max(p1_max, sd.t_p1_done - sd.t_p1_issue), p2_max = std::max(p2_max, sd.t_p2_done - sd.t_p2_issue);
+    }
+    st.ms_phase1_max = (float)(p1_max * 1e3), st.ms_phase2_max = (float)(p2_max * 1e3);
+    st.ms_phase1_span = (float)((p1_last - p1_first) * 1e3), st.ms_phase2_span = (float)((p2_last - p2_first) * 1e3);
+    return rc;
+}
+
+// the oldest capture in flight: waited for, replayed into `to`, its slot freed
+int collect_capture(adsb_multi *m, Sink &to) noexcept
 {
     if (m->collected == m->submitted) return ADSB_ERR_INVALID;
     Step &s = m->step[m->collected % kMultiSteps];
-    int rc = ADSB_OK;
-    bool direct_done = false;
-    adsb_multi_stats st{};
-    double tr0 = 0, tr1 = 0;
     if (!wait_done(m, [&] { return s.state.load(std::memory_order_acquire) == kDone; })) {
         // (the device threads bound their own waits, so this is a thread that died or a clock that jumped: the capture's
         // state is unknown and stays unfreed -- nothing more can be done with the handle but destroy it)
-        m->poisoned = true;
-        try {
-            m->poison_error = "a capture was never finished by the device threads";
-            m->last_error = m->poison_error;
-        } catch (...) {
-        }
+        poison(m, "a capture was never finished by the device threads");
         return ADSB_ERR_HIP;
     }
+    int rc = ADSB_OK;
+    adsb_multi_stats st{};
+    double tr0 = 0, tr1 = 0;
     try {
-        st.n_samples = s.n_samples;
-        st.n_devices = (uint32_t)m->n;
-        st.n_addrs_exchanged = s.fresh.size();
-        double p1_first = 0, p1_last = 0, p2_first = 0, p2_last = 0, p1_max = 0, p2_max = 0;
-        bool any_scored = false;
-        for (int k = 0; k < m->n; k++) {
-            const StepDev &sd = s.dev[k];
-            if (sd.rc != ADSB_OK && rc == ADSB_OK) {
-                rc = sd.rc;
-                m->last_error = "device " + std::to_string(m->dev[(size_t)k]->device) + " (shard " + std::to_string(k) + "): " + sd.error;
-            }
-            st.n_chunks += sd.st.n_chunks;
-            st.n_candidates += sd.st.n_candidates;
-            st.n_ap_entries += sd.st.n_ap_entries;
-            st.n_records += sd.scored ? sd.n_hits : sd.n_rec;
-            st.retries += sd.st.retries;
-            any_scored = any_scored || sd.scored;
-            p1_first = k ? std::min(p1_first, sd.t_p1_issue) : sd.t_p1_issue;
-            p1_last = std::max(p1_last, sd.t_p1_done);
-            p2_first = k ? std::min(p2_first, sd.t_p2_issue) : sd.t_p2_issue;
-            p2_last = std::max(p2_last, sd.t_p2_done);
-            p1_max = std::max(p1_max, sd.t_p1_done - sd.t_p1_issue);
-            p2_max = std::max(p2_max, sd.t_p2_done - sd.t_p2_issue);
-        }
-        st.ms_phase1_max = (float)(p1_max * 1e3);
-        st.ms_phase2_max = (float)(p2_max * 1e3);
-        st.ms_phase1_span = (float)((p1_last - p1_first) * 1e3);
-        st.ms_phase2_span = (float)((p2_last - p2_first) * 1e3);
+        st.n_samples = s.n_samples, st.n_devices = (uint32_t)m->n, st.n_addrs_exchanged = s.fresh.size();
+        rc = fold_shards(m, s, st);
         if (m->poisoned) {
             // (computed against a filter history that an earlier capture's failure broke: dropped)
             rc = refuse_poisoned(m);
         } else if (rc == ADSB_OK) {
             if (s.flush_before) m->filter.flush();   // icao_flush() took effect before this capture
             tr0 = now_s();
-            replay_capture(m, s, st, any_scored, out, direct, direct_cap, direct_n, direct_done, rc);
+            rc = replay_capture(m, s, st.n_records, to);
             tr1 = now_s();
         }
-        if (rc != ADSB_OK && !m->poisoned) {
-            m->poisoned = true;
-            m->poison_error = m->last_error;
-        }
+        if (rc != ADSB_OK && !m->poisoned) poison(m, m->last_error.c_str());
     } catch (...) {
         // (out of memory in the middle of the replay: the filter may hold half the capture's additions)
         rc = ADSB_ERR_NOMEM;
-        m->poisoned = true;
-        try {
-            m->poison_error = "out of memory while a capture was replayed";
-            m->last_error = m->poison_error;
-        } catch (...) {
-        }
+        poison(m, "out of memory while a capture was replayed");
     }
-    st.n_messages = rc != ADSB_OK ? 0 : (direct_done ? *direct_n : out.size());
+    st.n_messages = rc != ADSB_OK ? 0 : (to.direct_done ? to.n : to.out.size());
     st.ms_wall = (float)((s.t_done - s.t_submit) * 1e3);
     st.ms_exchange = (float)((s.t_exchange1 - s.t_exchange0) * 1e3);
     st.ms_replay = (float)((tr1 - tr0) * 1e3);
     m->stats = st;
-    if (rc != ADSB_OK) out.clear();
+    if (rc != ADSB_OK) to.out.clear();
     s.state.store(kFree, std::memory_order_release);
     m->collected++;
     return rc;
@@ -960,20 +966,18 @@ void resolve_wait(adsb_multi *m)
 void destroy_multi(adsb_multi *m) noexcept
 {
     // what is still in flight is finished first (its kernels write into the contexts' memory); every wait in there is bounded
-    std::vector<adsb_msg> drop;
     while (m->collected < m->submitted) {
-        drop.clear();
         const uint64_t before = m->collected;
-        (void)collect_capture(m, drop);
+        std::vector<adsb_msg> drop;
+        Sink to{drop};
+        (void)collect_capture(m, to);
         if (m->collected == before) break;   // (a capture the device threads never finished: its contexts are leaked below)
     }
     const bool stuck = m->collected < m->submitted;
-#ifdef ADSB_TUNING
     if (tuning_env("ADSB_HOST_TIMES") && m->parallel_scored)
         std::fprintf(stderr, "adsb_multi parallel replay: %llu captures; us per capture: plan %.1f, scan %.1f, merge %.1f, score %.1f, finish %.1f\n",
                      (unsigned long long)m->parallel_scored, m->t_stage[0] / m->parallel_scored * 1e6, m->t_stage[1] / m->parallel_scored * 1e6,
                      m->t_stage[2] / m->parallel_scored * 1e6, m->t_stage[3] / m->parallel_scored * 1e6, m->t_stage[4] / m->parallel_scored * 1e6);
-#endif
     for (auto &d : m->dev)
         if (d->th.joinable()) push_cmd(*d, Cmd{Cmd::kStop, 0});
     for (auto &d : m->dev)
@@ -999,16 +1003,25 @@ void destroy_multi(adsb_multi *m) noexcept
     delete m;
 }
 
-int finish_collect(adsb_multi *m, int rc, size_t direct_n, adsb_msg *out, size_t cap, size_t *n_out)
+// collect's last step: the oldest capture into the caller's array; what did not fit is kept for adsb_multi_fetch_messages
+int collect_into(adsb_multi *m, adsb_msg *out, size_t cap, size_t *n_out)
 {
-    if (rc != ADSB_OK) return rc;
-    if (direct_n != ~(size_t)0) {   // (the messages are in `out` already)
-        if (n_out) *n_out = direct_n;
-        m->has_undelivered = false;
-        m->undelivered.clear();
-        return ADSB_OK;
-    }
-    return deliver_multi(m, m->msgs, out, cap, n_out);
+    m->msgs.clear();
+    Sink to{m->msgs, out, cap};
+    if (int rc = collect_capture(m, to)) return rc;
+    const int rc = deliver_multi(m, m->msgs, out, cap, n_out);
+    if (to.direct_done && n_out) *n_out = to.n;   // (the messages are in `out` already, the list is empty)
+    return rc;
+}
+
+void even_split(const adsb_multi *m, size_t len, size_t *n) { for (int k = 0; k < m->n; k++) (void)adsb_multi_shard_range(len, m->n, k, nullptr, &n[k]); }
+
+void add_stats(adsb_multi_stats &to, const adsb_multi_stats &from)   // (n_devices and n_messages are the caller's to set)
+{
+    to.n_samples += from.n_samples, to.n_chunks += from.n_chunks, to.n_candidates += from.n_candidates, to.n_ap_entries += from.n_ap_entries;
+    to.n_records += from.n_records, to.retries += from.retries, to.n_addrs_exchanged += from.n_addrs_exchanged, to.ms_wall += from.ms_wall;
+    to.ms_replay += from.ms_replay, to.ms_exchange += from.ms_exchange, to.ms_phase1_max += from.ms_phase1_max, to.ms_phase2_max += from.ms_phase2_max;
+    to.ms_phase1_span += from.ms_phase1_span, to.ms_phase2_span += from.ms_phase2_span;
 }
 
 }  // namespace
@@ -1019,7 +1032,7 @@ int adsb_multi_create(adsb_multi **out, const int *devices, int n_devices, size_
 {
     if (!out) return ADSB_ERR_INVALID;
     *out = nullptr;
-    if (!devices || n_devices <= 0 || n_devices > 64) return ADSB_ERR_INVALID;
+    if (!devices || n_devices <= 0 || n_devices > kMaxDevices) return ADSB_ERR_INVALID;
     return abi_guard([&]() -> int {
         if (max_chunks_per_device == 0) max_chunks_per_device = 1;
         adsb_multi *m = new adsb_multi;
@@ -1117,8 +1130,8 @@ int adsb_multi_submit_iq(adsb_multi *m, const int16_t *iq_re_im, size_t n_sample
     if (!m || !iq_re_im || n_samples == 0) return ADSB_ERR_INVALID;
     return abi_guard([&]() -> int {
         if ((n_samples + kChunkSamples - 1) / kChunkSamples > (size_t)m->n * m->max_chunks) return ADSB_ERR_INVALID;
-        size_t n[64];
-        for (int k = 0; k < m->n; k++) (void)adsb_multi_shard_range(n_samples, m->n, k, nullptr, &n[k]);
+        size_t n[kMaxDevices];
+        even_split(m, n_samples, n);
         return submit_capture(m, nullptr, iq_re_im, true, n);
     });
 }
@@ -1157,13 +1170,12 @@ int adsb_multi_icao_flush(adsb_multi *m)
             int rc = ADSB_OK;
             for (auto &d : m->dev) {
                 if (!wait_done(m, [&] { return d->reset_done.load(std::memory_order_acquire) != 0; })) {
-                    m->last_error = "device " + std::to_string(d->device) + ": its thread did not answer the reset";
+                    device_error(m, d->index, ": its thread did not answer the reset");
                     return ADSB_ERR_HIP;
                 }
                 if (d->reset_rc != ADSB_OK && rc == ADSB_OK) {
                     rc = d->reset_rc;
-                    m->last_error = "device " + std::to_string(d->device) + " could not be reset (" + d->ctx->last_error +
-                                    "): the adsb_multi stays poisoned, destroy it";
+                    device_error(m, d->index, " could not be reset (" + d->ctx->last_error + "): the adsb_multi stays poisoned, destroy it");
                 }
             }
             if (rc != ADSB_OK) return rc;
@@ -1186,12 +1198,7 @@ int adsb_multi_submit_iq_device(adsb_multi *m, const void *const *device_iq, con
 int adsb_multi_collect(adsb_multi *m, adsb_msg *out, size_t cap, size_t *n_out)
 {
     if (!m || (!out && cap)) return ADSB_ERR_INVALID;
-    return abi_guard([&]() -> int {
-        m->msgs.clear();
-        size_t direct_n = ~(size_t)0;
-        const int rc = collect_capture(m, m->msgs, out, cap, &direct_n);
-        return finish_collect(m, rc, direct_n, out, cap, n_out);
-    });
+    return abi_guard([&] { return collect_into(m, out, cap, n_out); });
 }
 
 int adsb_multi_demod_iq_device(adsb_multi *m, const void *const *device_iq, const size_t *n_samples, adsb_msg *out,
@@ -1201,10 +1208,7 @@ int adsb_multi_demod_iq_device(adsb_multi *m, const void *const *device_iq, cons
     return abi_guard([&]() -> int {
         if (m->submitted != m->collected) return ADSB_ERR_BUSY;
         if (int rc = submit_capture(m, device_iq, nullptr, false, n_samples)) return rc;
-        m->msgs.clear();
-        size_t direct_n = ~(size_t)0;
-        const int rc = collect_capture(m, m->msgs, out, cap, &direct_n);
-        return finish_collect(m, rc, direct_n, out, cap, n_out);
+        return collect_into(m, out, cap, n_out);
     });
 }
 
@@ -1218,24 +1222,20 @@ int adsb_multi_demod_iq(adsb_multi *m, const int16_t *iq_re_im, size_t n_samples
         const size_t piece = (size_t)m->n * m->max_chunks * kChunkSamples;
         std::vector<adsb_msg> msgs;
         adsb_multi_stats total{};
-        size_t n[64];
+        size_t n[kMaxDevices];
         for (size_t off = 0; off < n_samples || (off == 0 && n_samples == 0); off += piece) {
             const size_t len = std::min(piece, n_samples - off);
-            for (int k = 0; k < m->n; k++) (void)adsb_multi_shard_range(len, m->n, k, nullptr, &n[k]);
+            even_split(m, len, n);
             if (int rc = submit_capture(m, nullptr, n_samples ? iq_re_im + 2 * off : nullptr, true, n)) return rc;
             std::vector<adsb_msg> part;
-            if (int rc = collect_capture(m, part)) return rc;
+            Sink to{part};
+            if (int rc = collect_capture(m, to)) return rc;
             const uint64_t chunk0 = off / kChunkSamples;
             for (auto &msg : part) {
                 msg.chunk += chunk0;
                 msgs.push_back(msg);
             }
-            total.n_samples += m->stats.n_samples, total.n_chunks += m->stats.n_chunks, total.n_candidates += m->stats.n_candidates;
-            total.n_ap_entries += m->stats.n_ap_entries, total.n_records += m->stats.n_records, total.retries += m->stats.retries;
-            total.n_addrs_exchanged += m->stats.n_addrs_exchanged, total.ms_wall += m->stats.ms_wall;
-            total.ms_replay += m->stats.ms_replay, total.ms_exchange += m->stats.ms_exchange;
-            total.ms_phase1_max += m->stats.ms_phase1_max, total.ms_phase2_max += m->stats.ms_phase2_max;
-            total.ms_phase1_span += m->stats.ms_phase1_span, total.ms_phase2_span += m->stats.ms_phase2_span;
+            add_stats(total, m->stats);
             if (n_samples == 0) break;
         }
         total.n_devices = (uint32_t)m->n;

@@ -1,7 +1,8 @@
 """adsb_multi's orchestration on the CPU, under ThreadSanitizer and under AddressSanitizer + UBSan.
 
-csrc/adsb_multi.cpp -- the device threads, the lock-free step state machine (Step::state, p1_left / p2_left, the command
-rings), dispatch_ready by whichever thread lands last, the collector, the replay pool behind it, the poisoned-handle rules
+csrc/adsb_multi.cpp -- the device threads (DeviceWorker), the lock-free step state machine (Step::state, p1_left / p2_left,
+the command rings), dispatch_ready by whichever thread lands last, the collector (collect_capture and the three replays
+behind replay_capture), the replay pool behind it, the poisoned-handle rules
 and the restart -- is compiled AS IT IS by g++ and linked against tests/multi_fake_backend.cpp, which fakes what lies below
 it: the handful of HIP calls it makes itself and the shard_* entry points of csrc/adsb_shard.cpp, as a "device" that slices
 its shard with the oracle, keeps the address superset the real context keeps, scores about half of its shards itself (as
