@@ -18,6 +18,7 @@ from .context import (  # noqa: F401
     Context,
     MagnitudeBuffer,
     ModeSMessage,
+    replay_records_rx,
     default_context,
 )
 from . import demod_2400, icao_filter, utils  # noqa: F401

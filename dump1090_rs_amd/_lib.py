@@ -22,6 +22,7 @@ ADSB_SCORE_FIXED_1BIT = 1200
 ADSB_FIX_2BIT = 3
 ADSB_SCORE_FIXED_2BIT = 1100
 ADSB_FAULT_PHASE1, ADSB_FAULT_PHASE2, ADSB_FAULT_HANG, ADSB_FAULT_RECORDS = 1, 2, 3, 4
+ADSB_MAX_RECEIVERS = 16384
 
 
 class AdsbMsg(C.Structure):
@@ -260,6 +261,25 @@ def lib() -> C.CDLL:
                  "adsb_multi_collect", "adsb_multi_pending", "adsb_multi_fetch_messages", "adsb_multi_get_stats",
                  "adsb_multi_filter_table", "adsb_multi_set_wait", "adsb_multi_get_wait", "adsb_multi_set_timeout_ms",
                  "adsb_multi_selftest_fail"):
+        getattr(L, name).restype = C.c_int
+    # many receivers, one pass (include/adsb_hip.h)
+    u32 = C.c_uint32
+    L.adsb_set_receivers.argtypes = [vp, u32]
+    L.adsb_get_receivers.argtypes = [vp]
+    L.adsb_icao_flush_receiver.argtypes = [vp, u32]
+    L.adsb_receiver_filter_table.argtypes = [vp, u32, vp]
+    for name in ("adsb_demod_iq_rx", "adsb_demod_iq_device_rx", "adsb_demod_iq_rx_u8", "adsb_demod_iq_device_rx_u8"):
+        getattr(L, name).argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(sz)]
+    L.adsb_submit_iq_device_rx.argtypes = [vp, vp, sz, vp]
+    L.adsb_submit_iq_device_rx_u8.argtypes = [vp, vp, sz, vp]
+    L.adsb_ring_submit_rx.argtypes = [vp, sz, vp]
+    L.adsb_replay_records_rx.argtypes = [vp, u32, vp, sz, vp, sz, C.c_int, C.c_int, vp, sz, C.POINTER(sz)]
+    L.adsb_selftest_rx_tune.argtypes = [vp, u32]
+    L.adsb_selftest_rx_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    for name in ("adsb_set_receivers", "adsb_get_receivers", "adsb_icao_flush_receiver", "adsb_receiver_filter_table",
+                 "adsb_demod_iq_rx", "adsb_demod_iq_device_rx", "adsb_demod_iq_rx_u8", "adsb_demod_iq_device_rx_u8",
+                 "adsb_submit_iq_device_rx", "adsb_submit_iq_device_rx_u8", "adsb_ring_submit_rx", "adsb_replay_records_rx",
+                 "adsb_selftest_rx_tune", "adsb_selftest_rx_counters"):
         getattr(L, name).restype = C.c_int
     L.adsb_host_replays.argtypes = [vp]
     L.adsb_host_replays.restype = C.c_uint64

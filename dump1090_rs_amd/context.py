@@ -129,6 +129,39 @@ def replay_records(records: np.ndarray, filter_table: Optional[np.ndarray] = Non
                          int(m.try_phase), int(m.chunk)) for m in out[: n.value]]
 
 
+def _as_map(receivers, n_samples: Optional[int] = None) -> np.ndarray:
+    """The receiver of every buffer of a call as the library takes it: uint32, C-contiguous (converted otherwise), one
+    entry per 131072-sample buffer."""
+    m = np.ascontiguousarray(receivers, dtype=np.uint32)
+    if m.ndim != 1:
+        raise ValueError("the receiver map is a flat array, one entry per buffer")
+    if n_samples is not None and m.shape[0] < -(-n_samples // MODES_MAG_BUF_SAMPLES):
+        raise ValueError(f"the receiver map names {m.shape[0]} buffers, the call has {-(-n_samples // MODES_MAG_BUF_SAMPLES)}")
+    return m
+
+
+def replay_records_rx(records: np.ndarray, receivers, filter_tables: np.ndarray, mode: int = 0, threads: int = 1,
+                      cap: Optional[int] = None) -> List["ModeSMessage"]:
+    """adsb_replay_records_rx: the ordered host replay with one filter per receiver.  `receivers[b]` is the receiver of
+    buffer b (the records' `chunk`); `filter_tables` ((n_receivers, 4096) u32, table A of every filter) is read and
+    updated.  threads > 1: the receivers dealt to that many threads -- the same result."""
+    L = _lib.lib()
+    rec = np.ascontiguousarray(records, dtype=TRIAL_DTYPE).copy()
+    m = _as_map(receivers)
+    assert filter_tables.dtype == np.uint32 and filter_tables.ndim == 2 and filter_tables.shape[1] == 4096 \
+        and filter_tables.flags.c_contiguous
+    cap = cap or max(4096, rec.shape[0])
+    out = (AdsbMsg * cap)()
+    n = C.c_size_t()
+    st = L.adsb_replay_records_rx(filter_tables.ctypes.data, filter_tables.shape[0], m.ctypes.data if m.size else None,
+                                  m.shape[0], rec.ctypes.data if rec.size else None, rec.shape[0], int(mode), int(threads),
+                                  out, cap, C.byref(n))
+    if st != _lib.ADSB_OK:
+        raise AdsbError(st, f"adsb_replay_records_rx: {L.adsb_strerror(st).decode()}")
+    return [ModeSMessage(bytes(x.msg), int(x.len), float(x.signal_level), int(x.score), int(x.j),
+                         int(x.try_phase), int(x.chunk)) for x in out[: n.value]]
+
+
 class Context:
     """One adsb_ctx: device buffers, stream and the ICAO filter of one stream of IQ."""
 
@@ -404,6 +437,81 @@ class Context:
     def ring_submit(self, n_samples: int) -> None:
         self._check(self._L.adsb_ring_submit(self._h, n_samples), "adsb_ring_submit")
 
+    # -- many receivers, one pass: one ICAO filter per receiver, `receivers[b]` names the receiver of buffer b of a call
+    #    (include/adsb_hip.h, "Many receivers, one pass")
+    def set_receivers(self, n: int) -> None:
+        """adsb_set_receivers: n filters (0: off); every receiver restarts from an empty filter."""
+        self._check(self._L.adsb_set_receivers(self._h, int(n)), "adsb_set_receivers")
+
+    def receivers(self) -> int:
+        return int(self._L.adsb_get_receivers(self._h))
+
+    def icao_flush_receiver(self, r: int) -> None:
+        """icao_flush() for receiver r alone, for the passes submitted after it."""
+        self._check(self._L.adsb_icao_flush_receiver(self._h, int(r)), "adsb_icao_flush_receiver")
+
+    def receiver_filter_table(self, r: int) -> np.ndarray:
+        """Table A (4096 u32) of receiver r's filter."""
+        out = np.zeros(4096, dtype=np.uint32)
+        self._check(self._L.adsb_receiver_filter_table(self._h, int(r), out.ctypes.data), "adsb_receiver_filter_table")
+        return out
+
+    def demod_iq_rx(self, iq, receivers, cap: Optional[int] = None) -> List[ModeSMessage]:
+        a = _as_iq(iq)
+        m = _as_map(receivers, a.shape[0])
+        cap = cap or max(4096, a.shape[0] // 256)
+        return self._collect(
+            lambda out, c, n: self._L.adsb_demod_iq_rx(self._h, a.ctypes.data, a.shape[0], m.ctypes.data, out, c, n),
+            "adsb_demod_iq_rx", cap)
+
+    def demod_iq_rx_u8(self, iq, receivers, cap: Optional[int] = None) -> List[ModeSMessage]:
+        a = _as_cu8(iq)
+        m = _as_map(receivers, a.shape[0])
+        cap = cap or max(4096, a.shape[0] // 256)
+        return self._collect(
+            lambda out, c, n: self._L.adsb_demod_iq_rx_u8(self._h, a.ctypes.data, a.shape[0], m.ctypes.data, out, c, n),
+            "adsb_demod_iq_rx_u8", cap)
+
+    def demod_iq_device_rx(self, device_ptr: int, n_samples: int, receivers, cap: Optional[int] = None) -> List[ModeSMessage]:
+        m = _as_map(receivers, n_samples)
+        cap = cap or max(4096, n_samples // 256)
+        return self._collect(
+            lambda out, c, n: self._L.adsb_demod_iq_device_rx(self._h, C.c_void_p(device_ptr), n_samples, m.ctypes.data, out, c, n),
+            "adsb_demod_iq_device_rx", cap)
+
+    def demod_iq_device_rx_u8(self, device_ptr: int, n_samples: int, receivers, cap: Optional[int] = None) -> List[ModeSMessage]:
+        m = _as_map(receivers, n_samples)
+        cap = cap or max(4096, n_samples // 256)
+        return self._collect(
+            lambda out, c, n: self._L.adsb_demod_iq_device_rx_u8(self._h, C.c_void_p(device_ptr), n_samples, m.ctypes.data, out, c, n),
+            "adsb_demod_iq_device_rx_u8", cap)
+
+    def submit_iq_device_rx(self, device_ptr: int, n_samples: int, receivers) -> None:
+        m = _as_map(receivers, n_samples)   # (copied by the call: it need not outlive it)
+        self._check(self._L.adsb_submit_iq_device_rx(self._h, C.c_void_p(device_ptr), n_samples, m.ctypes.data),
+                    "adsb_submit_iq_device_rx")
+
+    def submit_iq_device_rx_u8(self, device_ptr: int, n_samples: int, receivers) -> None:
+        m = _as_map(receivers, n_samples)
+        self._check(self._L.adsb_submit_iq_device_rx_u8(self._h, C.c_void_p(device_ptr), n_samples, m.ctypes.data),
+                    "adsb_submit_iq_device_rx_u8")
+
+    def ring_submit_rx(self, n_samples: int, receivers) -> None:
+        m = _as_map(receivers, n_samples)
+        self._check(self._L.adsb_ring_submit_rx(self._h, n_samples, m.ctypes.data), "adsb_ring_submit_rx")
+
+    def selftest_rx_tune(self, parallel_min: int = 0) -> None:
+        self._check(self._L.adsb_selftest_rx_tune(self._h, int(parallel_min)), "adsb_selftest_rx_tune")
+
+    def selftest_rx_counters(self) -> dict:
+        """adsb_selftest_rx_counters: passes replayed per receiver, those of them replayed by several threads, and how
+        often the device's superset was put back from the union of the receivers' filters."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.adsb_selftest_rx_counters(self._h, out), "adsb_selftest_rx_counters")
+        return {"rx_passes": int(out[0]), "pooled_passes": int(out[1]), "union_reseeds": int(out[2])}
+
+    def pending(self) -> int:
+        return int(self._L.adsb_pending(self._h))
     def pending(self) -> int:
         return int(self._L.adsb_pending(self._h))
 

@@ -39,10 +39,46 @@ bool take_device_result(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vecto
     return true;
 }
 
+// The ordered replay of a pass whose buffers belong to several receivers (adsb_set_receivers): every record against the
+// filter of the receiver of its buffer, sl.rx_map[chunk_offset + chunk] (chunk_offset: the buffer the overflow fallback
+// is at).  A pass of at least rx_parallel_min records with more than one receiver in it is dealt, receiver by receiver,
+// to the threads of a pool made when the first such pass comes along (adsb_replay_host.h: ReceiverReplay).
+// *gained: some receiver's filter took a new address.
+int replay_receivers(adsb_ctx *c, const Slot &sl, size_t n, uint64_t chunk_offset, std::vector<adsb_msg> &out, bool *gained)
+{
+    const size_t first = (size_t)chunk_offset, last = std::min(sl.rx_map.size(), first + sl.n_chunks);
+    bool several = false;
+    for (size_t b = first + 1; b < last && !several; b++) several = sl.rx_map[b] != sl.rx_map[first];
+    ReplayPool *pool = nullptr;
+    if (several && n >= c->rx_parallel_min) {
+        if (!c->rx_pool) {
+            // up to six threads beside the caller, never more than a quarter of the cores; they sleep between passes
+            const unsigned hw = std::thread::hardware_concurrency();
+            c->rx_pool.reset(new ReplayPool((int)std::min(6u, std::max(1u, hw / 4)), {}, 0));
+        }
+        pool = c->rx_pool.get();
+    }
+    bool pooled = false;
+    if (!c->rx_replay.run(c->rx_filter_of.data(), sl.rx_map.data(), sl.rx_map.size(), c->crc, sl.h_rec, n, chunk_offset, out, pool,
+                          &c->host_sorts, gained, &pooled)) {
+        c->last_error = "a trial record names a buffer outside the pass that wrote it";
+        return ADSB_ERR_HIP;
+    }
+    c->rx_passes++;
+    c->rx_pooled += pooled;
+    return ADSB_OK;
+}
+
 }  // namespace
 
 namespace adsb {
 namespace host {
+
+void flush_host_filters(adsb_ctx *c)
+{
+    c->filter.flush();
+    for (IcaoFilter &f : c->rx_filters) f.flush();
+}
 
 // The records and the summary travel to host memory as separate posted writes; the summary's
 // sequence word says the pass is done, this says every one of its records has landed whole: the
@@ -229,7 +265,14 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
     {
         HT(c, HT_REPLAY);
         const uint64_t before = c->filter.inserts();
-        if (!skip_replay) replay(c->filter, c->crc, sl.h_rec, n, chunk_offset, out, &c->host_sorts);
+        if (c->n_receivers && !skip_replay) {
+            // (conservative: the address ANY receiver's filter gained may be one the union already held -- never wrong)
+            bool gained = false;
+            if (int rc = replay_receivers(c, sl, n, chunk_offset, out, &gained)) return rc;
+            if (gained) c->last_new_insert_seq = sl.scan_seq;
+        } else if (!skip_replay) {
+            replay(c->filter, c->crc, sl.h_rec, n, chunk_offset, out, &c->host_sorts);
+        }
         if (c->filter.inserts() != before) c->last_new_insert_seq = sl.scan_seq;
     }
 #ifdef ADSB_TUNING
@@ -248,7 +291,11 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
     adsb_stats st{};
     st.n_samples = sl.n_samples;
     st.n_chunks = sl.n_chunks;
-    if (sl.flush_before) c->filter.flush();  // icao_flush() took effect before this pass
+    if (sl.flush_before) flush_host_filters(c);  // icao_flush() took effect before this pass
+    // ... and so did the adsb_icao_flush_receiver calls recorded against it (host only: the device's superset stays one)
+    for (uint32_t r : sl.rx_flush)
+        if (r < c->rx_filter_of.size()) c->rx_filter_of[r]->flush();
+    sl.rx_flush.clear();
     int rc = finish_pass(c, sl, 0, st, out);
     if (rc == 2) {
         // a one-launch pass that a pass in flight beside it may have invalidated (finish_pass): once more

@@ -595,6 +595,8 @@ int adsb_set_carry_over(adsb_ctx *c, int enabled)
 try {
     if (!c) return ADSB_ERR_INVALID;
     if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    // (the lead-in of a buffer would have to be the end of ITS receiver's previous buffer: adsb_set_receivers)
+    if (enabled && c->n_receivers) return ADSB_ERR_INVALID;
     ADSB_ON_DEVICE(c);
     c->carry_over = enabled != 0;
     // the stream starts here: nothing precedes the next call
@@ -674,6 +676,76 @@ int adsb_icao_flush(adsb_ctx *c)
     // clears the device bitmap (stream-ordered), and the host filter is flushed when that
     // pass is collected, after the passes before it have been replayed.
     c->flush_pending = true;
+    return ADSB_OK;
+}
+
+// ---- many receivers, one pass (include/adsb_hip.h) ----
+int adsb_set_receivers(adsb_ctx *c, uint32_t n_receivers)
+try {
+    if (!c || n_receivers > ADSB_MAX_RECEIVERS || (n_receivers && c->carry_over)) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    if (n_receivers == c->n_receivers) return ADSB_OK;
+    // everything that can fail first: the filters of receivers 1 .. n - 1 (16 KB each) and, per pass in flight, room
+    // for the largest map, so that no submit allocates
+    std::vector<IcaoFilter> filters(n_receivers > 1 ? n_receivers - 1 : 0);
+    std::vector<IcaoFilter *> filter_of(n_receivers);
+    for (uint32_t r = 0; r < n_receivers; r++) filter_of[r] = r ? &filters[r - 1] : &c->filter;
+    for (int si = 0; si < c->n_slots; si++) {
+        c->slot[si].rx_map.reserve(n_receivers ? c->max_chunks : 0);
+        c->slot[si].rx_map.clear();
+        c->slot[si].rx_flush.clear();
+    }
+    c->rx_flush_next.clear();
+    c->rx_filters.swap(filters);   // (the vector's elements stay where they are: filter_of points at them)
+    c->rx_filter_of.swap(filter_of);
+    c->n_receivers = n_receivers;
+    // every receiver starts from an empty filter, as after adsb_icao_flush: the host's filters now (nothing is in
+    // flight), the device's superset with the next pass; and the device's own copy of the one filter is rebuilt from
+    // the host's before a pass is scored on the device again
+    c->filter.flush();
+    c->flush_pending = true;
+    c->score_epoch++;
+    c->exact_valid = false;
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_get_receivers(const adsb_ctx *c) { return c ? (int)c->n_receivers : ADSB_ERR_INVALID; }
+
+int adsb_icao_flush_receiver(adsb_ctx *c, uint32_t receiver)
+try {
+    if (!c || receiver >= c->n_receivers) return ADSB_ERR_INVALID;
+    // Host only: the device's superset keeps the receiver's addresses (it stays a superset of every filter).  With
+    // nothing left to replay the filter is emptied here; otherwise when the next pass submitted is collected, in front
+    // of its replay, behind the replays of the passes in flight now.
+    if (c->submitted == c->collected) c->rx_filter_of[receiver]->flush();
+    else c->rx_flush_next.push_back(receiver);
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_receiver_filter_table(const adsb_ctx *c, uint32_t receiver, uint32_t *out4096)
+try {
+    if (!c || !out4096 || receiver >= c->n_receivers) return ADSB_ERR_INVALID;
+    if (c->submitted != c->collected) return ADSB_ERR_BUSY;
+    c->rx_filter_of[receiver]->store(out4096);
+    // (flushes that wait for the next pass have emptied it as far as the caller is concerned)
+    bool flushed = c->flush_pending;
+    for (uint32_t r : c->rx_flush_next) flushed = flushed || r == receiver;
+    if (flushed) std::memset(out4096, 0, IcaoFilter::kSize * sizeof(uint32_t));
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_selftest_rx_tune(adsb_ctx *c, uint32_t parallel_min)
+{
+    if (!c) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
+    c->rx_parallel_min = parallel_min ? parallel_min : kRxParallelReplayMin;
+    return ADSB_OK;
+}
+
+int adsb_selftest_rx_counters(const adsb_ctx *c, uint64_t *out4)
+{
+    if (!c || !out4) return ADSB_ERR_INVALID;
+    out4[0] = c->rx_passes, out4[1] = c->rx_pooled, out4[2] = c->rx_reseeds, out4[3] = 0;
     return ADSB_OK;
 }
 

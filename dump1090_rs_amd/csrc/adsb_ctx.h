@@ -97,6 +97,10 @@ struct Slot {
     adsb_signal_stats *h_sig = nullptr, *h_sig_dev = nullptr;
     uint32_t *d_sig_part = nullptr, *d_sig_ticket = nullptr;
     std::vector<adsb_signal_stats> parked_sig;
+    // many receivers, one pass (adsb_set_receivers): the receiver of every buffer of this pass (reserved to max_chunks when
+    // the mode is set: no allocation per submit), and the receivers whose host filters an adsb_icao_flush_receiver empties
+    // in front of this pass's replay
+    std::vector<uint32_t> rx_map, rx_flush;
 };
 
 // Passes in flight: 4 and the device never waits for the host between large passes (3 do for sparse
@@ -113,6 +117,9 @@ constexpr int kScanStreams = ADSB_SCAN_STREAMS;
 constexpr int kScanEvRing = kSlots + 3;  // scan start / stop event pairs in rotation (finish_pass: ms_scan_exclusive)
 
 constexpr size_t kTimelineWords = (size_t)adsb::kApSegments * 8 * 8;  // 8 waves x 8 counters per workgroup
+
+// records in a pass from which its per-receiver replay is dealt to several threads (adsb_multi's kParallelReplayMin)
+constexpr uint32_t kRxParallelReplayMin = 8192;
 
 struct adsb_ctx {
     int device = -1;
@@ -299,6 +306,20 @@ struct adsb_ctx {
     uint32_t *d_sig_block = nullptr;
     std::vector<adsb_signal_stats> sig_out;
     uint64_t sig_launches = 0;   // k_signal_stats launches so far (adsb_selftest_signal_launches)
+    // Many receivers, one pass (adsb_set_receivers; include/adsb_hip.h).  The device side does not know whose buffer it
+    // scans: the address superset holds the union of all receivers' addresses, which is a superset of every receiver's
+    // filter.  The host replays every buffer against the filter of its receiver: `filter` is receiver 0's (so that the
+    // default path is what it always was), rx_filters hold receivers 1 .. n - 1.
+    uint32_t n_receivers = 0;                // 0: off
+    std::vector<IcaoFilter> rx_filters;
+    std::vector<IcaoFilter *> rx_filter_of;  // receiver -> its filter
+    const uint32_t *rx_call_map = nullptr;   // the caller's map, from the first buffer of the next pass submitted on (null:
+                                             // a plain call, every buffer is receiver 0); submit() copies and advances it
+    std::vector<uint32_t> rx_flush_next;     // adsb_icao_flush_receiver calls recorded against the next submission
+    adsb::host::ReceiverReplay rx_replay;
+    std::unique_ptr<adsb::host::ReplayPool> rx_pool;     // created with the first pass that is replayed by several threads
+    uint32_t rx_parallel_min = kRxParallelReplayMin;
+    uint64_t rx_passes = 0, rx_pooled = 0, rx_reseeds = 0;   // adsb_selftest_rx_counters
 };
 
 namespace adsb {
@@ -415,6 +436,7 @@ void wire_score(const Slot &sl, ScanParams &p, uint32_t *exact, uint32_t *exact_
 uint32_t next_seq(adsb_ctx *c);
 void stamp_seq(adsb_ctx *c, Slot &sl, ScanParams &p, bool scored = false);
 // the 24-bit addresses in the host's filter table / room for n addresses in c->d_addrs (`alloc` entries when it has to grow)
+// (with receivers on: the union of all receivers' filters, sorted, each address once)
 std::vector<uint32_t> filter_addresses(const adsb_ctx *c);
 int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc);
 int resync_exact(adsb_ctx *c);
@@ -430,6 +452,24 @@ void soapy_u8_table(int16_t *out256);
 int ensure_stage(adsb_ctx *c, size_t bytes);
 int ensure_host_stage(adsb_ctx *c, size_t bytes);
 
+// An _rx call's map: ADSB_ERR_INVALID unless receivers are on and every one of the call's buffers names one of them
+inline int rx_check(const adsb_ctx *c, size_t n_samples, const uint32_t *map)
+{
+    if (!c || !c->n_receivers || !map) return ADSB_ERR_INVALID;
+    const size_t n_buffers = n_samples / kChunkSamples + (n_samples % kChunkSamples != 0);
+    for (size_t b = 0; b < n_buffers; b++)
+        if (map[b] >= c->n_receivers) return ADSB_ERR_INVALID;
+    return ADSB_OK;
+}
+// ... handed to the passes the call submits (submit() copies each pass's part), for the length of the call
+struct RxCall {
+    adsb_ctx *c;
+    RxCall(adsb_ctx *ctx, const uint32_t *map) : c(ctx) { c->rx_call_map = map; }
+    ~RxCall() { c->rx_call_map = nullptr; }
+    RxCall(const RxCall &) = delete;
+    RxCall &operator=(const RxCall &) = delete;
+};
+
 // adsb_context.cpp: the signal-statistics storage of every slot, on first enable
 int ensure_signal_stats(adsb_ctx *c);
 
@@ -441,6 +481,8 @@ int park_pending(adsb_ctx *c);
 int collect_next(adsb_ctx *c, std::vector<adsb_msg> &out);
 int deliver(adsb_ctx *c, std::vector<adsb_msg> &msgs, adsb_msg *out, size_t cap, size_t *n_out);
 bool summary_landed(const Summary *s, uint32_t seq);
+// adsb_icao_flush for the host side: every receiver's filter
+void flush_host_filters(adsb_ctx *c);
 
 // adsb_shard.cpp: one shard of a capture in slot k, phase by phase, nothing blocking but shard_phase_wait
 // (and the buffer-by-buffer fallback of a shard that overflows the lists).  Order of calls per slot:

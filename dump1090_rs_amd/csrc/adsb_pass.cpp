@@ -169,7 +169,8 @@ static int plan_pass(adsb_ctx *c, const Slot &sl, SrcFormat fmt, uint32_t n_chun
     // time; the worst-case lists of the fallback are the host's too.
     pl.ordered = !opt.force_simple && n_chunks > kInlineTailChunks && sl.hits_cap == c->hits_cap && c->dense_mode;
     // (in every error-correction mode: k_score / k_emit score and repair a fix pass's DF17/18 trials themselves)
-    const bool score_on_device = pl.ordered && c->score.si;
+    // (never with receivers on: k_score holds ONE filter, the replay of such a pass is the host's, buffer by buffer)
+    const bool score_on_device = pl.ordered && c->score.si && !c->n_receivers;
     if (score_on_device && !c->exact_valid) {
         // the device's copy of the filter can only be rebuilt from the host's once every pass in
         // flight has been replayed: finish them now (their results wait for adsb_collect)
@@ -510,6 +511,14 @@ std::vector<uint32_t> filter_addresses(const adsb_ctx *c)
     std::vector<uint32_t> addrs;
     for (uint32_t a : c->filter.table())
         if (a != 0 && a <= 0xFFFFFFu) addrs.push_back(a);  // DF18 entries (addr | 1 << 25) match no 24-bit residual
+    if (c->n_receivers > 1) {
+        // the superset every receiver's buffers are matched against: the union of all their filters
+        for (const IcaoFilter &f : c->rx_filters)
+            for (uint32_t a : f.table())
+                if (a != 0 && a <= 0xFFFFFFu) addrs.push_back(a);
+        std::sort(addrs.begin(), addrs.end());
+        addrs.erase(std::unique(addrs.begin(), addrs.end()), addrs.end());
+    }
     return addrs;
 }
 
@@ -550,7 +559,9 @@ int reseed_bitmap_from_filter(adsb_ctx *c)
 {
     const std::vector<uint32_t> addrs = filter_addresses(c);
     if (addrs.empty()) return ADSB_OK;
-    if (int rc = ensure_addrs(c, addrs.size(), IcaoFilter::kSize)) return rc;
+    if (c->n_receivers) c->rx_reseeds++;
+    // (one filter holds at most 4096 addresses; the union of many receivers' may hold more)
+    if (int rc = ensure_addrs(c, addrs.size(), std::max<size_t>(IcaoFilter::kSize, addrs.size()))) return rc;
     HIP_TRY(c, hipMemcpy(c->d_addrs, addrs.data(), addrs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (int e = launch_set_addresses(c->d_addrs, (uint32_t)addrs.size(), c->d_bitmap[c->cur_bitmap], c->bitmap_lg, c->scan_stream[0]))
         return fail(c, (hipError_t)e, "launch_set_addresses");
@@ -575,6 +586,19 @@ int submit(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, bo
     c->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - te0).count();
 #endif
     if (rc) return rc;
+    if (c->n_receivers) {
+        // whose buffers these are: the caller's map from this pass's first buffer on (a blocking call cut into passes
+        // hands it on piece by piece), or receiver 0 throughout for a plain call; and the receiver flushes asked for
+        // since the previous submission (within the capacity reserved by adsb_set_receivers: nothing is allocated)
+        if (c->rx_call_map) {
+            sl.rx_map.assign(c->rx_call_map, c->rx_call_map + n_chunks);
+            c->rx_call_map += n_chunks;
+        } else {
+            sl.rx_map.assign((size_t)n_chunks, 0u);
+        }
+        sl.rx_flush.clear();
+        sl.rx_flush.swap(c->rx_flush_next);
+    }
     sl.busy = true;
     c->submitted++;
     return ADSB_OK;
@@ -867,6 +891,54 @@ try {
 
 int adsb_submit_iq_device_u8(adsb_ctx *c, const void *d_iq, size_t n_samples)
 try {
+    return submit_device_entry(c, d_iq, n_samples, SrcFormat::kCu8);
+} ADSB_ABI_CATCH
+
+// ---- many receivers, one pass: the calls above with the receiver of every buffer (rx_check: the mode is on and the
+// whole map is valid, before anything is enqueued or any filter touched; RxCall: the passes of this call take it) ----
+int adsb_demod_iq_rx(adsb_ctx *c, const int16_t *iq, size_t n_samples, const uint32_t *receiver_of_buffer, adsb_msg *out,
+                     size_t cap, size_t *n_out)
+try {
+    if (int rc = rx_check(c, n_samples, receiver_of_buffer)) return rc;
+    RxCall call(c, receiver_of_buffer);
+    return demod_host(c, iq, n_samples, out, cap, n_out, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_demod_iq_rx_u8(adsb_ctx *c, const uint8_t *iq, size_t n_samples, const uint32_t *receiver_of_buffer, adsb_msg *out,
+                        size_t cap, size_t *n_out)
+try {
+    if (int rc = rx_check(c, n_samples, receiver_of_buffer)) return rc;
+    RxCall call(c, receiver_of_buffer);
+    return demod_host(c, iq, n_samples, out, cap, n_out, SrcFormat::kCu8);
+} ADSB_ABI_CATCH
+
+int adsb_demod_iq_device_rx(adsb_ctx *c, const void *d_iq, size_t n_samples, const uint32_t *receiver_of_buffer, adsb_msg *out,
+                            size_t cap, size_t *n_out)
+try {
+    if (int rc = rx_check(c, n_samples, receiver_of_buffer)) return rc;
+    RxCall call(c, receiver_of_buffer);
+    return demod_device_entry(c, d_iq, n_samples, out, cap, n_out, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_demod_iq_device_rx_u8(adsb_ctx *c, const void *d_iq, size_t n_samples, const uint32_t *receiver_of_buffer,
+                               adsb_msg *out, size_t cap, size_t *n_out)
+try {
+    if (int rc = rx_check(c, n_samples, receiver_of_buffer)) return rc;
+    RxCall call(c, receiver_of_buffer);
+    return demod_device_entry(c, d_iq, n_samples, out, cap, n_out, SrcFormat::kCu8);
+} ADSB_ABI_CATCH
+
+int adsb_submit_iq_device_rx(adsb_ctx *c, const void *d_iq, size_t n_samples, const uint32_t *receiver_of_buffer)
+try {
+    if (int rc = rx_check(c, n_samples, receiver_of_buffer)) return rc;
+    RxCall call(c, receiver_of_buffer);
+    return submit_device_entry(c, d_iq, n_samples, SrcFormat::kCs16);
+} ADSB_ABI_CATCH
+
+int adsb_submit_iq_device_rx_u8(adsb_ctx *c, const void *d_iq, size_t n_samples, const uint32_t *receiver_of_buffer)
+try {
+    if (int rc = rx_check(c, n_samples, receiver_of_buffer)) return rc;
+    RxCall call(c, receiver_of_buffer);
     return submit_device_entry(c, d_iq, n_samples, SrcFormat::kCu8);
 } ADSB_ABI_CATCH
 

@@ -434,6 +434,91 @@ void ParallelReplay::finish(IcaoFilter &filter, std::vector<adsb_msg> &out)
     apply_adds(filter);
 }
 
+bool ReceiverReplay::run(IcaoFilter *const *filters, const uint32_t *map, size_t n_map, const Crc24 &crc, const TrialRecord *rec, size_t n,
+                         uint64_t chunk_offset, std::vector<adsb_msg> &out, ReplayPool *pool, uint64_t *host_sorts, bool *gained,
+                         bool *pooled)
+{
+    if (gained) *gained = false;
+    if (pooled) *pooled = false;
+    // the records stay where they are (they may sit in mapped host memory); out of order, their indices are sorted
+    const bool sorted = replay_order(rec, n, order_);
+    const uint32_t *ord = sorted ? nullptr : order_.data();
+    auto at = [rec, ord](size_t i) -> const TrialRecord & { return rec[ord ? ord[i] : i]; };
+    // one run per buffer that left records, with the receiver it belongs to
+    runs_.clear();
+    bool several = false;
+    uint32_t top = 0;
+    for (size_t i = 0; i < n;) {
+        const uint32_t chunk = at(i).chunk;
+        if (chunk_offset + chunk >= n_map) return false;
+        size_t end = i + 1;
+        while (end < n && at(end).chunk == chunk) end++;
+        const uint32_t r = map[chunk_offset + chunk];
+        several = several || (!runs_.empty() && r != runs_[0].receiver);
+        top = std::max(top, r);
+        runs_.push_back({i, end, r, 0, 0, 0});
+        i = end;
+    }
+    if (!sorted && host_sorts) ++*host_sorts;
+    if (!pool || !several) {
+        // one walk in (buffer, j, try_phase) order, the filter switched at buffer boundaries
+        for (const Run &r : runs_) {
+            IcaoFilter &f = *filters[r.receiver];
+            const uint64_t before = f.inserts();
+            replay_in_order(f, crc, r.end - r.begin, chunk_offset, out,
+                            [&](size_t i) -> const TrialRecord & { return at(r.begin + i); }, NoPosition{});
+            if (gained && f.inserts() != before) *gained = true;
+        }
+        return true;
+    }
+    // a part per receiver present: its buffers, in order
+    part_of_.assign((size_t)top + 1, 0u);
+    size_t n_parts = 0;
+    for (size_t k = 0; k < runs_.size(); k++) {
+        Run &r = runs_[k];
+        if (!part_of_[r.receiver]) {
+            if (parts_.size() <= n_parts) parts_.resize(n_parts + 1);
+            Part &p = parts_[n_parts];
+            p.receiver = r.receiver;
+            p.runs.clear();
+            p.out.clear();
+            p.gained = false;
+            part_of_[r.receiver] = (uint32_t)++n_parts;
+        }
+        r.part = part_of_[r.receiver] - 1;
+        parts_[r.part].runs.push_back((uint32_t)k);
+    }
+    const std::function<void(int)> replay_part = [&](int i) {
+        Part &p = parts_[(size_t)i];
+        std::vector<adsb_msg> mine = std::move(p.out);   // (worked on in a local and handed back: see ParallelReplay::scan_part)
+        IcaoFilter &f = *filters[p.receiver];
+        const uint64_t before = f.inserts();
+        for (uint32_t k : p.runs) {
+            Run &r = runs_[k];
+            r.out_begin = mine.size();
+            replay_in_order(f, crc, r.end - r.begin, chunk_offset, mine,
+                            [&](size_t q) -> const TrialRecord & { return at(r.begin + q); }, NoPosition{});
+            r.out_end = mine.size();
+        }
+        p.gained = f.inserts() != before;
+        p.out = std::move(mine);
+    };
+    pool->run((int)n_parts, replay_part);
+    // the buffers' messages in buffer order
+    size_t total = 0;
+    for (size_t i = 0; i < n_parts; i++) {
+        total += parts_[i].out.size();
+        if (gained && parts_[i].gained) *gained = true;
+    }
+    out.reserve(out.size() + total);
+    for (const Run &r : runs_) {
+        const std::vector<adsb_msg> &from = parts_[r.part].out;
+        out.insert(out.end(), from.begin() + (std::ptrdiff_t)r.out_begin, from.begin() + (std::ptrdiff_t)r.out_end);
+    }
+    if (pooled) *pooled = true;
+    return true;
+}
+
 // mode_s/mod.rs:80-84 (DF11, IID 0) and :97-99 (DF17): the addresses the replay will add
 void learned_addresses(const Crc24 &crc, const TrialRecord *rec, size_t n, std::vector<uint32_t> &addrs)
 {
@@ -492,6 +577,38 @@ try {
     std::vector<adsb_msg> msgs;
     replay(filter, crc, reinterpret_cast<const TrialRecord *>(records), n, 0, msgs);
     filter.store(filter_table);
+    const size_t k = std::min(cap, msgs.size());
+    if (k) std::memcpy(out, msgs.data(), k * sizeof(adsb_msg));
+    if (n_out) *n_out = msgs.size();
+    return msgs.size() > cap ? ADSB_ERR_CAPACITY : ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_replay_records_rx(uint32_t *filter_tables, uint32_t n_receivers, const uint32_t *receiver_of_buffer, size_t n_buffers,
+                           adsb_trial *records, size_t n, int mode, int threads, adsb_msg *out, size_t cap, size_t *n_out)
+try {
+    if (!filter_tables || n_receivers == 0 || n_receivers > ADSB_MAX_RECEIVERS || (!receiver_of_buffer && n_buffers) ||
+        (!records && n) || (!out && cap))
+        return ADSB_ERR_INVALID;
+    if (mode != ADSB_FIX_NONE && mode != ADSB_FIX_1BIT && mode != ADSB_FIX_2BIT) return ADSB_ERR_INVALID;
+    for (size_t b = 0; b < n_buffers; b++)
+        if (receiver_of_buffer[b] >= n_receivers) return ADSB_ERR_INVALID;
+    const TrialRecord *rec = reinterpret_cast<const TrialRecord *>(records);
+    for (size_t i = 0; i < n; i++)
+        if (rec[i].chunk >= n_buffers) return ADSB_ERR_INVALID;   // (before any table is touched)
+    Crc24 crc;
+    crc.set_fix(mode);
+    std::vector<IcaoFilter> filters(n_receivers);
+    std::vector<IcaoFilter *> filter_of(n_receivers);
+    for (uint32_t r = 0; r < n_receivers; r++) {
+        filters[r].load(filter_tables + (size_t)r * IcaoFilter::kSize);
+        filter_of[r] = &filters[r];
+    }
+    std::unique_ptr<ReplayPool> pool;
+    if (threads > 1) pool.reset(new ReplayPool(std::min(threads, 64) - 1, {}, 0));
+    std::vector<adsb_msg> msgs;
+    ReceiverReplay rr;
+    if (!rr.run(filter_of.data(), receiver_of_buffer, n_buffers, crc, rec, n, 0, msgs, pool.get())) return ADSB_ERR_INVALID;
+    for (uint32_t r = 0; r < n_receivers; r++) filters[r].store(filter_tables + (size_t)r * IcaoFilter::kSize);
     const size_t k = std::min(cap, msgs.size());
     if (k) std::memcpy(out, msgs.data(), k * sizeof(adsb_msg));
     if (n_out) *n_out = msgs.size();

@@ -162,6 +162,21 @@ class ReplayPool {
         job->pr = &pr;
         job->stage = stage;
         job->parts = pr.parts();
+        run_job(job);
+    }
+    // ... the same for any work cut into `parts` independent parts (the per-receiver replay: a part is a receiver)
+    void run(int parts, const std::function<void(int)> &fn)
+    {
+        auto job = std::make_shared<Job>();
+        job->fn = &fn;
+        job->parts = parts;
+        run_job(job);
+    }
+
+  private:
+    struct Job;
+    void run_job(const std::shared_ptr<Job> &job)
+    {
         job->claimed.reset(new std::atomic<uint8_t>[(size_t)job->parts]);
         for (int i = 0; i < job->parts; i++) job->claimed[(size_t)i].store(0, std::memory_order_relaxed);
         {
@@ -176,11 +191,10 @@ class ReplayPool {
         // it happens and raised again here, on the caller's thread, whose callers turn it into a status)
         if (job->failed.load(std::memory_order_acquire)) throw std::bad_alloc();
     }
-
-  private:
     struct Job {
         ParallelReplay *pr = nullptr;
         void (ParallelReplay::*stage)(int) = nullptr;
+        const std::function<void(int)> *fn = nullptr;   // instead of pr / stage (it outlives the job: run() waits for every part)
         int parts = 0;
         std::unique_ptr<std::atomic<uint8_t>[]> claimed;
         std::atomic<int> done{0};
@@ -195,7 +209,8 @@ class ReplayPool {
         auto claim = [&](int i) {
             if (job.claimed[(size_t)i].exchange(1, std::memory_order_acq_rel)) return;
             try {
-                (job.pr->*job.stage)(i);
+                if (job.fn) (*job.fn)(i);
+                else (job.pr->*job.stage)(i);
             } catch (...) {
                 job.failed.store(true, std::memory_order_release);
             }
@@ -232,6 +247,41 @@ class ReplayPool {
     std::atomic<uint64_t> gen_{0};
     bool stop_ = false;
     std::shared_ptr<Job> job_;
+};
+
+// The ordered replay of a pass that holds the buffers of several receivers (include/adsb_hip.h, "Many receivers, one
+// pass"): buffer b belongs to receiver map[chunk_offset + b], and every record is scored against the filter of its
+// buffer's receiver.  A buffer belongs to one receiver, so walking the records once in (buffer, j, try_phase) order and
+// switching the filter at buffer boundaries replays every receiver's records in that receiver's own order, and the
+// messages come out in (buffer, j) order with no merge.  With a pool (and more than one receiver present) the
+// receivers are dealt to its threads instead: receivers never share a filter, so each replays its own buffers
+// serially and independently of the others, and the caller strings the buffers' messages together in buffer order.
+// The same messages and the same tables either way.  The scratch vectors are kept from pass to pass.
+class ReceiverReplay {
+  public:
+    // false: a record's buffer lies outside the map (nothing has been replayed then).  `filters`: one per receiver;
+    // every map entry is below their number (the caller has checked).  *gained: some filter took a new address.
+    bool run(IcaoFilter *const *filters, const uint32_t *map, size_t n_map, const Crc24 &crc, const TrialRecord *rec, size_t n,
+             uint64_t chunk_offset, std::vector<adsb_msg> &out, ReplayPool *pool, uint64_t *host_sorts = nullptr,
+             bool *gained = nullptr, bool *pooled = nullptr);
+
+  private:
+    struct Run {            // the records of one buffer, [begin, end) in replay order
+        size_t begin, end;
+        uint32_t receiver;
+        uint32_t part;      // pooled: which receiver's list it went to, and where its messages start and end there
+        size_t out_begin, out_end;
+    };
+    struct alignas(128) Part {
+        uint32_t receiver = 0;
+        std::vector<uint32_t> runs;
+        std::vector<adsb_msg> out;
+        bool gained = false;
+    };
+    std::vector<uint32_t> order_;
+    std::vector<Run> runs_;
+    std::vector<Part> parts_;
+    std::vector<uint32_t> part_of_;   // receiver -> part + 1 (0: none), only the entries of receivers present are touched
 };
 
 // The sorted union of several sorted, duplicate-free address lists (the shards' learned addresses), appended to

@@ -95,8 +95,8 @@ try {
     return rc;
 } ADSB_ABI_CATCH
 
-int adsb_ring_submit(adsb_ctx *c, size_t n_samples)
-try {
+static int ring_submit(adsb_ctx *c, size_t n_samples)
+{
     if (!c || !c->ring_samples || n_samples == 0 || n_samples > c->ring_samples) return ADSB_ERR_INVALID;
     if (c->slot[c->submitted % (uint64_t)c->n_slots].busy || c->slot[c->submitted % (uint64_t)c->n_slots].parked) return ADSB_ERR_BUSY;
     ADSB_ON_DEVICE(c);
@@ -137,6 +137,19 @@ try {
     const int rc = submit(c, r.d_iq, c->ring_fmt, n_samples, false, input_ready_now());
     c->input_on_stream = nullptr;
     return rc;
+}
+
+int adsb_ring_submit(adsb_ctx *c, size_t n_samples)
+try {
+    return ring_submit(c, n_samples);
+} ADSB_ABI_CATCH
+
+// ... the slot's buffers belonging to the receivers the map names (include/adsb_hip.h, "Many receivers, one pass")
+int adsb_ring_submit_rx(adsb_ctx *c, size_t n_samples, const uint32_t *receiver_of_buffer)
+try {
+    if (int rc = rx_check(c, n_samples, receiver_of_buffer)) return rc;
+    RxCall call(c, receiver_of_buffer);
+    return ring_submit(c, n_samples);
 } ADSB_ABI_CATCH
 
 int adsb_host_register(adsb_ctx *c, void *host_ptr, size_t bytes)

@@ -574,6 +574,7 @@ int adsb_shard_scan(adsb_ctx *c, const void *device_iq, size_t n_samples, uint32
                     size_t *n_addrs)
 try {
     if (!c || (!device_iq && n_samples) || (!addrs_out && cap)) return ADSB_ERR_INVALID;
+    if (c->n_receivers) return ADSB_ERR_INVALID;   // (a shard is a range of ONE stream: adsb_set_receivers)
     if (c->submitted != c->delivered || c->shard_active || c->shard[0].active) return ADSB_ERR_BUSY;
     if (n_addrs) *n_addrs = 0;
     if ((uintptr_t)device_iq % 16) return ADSB_ERR_INVALID;

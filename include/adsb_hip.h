@@ -28,7 +28,8 @@
  * from an empty filter is acceptable); an adsb_multi says so itself
  * (ADSB_ERR_POISONED) and restarts on adsb_multi_icao_flush.  One adsb_ctx per host thread / per GPU: the ICAO address filter
  * (process-global statics in the reference, src/icao_filter.rs:8-9) lives in the
- * context, so contexts are independent streams.  There is no CPU fallback:
+ * context, so contexts are independent streams (one context can also serve many receivers, each with a filter of
+ * its own: "Many receivers, one pass").  There is no CPU fallback:
  * adsb_create fails with ADSB_ERR_NO_DEVICE when no gfx950 device is usable.
  * The host side of the library is built for x86-64 Linux hosts (its spin loops are
  * the `pause` instruction; thread placement reads sysfs): the hosts MI355X boards sit in.
@@ -127,7 +128,8 @@ typedef struct {
  *            buffers add a pinned staging buffer of their size, the ring its slots.
  * Input denser than the lists are sized for (several times a busy airspace) is still
  * demodulated exactly, buffer by buffer through worst-case lists allocated on first use
- * (another 10 MB of device and 20 MB of pinned memory; stats.retries). */
+ * (another 10 MB of device and 20 MB of pinned memory; stats.retries).
+ * adsb_set_receivers(n) adds 16 KB of ordinary host memory per receiver beyond the first ("Many receivers, one pass"). */
 int adsb_create(adsb_ctx **out, int device, size_t max_chunks);
 void adsb_destroy(adsb_ctx *ctx);
 
@@ -394,6 +396,96 @@ int adsb_signal_bin(uint16_t m);
 ADSB_MUST_CHECK int adsb_signal_summary(const adsb_signal_stats *s, size_t n, adsb_signal_summary_t *out);
 /* Diagnostic: how many k_signal_stats launches this context has made (a pass with the mode off makes none). */
 uint64_t adsb_selftest_signal_launches(const adsb_ctx *ctx);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Many receivers, one pass -- opt-in, off by default; with the mode off nothing observable changes.
+ * One receiver produces 2.4 Msample/s: one 131072-sample buffer every 54.6 ms.  A host that gathers the IQ of many
+ * receivers (an aggregator fed by a few hundred SDRs, a batch job over many recordings) can fill a deep pass only with
+ * the buffers of all of them, and each receiver has an ICAO filter of its own.  adsb_set_receivers(ctx, n) gives the
+ * context n filters; the _rx calls below take, beside the IQ, a map that names the receiver of every buffer.
+ *
+ * The map.  receiver_of_buffer[b], b = 0 .. ceil(n_samples / 131072) - 1, is the receiver buffer b of the call belongs
+ * to, each < n.  The buffers of one receiver are consecutive buffers of THAT receiver's stream in ascending b, within a
+ * call and from call to call.  Only the last buffer of a call may be short.  The map is a plain host array, copied
+ * during the call: the caller may free it as soon as the call returns, also after a submit.  A blocking call longer
+ * than max_chunks buffers is cut into passes as always; the map is indexed by the buffer's index in the CALL.
+ *
+ * What comes back is what n independent plain contexts would return: feed receiver r's buffers, one adsb_demod_iq call
+ * per buffer, to a context r of its own; relabel every message's `chunk` with b; merge in ascending (chunk, j).  That
+ * merged list is the list the _rx call returns, field for field, signal_level bit for bit, and
+ * adsb_receiver_filter_table(r) equals context r's table A (4096 u32, src/icao_filter.rs:8) slot for slot.
+ * adsb_collect, adsb_fetch_messages, ADSB_ERR_CAPACITY, adsb_get_stats and adsb_fetch_signal_stats (one record per
+ * buffer) are shared with the plain calls and unchanged.
+ *
+ * How: the device does not know whose buffer it scans.  Every buffer starts from a zero lead-in, and the only state
+ * the device keeps across buffers is the address SUPERSET the address/parity trials are matched against -- with
+ * receivers on, the union of all receivers' addresses, which is a superset of each receiver's filter at every moment.
+ * A false superset hit costs one trial record that the host replay then scores -1; what differs is that replay, which
+ * scores every record against the filter of its buffer's receiver.  Passes are never scored on the device while
+ * receivers are on (adsb_host_replays counts every pass); a pass of several thousand records from more than one
+ * receiver is replayed by up to six more host threads, a receiver's buffers to one thread, created when the first such
+ * pass is collected and joined by adsb_destroy.
+ *
+ *   adsb_set_receivers(n)   n = 0: off (default).  ADSB_ERR_BUSY while passes are pending; ADSB_ERR_INVALID for
+ *                           n > ADSB_MAX_RECEIVERS and while carry-over is enabled (and adsb_set_carry_over(ctx, 1) is
+ *                           ADSB_ERR_INVALID while receivers are on: a buffer's lead-in would have to be the end of its
+ *                           own receiver's previous buffer).  Any change of n restarts every receiver from an empty
+ *                           filter, as adsb_icao_flush does.  Allocates (n - 1) x 16 KB of host memory for the
+ *                           filters, and room for a map of max_chunks entries per pass in flight.  Works on every
+ *                           context size.
+ *   adsb_get_receivers      n, or ADSB_ERR_INVALID for a null context.
+ *   with receivers on       the plain calls (adsb_demod_iq*, submit, the ring, adsb_demodulate2400) mean "every buffer
+ *                           is receiver 0": n = 1 is exactly the plain behaviour.  adsb_icao_flush empties EVERY
+ *                           receiver's filter.  adsb_shard_scan returns ADSB_ERR_INVALID; adsb_multi_* have no such
+ *                           mode.  Error correction (a repair consults the filter of the trial's own receiver), the CU8
+ *                           table, signal statistics, profiling, adsb_set_stream and adsb_host_register apply unchanged.
+ *   with receivers off      every _rx call, adsb_icao_flush_receiver and adsb_receiver_filter_table return
+ *                           ADSB_ERR_INVALID.
+ *   an invalid map          (null, or an entry >= n) is ADSB_ERR_INVALID with nothing enqueued and no filter touched.
+ *   adsb_icao_flush_receiver(r)  == icao_flush() for receiver r alone.  May be called with passes pending: it applies
+ *                           to the passes submitted after it, like adsb_icao_flush (it is recorded against the next
+ *                           submission and applied when that pass is collected, in front of its replay).  Host only:
+ *                           the device's superset is NOT cleared -- it stays a superset, r's old addresses cost a few
+ *                           records that score -1 until an adsb_icao_flush retires the superset.
+ *   adsb_receiver_filter_table(r)  table A of receiver r's filter, for inspection.  ADSB_ERR_BUSY while passes are in
+ *                           flight.
+ * Not offered: carry-over with receivers (the scan kernel would need a lead-in source per buffer), valid lengths per
+ * buffer, scoring on the device per receiver (a keyed filter set in the scoring kernels: the natural next step for
+ * busy batches), receivers in adsb_multi / the shard calls, and adsb_feed. */
+#define ADSB_MAX_RECEIVERS 16384
+int adsb_set_receivers(adsb_ctx *ctx, uint32_t n_receivers);
+int adsb_get_receivers(const adsb_ctx *ctx);
+int adsb_icao_flush_receiver(adsb_ctx *ctx, uint32_t receiver);
+int adsb_receiver_filter_table(const adsb_ctx *ctx, uint32_t receiver, uint32_t *out4096);
+/* adsb_demod_iq, adsb_demod_iq_device, adsb_submit_iq_device and their _u8 twins, with the map */
+int adsb_demod_iq_rx(adsb_ctx *ctx, const int16_t *iq_re_im, size_t n_samples, const uint32_t *receiver_of_buffer,
+                     adsb_msg *out, size_t cap, size_t *n_out);
+int adsb_demod_iq_device_rx(adsb_ctx *ctx, const void *device_iq_re_im, size_t n_samples,
+                            const uint32_t *receiver_of_buffer, adsb_msg *out, size_t cap, size_t *n_out);
+int adsb_submit_iq_device_rx(adsb_ctx *ctx, const void *device_iq_re_im, size_t n_samples,
+                             const uint32_t *receiver_of_buffer);
+int adsb_demod_iq_rx_u8(adsb_ctx *ctx, const uint8_t *iq_re_im, size_t n_samples, const uint32_t *receiver_of_buffer,
+                        adsb_msg *out, size_t cap, size_t *n_out);
+int adsb_demod_iq_device_rx_u8(adsb_ctx *ctx, const void *device_iq_re_im, size_t n_samples,
+                               const uint32_t *receiver_of_buffer, adsb_msg *out, size_t cap, size_t *n_out);
+int adsb_submit_iq_device_rx_u8(adsb_ctx *ctx, const void *device_iq_re_im, size_t n_samples,
+                                const uint32_t *receiver_of_buffer);
+/* adsb_ring_submit with the map of the slot's buffers (a ring of either format): the aggregator's loop -- one slot holds
+ * one buffer from each of up to max_chunks receivers */
+int adsb_ring_submit_rx(adsb_ctx *ctx, size_t n_samples, const uint32_t *receiver_of_buffer);
+/* Host only, no context: the ordered replay with one filter per receiver.  filter_tables: n_receivers x 4096 u32 (table A
+ * of receiver r at filter_tables + 4096 r), read and updated.  `records` in any order, chunk = buffer index
+ * (< n_buffers, the length of the map; ADSB_ERR_INVALID otherwise, as for a map entry >= n_receivers, with no table
+ * touched).  mode: ADSB_FIX_*.  threads <= 1: one walk over the records; threads > 1: the receivers dealt to that many
+ * threads.  The same messages and tables whatever `threads`. */
+int adsb_replay_records_rx(uint32_t *filter_tables, uint32_t n_receivers, const uint32_t *receiver_of_buffer, size_t n_buffers,
+                           adsb_trial *records, size_t n, int mode, int threads, adsb_msg *out, size_t cap, size_t *n_out);
+/* Test hooks (results never depend on them).  parallel_min: passes of at least this many trial records, with more than
+ * one receiver in them, are replayed by several host threads (0 = the default, 8192); ADSB_ERR_BUSY while passes are
+ * pending.  out4: [0] passes replayed per receiver, [1] of them by several threads, [2] times the device's superset was
+ * put back from the union of the receivers' filters (overflow fallback, rematch), [3] 0. */
+int adsb_selftest_rx_tune(adsb_ctx *ctx, uint32_t parallel_min);
+int adsb_selftest_rx_counters(const adsb_ctx *ctx, uint64_t *out4);
 
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167

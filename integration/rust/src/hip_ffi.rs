@@ -161,6 +161,21 @@ unsafe extern "C" {
     pub fn adsb_demod_iq_device_u8(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_submit_iq_device_u8(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize) -> c_int;
     pub fn adsb_selftest_u8_table(ctx: *mut AdsbCtx, out256: *mut i16) -> c_int;
+    // many receivers, one pass: one filter per receiver, the receiver of every buffer named by a map
+    pub fn adsb_set_receivers(ctx: *mut AdsbCtx, n_receivers: u32) -> c_int;
+    pub fn adsb_get_receivers(ctx: *const AdsbCtx) -> c_int;
+    pub fn adsb_icao_flush_receiver(ctx: *mut AdsbCtx, receiver: u32) -> c_int;
+    pub fn adsb_receiver_filter_table(ctx: *const AdsbCtx, receiver: u32, out4096: *mut u32) -> c_int;
+    pub fn adsb_demod_iq_rx(ctx: *mut AdsbCtx, iq_re_im: *const i16, n_samples: usize, receiver_of_buffer: *const u32, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_demod_iq_device_rx(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize, receiver_of_buffer: *const u32, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_submit_iq_device_rx(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize, receiver_of_buffer: *const u32) -> c_int;
+    pub fn adsb_demod_iq_rx_u8(ctx: *mut AdsbCtx, iq_re_im: *const u8, n_samples: usize, receiver_of_buffer: *const u32, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_demod_iq_device_rx_u8(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize, receiver_of_buffer: *const u32, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_submit_iq_device_rx_u8(ctx: *mut AdsbCtx, device_iq_re_im: *const c_void, n_samples: usize, receiver_of_buffer: *const u32) -> c_int;
+    pub fn adsb_ring_submit_rx(ctx: *mut AdsbCtx, n_samples: usize, receiver_of_buffer: *const u32) -> c_int;
+    pub fn adsb_replay_records_rx(filter_tables: *mut u32, n_receivers: u32, receiver_of_buffer: *const u32, n_buffers: usize, records: *mut AdsbTrial, n: usize, mode: c_int, threads: c_int, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_selftest_rx_tune(ctx: *mut AdsbCtx, parallel_min: u32) -> c_int;
+    pub fn adsb_selftest_rx_counters(ctx: *const AdsbCtx, out4: *mut u64) -> c_int;
     pub fn adsb_shard_scan(ctx: *mut AdsbCtx, device_iq: *const c_void, n_samples: usize, addrs_out: *mut u32, cap: usize, n_addrs: *mut usize) -> c_int;
     pub fn adsb_shard_finish(ctx: *mut AdsbCtx, extra_addrs: *const u32, n_extra: usize, records_out: *mut AdsbTrial, cap: usize, n_records: *mut usize) -> c_int;
     pub fn adsb_multi_create(out: *mut *mut AdsbMulti, devices: *const c_int, n_devices: c_int, max_chunks_per_device: usize) -> c_int;
