@@ -179,6 +179,88 @@ __global__ __launch_bounds__(256) void k_match(ScanParams p)
     }
 }
 
+// The match of a sparse stream's three-launch pass in a large context (no order_cnt, fast scan: the dap list is empty).
+// What k_match pays per block before it looks at its pair's ~2.5 entries per thread is a dependent chain -- table loads,
+// barrier, fill counts, entries, bitmap -- in a kernel that is all latency.  Here the fill counts come first, a block
+// whose segments are empty leaves at once (small passes use a fraction of the segments), and the first trip's entries are
+// in flight before the tables are staged, so the barrier waits for the longer of the two, not for both in turn.
+// K segment pairs per block, consecutive ones: the next pair's entries are loaded before this pair's are looked at, and
+// the staging is shared by K times as many entries -- measured, K = 2 and 4 are slower alone (9.0 and 12.2 us against 7.1)
+// and beside a scan (31 us against 27): many short blocks beat few long ones here too.  The kernel asks for no issue
+// priority: with it, it and the records kernel run in 16 us each beside a scan and the step gets 3 % longer.
+// (ADSB_MATCH_PAIRS: K, 0 = k_match for these passes too; the A/B is in profiles/README.md: tail_rate.jsonl.)
+#ifndef ADSB_MATCH_PAIRS
+#define ADSB_MATCH_PAIRS 1
+#endif
+template <int K>
+__global__ __launch_bounds__(256) void k_match_sparse(ScanParams p, uint32_t n_pairs)
+{
+    __shared__ uint32_t stab[3 * 256];
+    __shared__ uint32_t coarse[kCoarseWords];
+    const uint32_t seg_cap = p.seg_cap, tid = threadIdx.x;
+    const uint32_t pair0 = blockIdx.x * (uint32_t)K;
+    uint32_t n[K][2], any = 0;
+#pragma unroll
+    for (int q = 0; q < K; q++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            n[q][h] = pair0 + q < n_pairs ? min(p.ctr->seg_ap[2 * (pair0 + q) + h], seg_cap) : 0u;
+            any |= n[q][h];
+        }
+    if (!any) return;  // (uniform: every thread read the same counts)
+    // entries [base, base + 512) of both segments of pair q: k = 0,1 from the first, 2,3 from the second
+    auto fetch = [&](const uint32_t (&cnt)[2], uint32_t pair, uint32_t base, uint64_t (&e)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t i = base + tid + (uint32_t)(k & 1) * 256u;
+            e[k] = i < cnt[k >> 1] ? p.ap[(uint64_t)(2 * pair + (k >> 1)) * seg_cap + i] : ~0ull;
+        }
+    };
+    auto look = [&](const uint64_t (&e)[4]) {
+        uint32_t c[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t code = entry_code(e[k]);
+            c[k] = entry_value(e[k]);
+            if (code >= 5 && code < 10) c[k] = gf_apply(stab, c[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (e[k] == ~0ull || !((coarse[(c[k] & 4095u) >> 5] >> (c[k] & 31)) & 1u)) continue;
+            const uint32_t at = bitmap_index(c[k], p.bitmap_lg);
+            if ((p.bitmap[at >> 5] >> (at & 31)) & 1u) {  // rare: one atomic each
+                const uint32_t idx = atomicAdd(&p.ctr->n_hits, 1u);
+                if (idx < p.hits_cap) {
+                    p.hits[idx] = e[k];
+                    if (p.hit_fields) p.hit_fields[(size_t)idx * kHitFieldWords + 5] = 0u;
+                } else {
+                    atomicOr(&p.ctr->overflow, 1u);
+                }
+            }
+        }
+    };
+    uint64_t e[4];
+    fetch(n[0], pair0, 0u, e);
+    for (uint32_t i = tid; i < 3 * 256; i += 256) stab[i] = p.tables[kTabX56 * 256 + i];
+    if (tid < kCoarseWords) coarse[tid] = p.bitmap[bitmap_words(p.bitmap_lg) + tid];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < K; q++) {
+        uint64_t nx[4];
+        if (q + 1 < K) fetch(n[q + 1 < K ? q + 1 : q], pair0 + q + 1, 0u, nx);
+        look(e);
+        const uint32_t nmax = max(n[q][0], n[q][1]);
+        for (uint32_t base = 512u; base < nmax; base += 512u) {  // (rare: the usual pair is a single trip)
+            uint64_t f[4];
+            fetch(n[q], pair0 + q, base, f);
+            look(f);
+        }
+        if (q + 1 < K)
+#pragma unroll
+            for (int k = 0; k < 4; k++) e[k] = nx[k];
+    }
+}
+
 // ---------------------------------------------------------------------------
 // order.  The hit list is filled in whatever order workgroups finish; the host replay needs
 // (buffer, j, try_phase) order (demodulate2400 walks j upwards and tries phases 4..8 at each,
@@ -647,9 +729,19 @@ int launch_reset(Counters *ctr, uint32_t *bitmap, uint32_t bitmap_lg, void *stre
     return hip_ok(hipGetLastError());
 }
 
-int launch_match(const ScanParams &p, void *stream)
+int launch_match(const ScanParams &p, void *stream, bool sparse_fast)
 {
     hip_clear();
+    if (sparse_fast && ADSB_MATCH_PAIRS && !p.order_cnt) {
+        // the segments this pass's scan can have filled: four per workgroup of its grid (adsb_scan_fast.hip: launch_scan)
+        const uint32_t tiles = p.n_chunks * (uint32_t)fastgeo::kTilesPerChunk;
+        const uint32_t n_pairs = 2u * std::min(tiles, (uint32_t)scan_resident_blocks());
+        constexpr uint32_t K = ADSB_MATCH_PAIRS ? ADSB_MATCH_PAIRS : 1;
+        static_assert(K <= 8, "the fill counts of a block's pairs are held in registers");
+        if (n_pairs == 0) return 0;
+        hipLaunchKernelGGL((k_match_sparse<(int)K>), dim3((n_pairs + K - 1) / K), dim3(256), 0, (hipStream_t)stream, p, n_pairs);
+        return hip_ok(hipGetLastError());
+    }
     // one block per two wave segments of the fast scan's AP list, 64 for the dap list; the fill
     // counts live on the device
     const uint32_t blocks = kApWaveSegs / 2 + 64;  // 64 blocks share the dap list
@@ -657,7 +749,13 @@ int launch_match(const ScanParams &p, void *stream)
     return hip_ok(hipGetLastError());
 }
 
-int launch_records(const ScanParams &p, SrcFormat fmt, TrialRecord *d_rec, void *stream)
+// Blocks of the records kernel behind a sparse stream's match (no order_cnt): a few hundred hits, whatever the pass's
+// size.  (ADSB_REC_SPARSE_BLOCKS: 0 = a block per buffer there too.)
+#ifndef ADSB_REC_SPARSE_BLOCKS
+#define ADSB_REC_SPARSE_BLOCKS 72
+#endif
+
+int launch_records(const ScanParams &p, SrcFormat fmt, TrialRecord *d_rec, void *stream, bool sparse_fast)
 {
     hip_clear();
     // Contiguous runs of hits per block (the count lives on the device); on sparse input most
@@ -672,6 +770,12 @@ int launch_records(const ScanParams &p, SrcFormat fmt, TrialRecord *d_rec, void 
     // profiles/r5_multi_overhead.txt; beyond 1024 blocks the runs per block simply get longer)
     uint32_t blocks = p.n_chunks + 8u;
     if (blocks > 1024) blocks = 1024;
+    // A sparse stream's pass (host-ordered, CS16): its hit list is bounded by hits_cap and holds a few hundred entries in
+    // practice, so a block per buffer is 500 blocks that find nothing and still take their turn at the one counter behind
+    // the last-block ticket.  A small fixed grid instead, whatever the pass's size: the runs per block get longer (at 2000
+    // hits: 28, less than one batch), the retired bitmap's clear is 7 x 16 bytes per thread instead of one.  Alone the
+    // kernel takes 11.3 us instead of 15.0, beside a scan 43 instead of 52; 32, 144 and 256 blocks measured no better.
+    if (sparse_fast && ADSB_REC_SPARSE_BLOCKS && !p.order_cnt && fmt == SrcFormat::kCs16) blocks = ADSB_REC_SPARSE_BLOCKS;
     if (fmt == SrcFormat::kCu8) {
         if (!p.u8_table) return (int)hipErrorInvalidValue;
         if (p.order_cnt)

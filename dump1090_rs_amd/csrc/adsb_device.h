@@ -323,8 +323,10 @@ int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream);   // fast (IQ
 int launch_pass_fused(const ScanParams &p, SrcFormat fmt, void *stream);
 int scan_resident_blocks();  // workgroups of the fast scan's persistent grid (<= kApSegments)
 int launch_scan_simple(const ScanParams &p, SrcFormat fmt, void *stream);  // reference-shaped path (not CU8: launch_widen_u8 first)
-int launch_match(const ScanParams &p, void *stream);
-int launch_records(const ScanParams &p, SrcFormat fmt, TrialRecord *d_rec, void *stream);
+// sparse_fast: the pass is a large context's host-ordered three-launch pass behind the fast scan (adsb_pass.cpp:
+// enqueue_tail) -- its match is k_match_sparse and its records kernel a small fixed grid; every other caller's stay as they are
+int launch_match(const ScanParams &p, void *stream, bool sparse_fast = false);
+int launch_records(const ScanParams &p, SrcFormat fmt, TrialRecord *d_rec, void *stream, bool sparse_fast = false);
 // sort the hit list by (buffer, j, try_phase) on the device, so that the records come out in the
 // order the host replays them in (src/demod_2400.rs:121,158: ascending j, then try_phase)
 int launch_order_hits(const ScanParams &p, void *stream);

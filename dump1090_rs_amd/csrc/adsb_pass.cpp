@@ -406,10 +406,12 @@ static int enqueue_tail(adsb_ctx *c, Slot &sl, const ScanParams &p, SrcFormat fm
     c->prev_inline = pl.inline_tail;
     c->prev_fused = false;
     if (pl.prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[2], ts));
+    // a sparse stream's pass in a large context: the lean match and the small records grid (adsb_aux.hip)
+    const bool sparse_fast = pl.fast && !pl.ordered && c->bitmap_lg == kFullBitmapLg;
     {
         HT(c, HT_MATCH_LAUNCH);
         if (!knob_skip_match())
-            if (int e = launch_match(p, ts)) return fail(c, (hipError_t)e, "launch_match");
+            if (int e = launch_match(p, ts, sparse_fast)) return fail(c, (hipError_t)e, "launch_match");
         if (int e = launch_order_hits(p, ts)) return fail(c, (hipError_t)e, "launch_order_hits");
     }
     if (pl.prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[3], ts));
@@ -417,7 +419,7 @@ static int enqueue_tail(adsb_ctx *c, Slot &sl, const ScanParams &p, SrcFormat fm
     // memory with write-through stores; `done` only has to say the kernel has drained
     {
         HT(c, HT_RECORDS_LAUNCH);
-        if (int e = launch_records(p, fmt, sl.h_rec_dev, ts)) return fail(c, (hipError_t)e, "launch_records");
+        if (int e = launch_records(p, fmt, sl.h_rec_dev, ts, sparse_fast)) return fail(c, (hipError_t)e, "launch_records");
     }
     sl.tail_q = ts;
     // (always: a later pass whose own tail runs on another stream -- a small one behind an icao_flush --
