@@ -276,6 +276,16 @@ def lib() -> C.CDLL:
     L.adsb_replay_records_rx.argtypes = [vp, u32, vp, sz, vp, sz, C.c_int, C.c_int, vp, sz, C.POINTER(sz)]
     L.adsb_selftest_rx_tune.argtypes = [vp, u32]
     L.adsb_selftest_rx_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.adsb_set_receiver_scoring.argtypes = [vp, C.c_int]
+    L.adsb_get_receiver_scoring.argtypes = [vp]
+    L.adsb_selftest_rx_score_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.adsb_selftest_rx_score_tune.argtypes = [vp, u32, u32]
+    L.adsb_selftest_rx_set_lookup.argtypes = [vp, vp, sz, vp, sz, vp]
+    L.adsb_rx_set_home.argtypes = [C.c_uint64, u32]
+    L.adsb_rx_set_home.restype = u32
+    for name in ("adsb_set_receiver_scoring", "adsb_get_receiver_scoring", "adsb_selftest_rx_score_counters",
+                 "adsb_selftest_rx_score_tune", "adsb_selftest_rx_set_lookup"):
+        getattr(L, name).restype = C.c_int
     for name in ("adsb_set_receivers", "adsb_get_receivers", "adsb_icao_flush_receiver", "adsb_receiver_filter_table",
                  "adsb_demod_iq_rx", "adsb_demod_iq_device_rx", "adsb_demod_iq_rx_u8", "adsb_demod_iq_device_rx_u8",
                  "adsb_submit_iq_device_rx", "adsb_submit_iq_device_rx_u8", "adsb_ring_submit_rx", "adsb_replay_records_rx",

@@ -140,6 +140,12 @@ def _as_map(receivers, n_samples: Optional[int] = None) -> np.ndarray:
     return m
 
 
+def rx_set_home(key: int, set_lg: int) -> int:
+    """adsb_rx_set_home (host only): the slot the probes of key = receiver << 24 | value start at in a keyed set of
+    2^set_lg slots."""
+    return int(_lib.lib().adsb_rx_set_home(int(key), int(set_lg)))
+
+
 def replay_records_rx(records: np.ndarray, receivers, filter_tables: np.ndarray, mode: int = 0, threads: int = 1,
                       cap: Optional[int] = None) -> List["ModeSMessage"]:
     """adsb_replay_records_rx: the ordered host replay with one filter per receiver.  `receivers[b]` is the receiver of
@@ -499,6 +505,32 @@ class Context:
     def ring_submit_rx(self, n_samples: int, receivers) -> None:
         m = _as_map(receivers, n_samples)
         self._check(self._L.adsb_ring_submit_rx(self._h, n_samples, m.ctypes.data), "adsb_ring_submit_rx")
+
+    def set_receiver_scoring(self, enabled: bool) -> None:
+        """adsb_set_receiver_scoring: dense passes of a receivers context are scored on the device, a filter per receiver."""
+        self._check(self._L.adsb_set_receiver_scoring(self._h, 1 if enabled else 0), "adsb_set_receiver_scoring")
+
+    def get_receiver_scoring(self) -> bool:
+        return int(self._L.adsb_get_receiver_scoring(self._h)) == 1
+
+    def selftest_rx_score_counters(self) -> dict:
+        """adsb_selftest_rx_score_counters: device results taken / scored passes the host replayed all the same / rebuilds
+        of the keyed set / passes in which an insertion ran out of probes."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.adsb_selftest_rx_score_counters(self._h, out), "adsb_selftest_rx_score_counters")
+        return {"taken": int(out[0]), "refused": int(out[1]), "rebuilds": int(out[2]), "no_room": int(out[3])}
+
+    def selftest_rx_score_tune(self, set_lg: int = 0, probe_max: int = 0) -> None:
+        self._check(self._L.adsb_selftest_rx_score_tune(self._h, int(set_lg), int(probe_max)), "adsb_selftest_rx_score_tune")
+
+    def selftest_rx_set_lookup(self, keys, queries):
+        """adsb_selftest_rx_set_lookup: (found[len(queries)] as a bool array, insertions that ran out of probes)."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        q = np.ascontiguousarray(queries, dtype=np.uint64)
+        out = np.zeros(q.shape[0] + 1, dtype=np.uint32)
+        self._check(self._L.adsb_selftest_rx_set_lookup(self._h, k.ctypes.data, k.shape[0], q.ctypes.data, q.shape[0], out.ctypes.data),
+                    "adsb_selftest_rx_set_lookup")
+        return out[:-1].astype(bool), int(out[-1])
 
     def selftest_rx_tune(self, parallel_min: int = 0) -> None:
         self._check(self._L.adsb_selftest_rx_tune(self._h, int(parallel_min)), "adsb_selftest_rx_tune")

@@ -7,6 +7,7 @@
 #include "adsb_scan_geometry.h"
 #include "adsb_tail_dev.h"
 #include "adsb_fix_dev.h"
+#include "adsb_score_dev.h"
 
 namespace adsb {
 
@@ -336,54 +337,11 @@ __device__ __forceinline__ bool score_in_filter(const ScoreDev &sd, uint32_t v, 
     return score_hash_first(sd, v) < i;
 }
 
-// A trial the record builder left unclassified (kSkOther) in a pass that repairs (ScanParams::fix, include/adsb_hip.h:
-// adsb_set_error_correction): a DF17/18 whose residual c -- bits 40..63 of its record's `power` -- names one flipped bit,
-// or (mode 3) two, scores 1200 / 1100 when the REPAIRED address is in the filter at that moment (DF18 too, with the
-// plain address), else -1; it adds nothing and is no adder in the hash.  `damaged`: the address field as sliced.
-// Everything else stays -2.  Only such trials come here: the common kinds never see the lookup.
-// *repair: the bits found, a | b << 8 (k_emit flips them; it gets them through ScoreDev::flag and looks nothing up).
-__device__ __forceinline__ int score_repair(const ScoreDev &sd, uint32_t i, uint32_t damaged, const uint32_t *tables, uint32_t fix,
-                                            uint32_t *repair)
-{
-    const TrialRecord &r = sd.rec[i];
-    const uint32_t df = (uint32_t)r.msg[0] >> 3;
-    if (df != 17u && df != 18u) return -2;
-    const uint32_t ab = fix_lookup(tables, (uint32_t)(r.power >> 40), fix);
-    if (ab == kFixNoRepair) return -2;
-    *repair = ab;
-    const uint32_t a = ab & 0xFFu, b = ab >> 8;
-    const uint32_t addr = damaged ^ fix_addr_mask(a) ^ fix_addr_mask(b);
-    if (!score_in_filter(sd, addr, i)) return -1;
-    return a == kFixNoBit ? ADSB_SCORE_FIXED_1BIT : ADSB_SCORE_FIXED_2BIT;
-}
-
-// src/mode_s/mod.rs:56-135 for trial i; *adds: the value this trial hands to icao_filter_add (or 0)
-__device__ __forceinline__ int score_trial(const ScoreDev &sd, uint32_t i, uint32_t *adds, const uint32_t *tables, uint32_t fix,
-                                           uint32_t *repair)
-{
-    const uint32_t w = sd.si[i], v = w & 0xFFFFFFu, kind = w >> 24;
-    *adds = 0;
-    switch (kind) {
-    case kSkApShort: return score_in_filter(sd, v, i) ? 1000 : -1;
-    case kSkApLong: return score_in_filter(sd, v, i) ? 1000 : -2;
-    case kSkDf11: return score_in_filter(sd, v, i) ? 1000 : -1;
-    case kSkDf11Iid0:
-        if (score_in_filter(sd, v, i)) return 1600;
-        *adds = v;
-        return 750;
-    case kSkDf17:
-        if (score_in_filter(sd, v, i)) return 1800;
-        *adds = v;
-        return 1400;
-    case kSkDf18:
-        if (score_in_filter(sd, v, i)) return 1800;
-        *adds = v | (1u << 25);                       // ICAO_FILTER_ADSB_NT, src/icao_filter.rs:6
-        return 1400;
-    case kSkNone: return -3;                          // the reference's None: never taken
-    case kSkOther: return fix ? score_repair(sd, i, v, tables, fix, repair) : -2;
-    default: return -2;
-    }
-}
+// the one filter of a plain pass, as the shared scoring of a trial asks for it (adsb_score_dev.h: score_trial)
+struct PlainFilter {
+    const ScoreDev &sd;
+    __device__ __forceinline__ bool operator()(uint32_t v, uint32_t i) const { return score_in_filter(sd, v, i); }
+};
 
 
 // k_score: one thread per hit.  Its own score, whether it is the one its (buffer, j) emits
@@ -395,6 +353,7 @@ __global__ __launch_bounds__(256) void k_score(ScanParams p)
     const uint32_t n = sd.state->n;
     const uint32_t per = (n + gridDim.x - 1) / gridDim.x;
     const uint32_t first = blockIdx.x * per, last = min(n, first + per);
+    const PlainFilter in_filter{sd};
     uint32_t emits = 0, addc = 0;
     for (uint32_t i = first + threadIdx.x; i < last; i += blockDim.x) {
         const uint64_t pos = sd.pos[i];
@@ -404,7 +363,7 @@ __global__ __launch_bounds__(256) void k_score(ScanParams p)
         uint32_t win = 0xFFFFFFFFu, my_add = 0, my_fix = kFixNoRepair;
         for (uint32_t k = g0; k < n && k < g0 + 16 && sd.pos[k] == pos; k++) {
             uint32_t a, fx = kFixNoRepair;
-            const int s = score_trial(sd, k, &a, p.tables, p.fix, &fx);
+            const int s = score_trial(sd, k, &a, p.tables, p.fix, &fx, in_filter);
             if (k == i) {
                 mine = s;
                 my_add = a;

@@ -39,6 +39,66 @@ bool take_device_result(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vecto
     return true;
 }
 
+// The same for a pass of several receivers scored by the keyed kernels (adsb_score_rx.hip): the additions come as (value,
+// receiver) pairs, and the guard holds for EVERY receiver that has an addition in the pass -- held[r] + adds[r] + 64 < 4096,
+// with held[r] kept from pass to pass and counted afresh whenever the host has touched the filters itself.
+bool take_device_result_rx(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vector<adsb_msg> &out)
+{
+    if (!sl.rx_scored || sl.score_epoch != c->score_epoch) return false;
+    const ScoreSummary *ss = sl.h_ssum;
+    if (__atomic_load_n(&ss->seq, __ATOMIC_ACQUIRE) != sl.seq) return false;
+    if (ss->no_room) c->rx_no_room++;
+    if (!ss->scored) return false;
+    const size_t nm = ss->n_msgs, na = ss->n_adds;
+    if (nm > c->score.cap || na > c->score.cap) return false;
+    if (!c->rx_held_valid) {
+        c->rx_held.assign(c->n_receivers, 0u);
+        c->rx_pass_adds.assign(c->n_receivers, 0u);
+        for (uint32_t r = 0; r < c->n_receivers; r++)
+            for (uint32_t a : c->rx_filter_of[r]->table()) c->rx_held[r] += a != 0;
+        c->rx_held_valid = true;
+    }
+    bool room = true;
+    c->rx_touched.clear();
+    for (size_t i = 0; i < na && room; i++) {
+        const uint32_t r = sl.h_add_rx[i];
+        if (r >= c->n_receivers) room = false;   // (not a receiver: not this pass's whole result)
+        else if (c->rx_pass_adds[r]++ == 0) c->rx_touched.push_back(r);
+    }
+    for (uint32_t r : c->rx_touched) {
+        room = room && (size_t)c->rx_held[r] + c->rx_pass_adds[r] + 64 < IcaoFilter::kSize;
+        c->rx_pass_adds[r] = 0;
+    }
+    if (!room) return false;
+    const uint64_t want = (uint64_t)ss->msg_sum_hi << 32 | ss->msg_sum_lo;
+    bool whole = false;
+    for (int attempt = 0; attempt < 200 && !whole; attempt++) {
+        uint64_t got = 0;
+        const uint64_t *w = reinterpret_cast<const uint64_t *>(sl.h_msgs);
+        for (size_t i = 0; i < 5 * nm; i++) got += __atomic_load_n(&w[i], __ATOMIC_RELAXED);
+        whole = got == want;
+    }
+    if (!whole) return false;
+    const size_t at = out.size();
+    out.insert(out.end(), sl.h_msgs, sl.h_msgs + nm);
+    if (chunk_offset)
+        for (size_t i = at; i < out.size(); i++) out[i].chunk += chunk_offset;
+    bool gained = false;
+    for (size_t i = 0; i < na; i++) {
+        const uint32_t r = sl.h_add_rx[i];
+        IcaoFilter &f = *c->rx_filter_of[r];
+        const uint64_t before = f.inserts();
+        f.add(sl.h_adds[i]);
+        if (f.inserts() != before) {
+            c->rx_held[r]++;
+            gained = true;
+        }
+    }
+    if (gained) c->last_new_insert_seq = sl.scan_seq;
+    c->rx_scored_taken++;
+    return true;
+}
+
 // The ordered replay of a pass whose buffers belong to several receivers (adsb_set_receivers): every record against the
 // filter of the receiver of its buffer, sl.rx_map[chunk_offset + chunk] (chunk_offset: the buffer the overflow fallback
 // is at).  A pass of at least rx_parallel_min records with more than one receiver in it is dealt, receiver by receiver,
@@ -78,6 +138,7 @@ void flush_host_filters(adsb_ctx *c)
 {
     c->filter.flush();
     for (IcaoFilter &f : c->rx_filters) f.flush();
+    std::fill(c->rx_held.begin(), c->rx_held.end(), 0u);   // (take_device_result_rx's counts, while they are valid: all empty)
 }
 
 // The records and the summary travel to host memory as separate posted writes; the summary's
@@ -250,7 +311,8 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
         if (n >= 8u * (size_t)sl.n_chunks) c->dense_mode = true;
         else if (n < 2u * (size_t)sl.n_chunks) c->dense_mode = false;
     }
-    if (take_device_result(c, sl, chunk_offset, out)) return 0;
+    if (sl.rx_scored ? take_device_result_rx(c, sl, chunk_offset, out) : take_device_result(c, sl, chunk_offset, out)) return 0;
+    if (sl.rx_scored) c->rx_scored_refused++;
     if (rec_on_device && n) {
         HIP_TRY(c, hipMemcpy(sl.h_rec, sl.score.rec, n * sizeof(TrialRecord), hipMemcpyDeviceToHost));
         if (int rc = verify_records(c, sl.h_sum, sl.h_rec, n)) return rc;
@@ -258,6 +320,7 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
     c->host_replays++;
     c->score_epoch++;        // passes in flight were scored on the device without what this replay adds
     c->exact_valid = false;
+    c->rx_set_valid = c->rx_held_valid = false;
     static const bool skip_replay = tuning_env("ADSB_SKIP_REPLAY") != nullptr;  // measurement aid (tuning build only)
 #ifdef ADSB_TUNING
     const auto tr0 = std::chrono::steady_clock::now();
@@ -294,7 +357,10 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
     if (sl.flush_before) flush_host_filters(c);  // icao_flush() took effect before this pass
     // ... and so did the adsb_icao_flush_receiver calls recorded against it (host only: the device's superset stays one)
     for (uint32_t r : sl.rx_flush)
-        if (r < c->rx_filter_of.size()) c->rx_filter_of[r]->flush();
+        if (r < c->rx_filter_of.size()) {
+            c->rx_filter_of[r]->flush();
+            if (r < c->rx_held.size()) c->rx_held[r] = 0;
+        }
     sl.rx_flush.clear();
     int rc = finish_pass(c, sl, 0, st, out);
     if (rc == 2) {

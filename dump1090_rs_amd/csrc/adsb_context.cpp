@@ -374,6 +374,63 @@ int ensure_signal_stats(adsb_ctx *c)
     return ADSB_OK;
 }
 
+// Receivers scored on the device (adsb_set_receiver_scoring): per pass in flight a device copy of the map with its pinned
+// staging, a keyed first-adder table the size of the slot's plain one, the keyed slot of every hit, and the receiver of
+// every addition in mapped host memory; per context two keyed sets of 8 << rx_set_lg_for(n_receivers) bytes.  Reserved the
+// first time the mode is on together with receivers, in a context that scores on the device at all; the sets are
+// re-made when the number of receivers changes.  Nothing may be in flight.
+uint32_t rx_set_lg_for(uint32_t n_receivers)
+{
+    uint32_t lg = kRxSetLgMin;   // 2 x 4096 slots for one receiver
+    while (lg < kRxSetLgMax && (1ull << lg) < 2ull * IcaoFilter::kSize * std::max(1u, n_receivers)) lg++;
+    return lg;
+}
+
+int ensure_rx_scoring(adsb_ctx *c)
+{
+    if (!c->score.si || !c->n_receivers) return ADSB_OK;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t hsize = (size_t)c->score.hash_mask + 1, map_bytes = up(c->max_chunks * sizeof(uint32_t)),
+                 per_slot = map_bytes + up((size_t)c->score.cap * sizeof(uint32_t));
+    if (!c->h_rx_block) {
+        char *h_dev = nullptr;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_rx_block, per_slot * (size_t)c->n_slots, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(c, hipHostGetDevicePointer((void **)&h_dev, c->h_rx_block, 0));
+        uint32_t first_lg = 0;
+        while (((size_t)1 << first_lg) < hsize) first_lg++;
+        for (int si = 0; si < c->n_slots; si++) {
+            Slot &sl = c->slot[si];
+            sl.h_rx_map = reinterpret_cast<uint32_t *>(c->h_rx_block + per_slot * (size_t)si);
+            sl.h_add_rx = reinterpret_cast<uint32_t *>(c->h_rx_block + per_slot * (size_t)si + map_bytes);
+            sl.h_add_rx_dev = reinterpret_cast<uint32_t *>(h_dev + per_slot * (size_t)si + map_bytes);
+            if (!sl.d_rx_map) HIP_TRY(c, hipMalloc((void **)&sl.d_rx_map, c->max_chunks * sizeof(uint32_t)));
+            if (!sl.d_rx_slot) HIP_TRY(c, hipMalloc((void **)&sl.d_rx_slot, (size_t)c->score.cap * sizeof(uint32_t)));
+            if (!sl.d_rx_first) HIP_TRY(c, hipMalloc((void **)&sl.d_rx_first, hsize * sizeof(unsigned long long)));
+            HIP_TRY(c, hipMemset(sl.d_rx_first, 0xFF, hsize * sizeof(unsigned long long)));
+            sl.rx = RxScoreDev{};
+            sl.rx.rx_map = sl.d_rx_map;
+            sl.rx.first = sl.d_rx_first;
+            sl.rx.first_lg = first_lg;
+            sl.rx.rx_slot = sl.d_rx_slot;
+            sl.rx.out_add_rx = sl.h_add_rx_dev;
+        }
+    }
+    if (!c->d_rx_failed) HIP_TRY(c, hipMalloc((void **)&c->d_rx_failed, sizeof(uint32_t)));
+    const uint32_t want_lg = rx_set_lg_for(c->n_receivers);
+    if (!c->rx_set[0] || !c->rx_set[1] || want_lg != c->rx_set_alloc_lg) {
+        for (auto &st : c->rx_set) {
+            if (st) (void)hipFree(st);
+            st = nullptr;
+        }
+        c->rx_set_alloc_lg = 0;
+        for (auto &st : c->rx_set) HIP_TRY(c, hipMalloc((void **)&st, sizeof(unsigned long long) << want_lg));
+        c->rx_set_alloc_lg = want_lg;
+        c->cur_rx_set = 0;
+    }
+    c->rx_set_valid = false;   // (the next scored pass fills them)
+    return ADSB_OK;
+}
+
 }  // namespace host
 }  // namespace adsb
 
@@ -434,6 +491,15 @@ void adsb_destroy(adsb_ctx *c)
     if (c->h_block) (void)hipHostFree(c->h_block);
     if (c->h_sig_block) (void)hipHostFree(c->h_sig_block);
     if (c->d_sig_block) (void)hipFree(c->d_sig_block);
+    if (c->score_stream) (void)hipStreamSynchronize(c->score_stream);
+    for (Slot &sl : c->slot)
+        for (void *q : {(void *)sl.d_rx_map, (void *)sl.d_rx_slot, (void *)sl.d_rx_first})
+            if (q) (void)hipFree(q);
+    for (auto *st : c->rx_set)
+        if (st) (void)hipFree(st);
+    if (c->d_rx_keys) (void)hipFree(c->d_rx_keys);
+    if (c->d_rx_failed) (void)hipFree(c->d_rx_failed);
+    if (c->h_rx_block) (void)hipHostFree(c->h_rx_block);
     if (c->tail_stream) (void)hipStreamSynchronize(c->tail_stream);
     for (Slot &sl : c->slot) {
         for (void *q : {(void *)sl.score.si, (void *)sl.score.rec, (void *)sl.score.flag, (void *)sl.score.slot, (void *)sl.score.pos,
@@ -706,6 +772,11 @@ try {
     c->flush_pending = true;
     c->score_epoch++;
     c->exact_valid = false;
+    c->rx_set_valid = c->rx_set_full = c->rx_held_valid = false;
+    if (c->rx_scoring) {   // the keyed sets are sized from the number of receivers
+        ADSB_ON_DEVICE(c);
+        if (int rc = ensure_rx_scoring(c)) return rc;
+    }
     return ADSB_OK;
 } ADSB_ABI_CATCH
 
@@ -717,8 +788,14 @@ try {
     // Host only: the device's superset keeps the receiver's addresses (it stays a superset of every filter).  With
     // nothing left to replay the filter is emptied here; otherwise when the next pass submitted is collected, in front
     // of its replay, behind the replays of the passes in flight now.
-    if (c->submitted == c->collected) c->rx_filter_of[receiver]->flush();
-    else c->rx_flush_next.push_back(receiver);
+    if (c->submitted == c->collected) {
+        c->rx_filter_of[receiver]->flush();
+        if (receiver < c->rx_held.size()) c->rx_held[receiver] = 0;
+    } else {
+        c->rx_flush_next.push_back(receiver);
+    }
+    // (scoring on the device: the keyed set cannot forget one receiver -- the next scored pass drains and rebuilds it)
+    c->rx_set_valid = false;
     return ADSB_OK;
 } ADSB_ABI_CATCH
 
@@ -749,6 +826,80 @@ int adsb_selftest_rx_counters(const adsb_ctx *c, uint64_t *out4)
     return ADSB_OK;
 }
 
+// ---- receivers scored on the device (include/adsb_hip.h) ----
+int adsb_set_receiver_scoring(adsb_ctx *c, int enabled)
+try {
+    if (!c) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    if (enabled && !c->rx_scoring) {
+        ADSB_ON_DEVICE(c);
+        c->rx_scoring = true;   // (remembered whatever comes of it: adsb_set_receivers reserves what is missing)
+        if (int rc = ensure_rx_scoring(c)) {
+            c->rx_scoring = false;
+            return rc;
+        }
+    }
+    c->rx_scoring = enabled != 0;
+    // either way the passes in flight are none, and the next scored pass of either kind rebuilds what it scores against
+    c->rx_set_valid = false;
+    return ADSB_OK;
+} ADSB_ABI_CATCH
+
+int adsb_get_receiver_scoring(const adsb_ctx *c) { return c ? (c->rx_scoring ? 1 : 0) : ADSB_ERR_INVALID; }
+
+int adsb_selftest_rx_score_counters(const adsb_ctx *c, uint64_t *out4)
+{
+    if (!c || !out4) return ADSB_ERR_INVALID;
+    out4[0] = c->rx_scored_taken, out4[1] = c->rx_scored_refused, out4[2] = c->rx_set_rebuilds, out4[3] = c->rx_no_room;
+    return ADSB_OK;
+}
+
+int adsb_selftest_rx_score_tune(adsb_ctx *c, uint32_t set_lg, uint32_t probe_max)
+{
+    if (!c || (set_lg && (set_lg < 4 || set_lg > kRxSetLgMax)) || probe_max > 4096) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
+    c->rx_tune_lg = set_lg;
+    c->rx_tune_probe = probe_max;
+    c->rx_set_valid = c->rx_set_full = false;   // (the sets are re-made with the new geometry before they are used again)
+    return ADSB_OK;
+}
+
+uint32_t adsb_rx_set_home(uint64_t key, uint32_t set_lg) { return set_lg >= 1 && set_lg <= 32 ? rx_set_home(key, set_lg) : 0u; }
+
+int adsb_selftest_rx_set_lookup(adsb_ctx *c, const uint64_t *keys, size_t n_keys, const uint64_t *queries, size_t n_q, uint32_t *out)
+try {
+    if (!c || !out || (!keys && n_keys) || (!queries && n_q) || n_keys > (1u << 24) || n_q > (1u << 24)) return ADSB_ERR_INVALID;
+    for (size_t i = 0; i < n_keys; i++)
+        if (keys[i] == ~0ull) return ADSB_ERR_INVALID;   // (the empty slot's value: no (receiver, value) pair makes it)
+    ADSB_ON_DEVICE(c);
+    // a scratch set with the geometry the context's own sets have now (the tuned one, or the default for its receivers)
+    const uint32_t dflt = rx_set_lg_for(c->n_receivers);
+    const uint32_t lg = c->rx_tune_lg ? std::min(c->rx_tune_lg, dflt) : dflt, probe_max = c->rx_probe_max();
+    const size_t set_bytes = sizeof(unsigned long long) << lg, in_bytes = (n_keys + n_q) * sizeof(unsigned long long);
+    char *d = nullptr;
+    const size_t o_in = set_bytes, o_out = o_in + ((in_bytes + 255) & ~(size_t)255), total = o_out + (n_q + 1) * sizeof(uint32_t);
+    HIP_TRY(c, hipMalloc((void **)&d, total));
+    int rc = ADSB_OK;
+    auto step = [&](hipError_t e, const char *what) {
+        if (rc == ADSB_OK && e != hipSuccess) rc = fail(c, e, what);
+    };
+    unsigned long long *d_set = reinterpret_cast<unsigned long long *>(d), *d_in = reinterpret_cast<unsigned long long *>(d + o_in);
+    uint32_t *d_out = reinterpret_cast<uint32_t *>(d + o_out);
+    step(hipMemsetAsync(d_set, 0xFF, set_bytes, c->stream), "hipMemsetAsync");
+    step(hipMemsetAsync(d_out, 0, (n_q + 1) * sizeof(uint32_t), c->stream), "hipMemsetAsync");
+    if (n_keys) step(hipMemcpyAsync(d_in, keys, n_keys * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync");
+    if (n_q) step(hipMemcpyAsync(d_in + n_keys, queries, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync");
+    c->own_stream_dirty = true;
+    if (rc == ADSB_OK)
+        if (int e = launch_rx_set_fill(d_in, (uint32_t)n_keys, d_set, lg, probe_max, d_out + n_q, c->stream)) rc = fail(c, (hipError_t)e, "launch_rx_set_fill");
+    if (rc == ADSB_OK)
+        if (int e = launch_rx_set_lookup(d_in + n_keys, (uint32_t)n_q, d_set, lg, probe_max, d_out, c->stream)) rc = fail(c, (hipError_t)e, "launch_rx_set_lookup");
+    step(hipMemcpyAsync(out, d_out, (n_q + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
+    step(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    (void)hipFree(d);
+    return rc;
+} ADSB_ABI_CATCH
+
 uint64_t adsb_host_sorts(const adsb_ctx *c) { return c ? c->host_sorts : 0; }
 uint64_t adsb_host_replays(const adsb_ctx *c) { return c ? c->host_replays : 0; }
 uint64_t adsb_host_rematches(const adsb_ctx *c) { return c ? c->rematches : 0; }
@@ -763,6 +914,6 @@ int adsb_get_stats(const adsb_ctx *c, adsb_stats *out)
 
 const char *adsb_last_error(const adsb_ctx *c) { return c ? c->last_error.c_str() : ""; }
 
-const char *adsb_version(void) { return "adsb_hip 0.22 gfx950 scan=v9-tile-buckets tail=v8-sparse-lean multi=v3-bounded-waits streams=v2-own-queues stats=v1"; }
+const char *adsb_version(void) { return "adsb_hip 0.22 gfx950 scan=v9-tile-buckets tail=v8-sparse-lean multi=v3-bounded-waits streams=v2-own-queues stats=v1 rxscore=v1"; }
 
 }  // extern "C"

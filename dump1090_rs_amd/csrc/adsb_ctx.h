@@ -101,6 +101,15 @@ struct Slot {
     // the mode is set: no allocation per submit), and the receivers whose host filters an adsb_icao_flush_receiver empties
     // in front of this pass's replay
     std::vector<uint32_t> rx_map, rx_flush;
+    // ... scored on the device (adsb_set_receiver_scoring; all null until the mode is first enabled with receivers on): the
+    // device copy of the map and the pinned staging it is copied from in stream order, the keyed first-adder table and the
+    // slot of it every adder's key sits in, and the receiver of every addition in mapped host memory beside h_adds
+    bool rx_scored = false;        // this pass went through k_rx_adders / k_score_rx / k_emit_rx
+    uint32_t *d_rx_map = nullptr, *h_rx_map = nullptr;
+    unsigned long long *d_rx_first = nullptr;
+    uint32_t *d_rx_slot = nullptr;
+    uint32_t *h_add_rx = nullptr, *h_add_rx_dev = nullptr;
+    RxScoreDev rx{};
 };
 
 // Passes in flight: 4 and the device never waits for the host between large passes (3 do for sparse
@@ -320,6 +329,29 @@ struct adsb_ctx {
     std::unique_ptr<adsb::host::ReplayPool> rx_pool;     // created with the first pass that is replayed by several threads
     uint32_t rx_parallel_min = kRxParallelReplayMin;
     uint64_t rx_passes = 0, rx_pooled = 0, rx_reseeds = 0;   // adsb_selftest_rx_counters
+    // Device-side scoring with receivers on (adsb_set_receiver_scoring; adsb_device.h: RxScoreDev).  The keyed exact set
+    // plays the exact bitmap's part -- two in rotation, an icao_flush switches to the empty one and that pass's k_emit_rx
+    // empties the retired one -- and rx_set_valid plays exact_valid's: whenever the host scores a pass itself, or a single
+    // receiver is flushed (the set cannot forget one receiver), the next scored pass parks what is pending and rebuilds the
+    // set from every receiver's host filter.  The host's filters remain the authority.
+    bool rx_scoring = false;
+    unsigned long long *rx_set[2] = {nullptr, nullptr};
+    int cur_rx_set = 0;
+    uint32_t rx_set_alloc_lg = 0;            // log2 of the slots each set was allocated with (from n_receivers)
+    uint32_t rx_tune_lg = 0, rx_tune_probe = 0;   // adsb_selftest_rx_score_tune (0: the defaults)
+    bool rx_set_valid = false;
+    bool rx_set_full = false;                // a rebuild ran out of probes: the host scores until the next icao_flush
+    char *h_rx_block = nullptr;              // every slot's pinned map staging and h_add_rx: one mapped allocation
+    unsigned long long *d_rx_keys = nullptr; // the rebuild's keys (grown on demand) and its out-of-probes count
+    size_t rx_keys_cap = 0;
+    uint32_t *d_rx_failed = nullptr;
+    // addresses each receiver's filter holds (counted afresh when !rx_held_valid: the host replayed a pass; kept in step by the
+    // flushes and by the additions of the results taken) / additions of the pass being looked at, and the receivers that have any
+    std::vector<uint32_t> rx_held, rx_pass_adds, rx_touched;
+    bool rx_held_valid = false;
+    uint64_t rx_scored_taken = 0, rx_scored_refused = 0, rx_set_rebuilds = 0, rx_no_room = 0;   // adsb_selftest_rx_score_counters
+    uint32_t rx_set_lg() const { return rx_tune_lg ? std::min(rx_tune_lg, rx_set_alloc_lg) : rx_set_alloc_lg; }
+    uint32_t rx_probe_max() const { return rx_tune_probe ? rx_tune_probe : kRxProbeMax; }
 };
 
 namespace adsb {
@@ -440,6 +472,13 @@ void stamp_seq(adsb_ctx *c, Slot &sl, ScanParams &p, bool scored = false);
 std::vector<uint32_t> filter_addresses(const adsb_ctx *c);
 int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc);
 int resync_exact(adsb_ctx *c);
+// receivers scored on the device: the slots' buffers and the two keyed sets, sized for c->n_receivers (adsb_context.cpp;
+// nothing may be in flight; no-op in a context that never scores on the device or with receivers off); log2 of the slots
+// a keyed set gets for n receivers; and the keyed set rebuilt from every receiver's host filter (only while nothing is in
+// flight; false in c->rx_set_valid afterwards: it ran out of probes, c->rx_set_full)
+int ensure_rx_scoring(adsb_ctx *c);
+uint32_t rx_set_lg_for(uint32_t n_receivers);
+int rebuild_rx_set(adsb_ctx *c);
 int reseed_bitmap_from_filter(adsb_ctx *c);
 int submit(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, bool inline_tail = false,
            hipEvent_t input_done = nullptr);

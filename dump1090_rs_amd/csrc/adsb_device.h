@@ -158,14 +158,15 @@ struct ScoreState {
     uint32_t n;            // hits of this pass (0 when it is not to be scored: overflow, too many)
     uint32_t blocks_done;  // k_emit
     uint32_t scored;       // 1: k_score / k_emit handle this pass (a pass without a single hit included)
-    uint32_t reserved;
+    uint32_t reserved;     // a receivers pass (adsb_score_rx.hip): an insertion ran out of probes; k_emit_rx zeroes it again
     unsigned long long msg_sum;  // 64-bit sum of every u64 word of the messages written
 };
 struct ScoreSummary {      // in mapped host memory
     uint32_t n_msgs, n_adds;
     uint32_t msg_sum_lo, msg_sum_hi;
     uint32_t scored;       // 1: messages / adds are the pass's result; 0: the host replays the records
-    uint32_t pad[2];
+    uint32_t no_room;      // a receivers pass (k_emit_rx): an insertion into a keyed table ran out of probes (then scored = 0)
+    uint32_t pad;
     uint32_t seq;
 };
 struct ScoreDev {
@@ -193,6 +194,42 @@ struct ScoreDev {
 };
 constexpr int kScoreBlocks = 256;  // k_score / k_emit grid: block b owns a contiguous run of hits
 enum ScoreKind : uint32_t { kSkOther = 0, kSkApShort, kSkApLong, kSkDf11Iid0, kSkDf11, kSkDf17, kSkDf18, kSkNone };
+
+// Device-side scoring with one filter per receiver (adsb_set_receiver_scoring; adsb_score_rx.hip).  The argument of
+// ScoreDev with one change of key: "v is in the filter of THIS BUFFER'S RECEIVER r when trial i is scored" iff (r, v) was
+// in r's filter when the pass began -- the keyed exact set -- or an earlier trial of the pass in one of r's buffers added
+// it -- the keyed first-adder table.  Key = r << 24 | v (r < 16384: 38 bits).  Both tables are open addressing over
+// 64-bit words, ~0 = empty, nothing is ever deleted, and BOTH probe loops stop after a constant number of slots: an
+// insertion that finds neither its key nor an empty slot by then sets ScoreState::reserved, the pass's summary says
+// scored = 0 and the host replays the records; a lookup may stop there too, because a key that is in the table sits
+// within that many slots of its home.  Parameters of their own beside ScanParams: the plain kernels see the layout they
+// always had.
+constexpr uint32_t kRxSetLgMin = 13, kRxSetLgMax = 22;   // slots of a keyed set: 2^13 (64 KB) .. 2^22 (32 MiB)
+constexpr uint32_t kRxProbeMax = 64;                    // slots an insertion or a lookup walks at most
+__host__ __device__ inline uint32_t rx_set_home(unsigned long long key, uint32_t lg)
+{
+    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64u - lg));   // Fibonacci hashing: the top lg bits (1 <= lg <= 32)
+}
+struct ScanParams;
+struct RxScoreDev {
+    const uint32_t *rx_map;        // the receiver of every buffer of the pass (n_chunks; buffer = pos >> 24)
+    unsigned long long *first;     // adders: key << 24 | first index (i < 2^24), the size of ScoreDev::hash
+    uint32_t first_lg;
+    uint32_t *rx_slot;             // per hit: the slot of `first` its key sits in (adders), else 0xFFFFFFFF
+    uint32_t *out_add_rx;          // mapped host memory, beside ScoreDev::out_adds: the receiver of every addition
+    unsigned long long *set;       // the keyed exact set: the filters as they stand before this pass
+    uint32_t set_lg, probe_max;
+    unsigned long long *set_retired;   // after an icao_flush: the set the passes before it used, for k_emit_rx to clear
+    uint32_t retired_lg;
+};
+// k_rx_adders, k_score_rx, k_emit_rx on `stream`, in that order
+int launch_score_rx(const ScanParams &p, const RxScoreDev &x, void *stream);
+// insert n keys into a keyed set; *d_failed += insertions that ran out of probes
+int launch_rx_set_fill(const unsigned long long *d_keys, uint32_t n, unsigned long long *set, uint32_t set_lg, uint32_t probe_max,
+                       uint32_t *d_failed, void *stream);
+// self-test: out[i] = 1 when queries[i] is found by the lookup k_score_rx uses
+int launch_rx_set_lookup(const unsigned long long *d_queries, uint32_t n, const unsigned long long *set, uint32_t set_lg,
+                         uint32_t probe_max, uint32_t *d_out, void *stream);
 
 struct ScanParams {
     const void *src;        // IQ as {re,im} int16 pairs, or u16 magnitudes (from_mag)

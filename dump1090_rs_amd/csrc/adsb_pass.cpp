@@ -169,15 +169,36 @@ static int plan_pass(adsb_ctx *c, const Slot &sl, SrcFormat fmt, uint32_t n_chun
     // time; the worst-case lists of the fallback are the host's too.
     pl.ordered = !opt.force_simple && n_chunks > kInlineTailChunks && sl.hits_cap == c->hits_cap && c->dense_mode;
     // (in every error-correction mode: k_score / k_emit score and repair a fix pass's DF17/18 trials themselves)
-    // (never with receivers on: k_score holds ONE filter, the replay of such a pass is the host's, buffer by buffer)
-    const bool score_on_device = pl.ordered && c->score.si && !c->n_receivers;
-    if (score_on_device && !c->exact_valid) {
-        // the device's copy of the filter can only be rebuilt from the host's once every pass in
-        // flight has been replayed: finish them now (their results wait for adsb_collect)
-        if (int rc = park_pending(c)) return rc;
-        if (int rc = resync_exact(c)) return rc;
+    // (with receivers on only where adsb_set_receiver_scoring asked for it: k_score holds ONE filter, such a pass goes
+    // through the keyed kernels of adsb_score_rx.hip; otherwise its replay is the host's, buffer by buffer)
+    const bool rx = c->n_receivers != 0;
+    if (rx && c->flush_pending) c->rx_set_full = false;   // (every filter starts empty again: so can the keyed set)
+    const bool score_on_device = pl.ordered && c->score.si && (!rx || (c->rx_scoring && c->rx_set[0] && !c->rx_set_full));
+    if (score_on_device && rx) {
+        if (!c->rx_set_valid) {
+            // the keyed set can only be rebuilt from the host's filters once every pass in flight has been replayed:
+            // finish them now (their results wait for adsb_collect).  The receiver flushes recorded against this pass
+            // are what made the set invalid, or come behind whatever did: every earlier pass has been replayed by
+            // then, so they are applied to the host's filters here, in front of the rebuild.
+            if (int rc = park_pending(c)) return rc;
+            for (uint32_t r : c->rx_flush_next)
+                if (r < c->rx_filter_of.size()) {
+                    c->rx_filter_of[r]->flush();
+                    if (r < c->rx_held.size()) c->rx_held[r] = 0;
+                }
+            c->rx_flush_next.clear();
+            if (int rc = rebuild_rx_set(c)) return rc;
+        }
+        pl.scored = c->rx_set_valid;
+    } else {
+        if (score_on_device && !c->exact_valid) {
+            // the device's copy of the filter can only be rebuilt from the host's once every pass in
+            // flight has been replayed: finish them now (their results wait for adsb_collect)
+            if (int rc = park_pending(c)) return rc;
+            if (int rc = resync_exact(c)) return rc;
+        }
+        pl.scored = score_on_device && c->exact_valid;
     }
-    pl.scored = score_on_device && c->exact_valid;
     pl.prof = c->profiling;   // 1: the scan launch stamps its own begin / end; 2: classic event records between all kernels
     // A pass of a few buffers is all launch overhead and event traffic: it goes out as ONE launch whose last workgroup
     // matches, builds the records and publishes the summary, with no event behind it.  (Level 2 wants the kernels apart.)
@@ -215,7 +236,22 @@ static void fill_pass(adsb_ctx *c, Slot &sl, ScanParams &p, const void *d_src, S
     // sparse stream's scan stays the lean instantiation (and the reference-shaped kernel, the fallback's, fills none)
     p.hit_fields = pl.fused || (pl.ordered && !knob_no_hit_fields()) ? sl.d_hit_fields : nullptr;
     sl.device_scored = pl.scored;
-    if (pl.scored) {
+    sl.rx_scored = pl.scored && c->n_receivers;
+    if (sl.rx_scored) {
+        // the plain exact bitmap is not this pass's business (no rotation, nothing retired); the keyed set is
+        unsigned long long *set_retired = nullptr;
+        if (c->flush_pending) {  // icao_flush: this pass starts from the empty keyed set
+            set_retired = c->rx_set[c->cur_rx_set];
+            c->cur_rx_set ^= 1;
+        }
+        wire_score(sl, p, c->exact_bm[c->cur_exact], nullptr);
+        sl.rx.set = c->rx_set[c->cur_rx_set];
+        sl.rx.set_lg = c->rx_set_lg();
+        sl.rx.probe_max = c->rx_probe_max();
+        sl.rx.set_retired = set_retired;
+        sl.rx.retired_lg = c->rx_set_alloc_lg;   // (the whole allocation, whatever geometry the passes before used)
+        sl.score_epoch = c->score_epoch;
+    } else if (pl.scored) {
         uint32_t *exact_retired = nullptr;
         if (c->flush_pending) {  // icao_flush: this pass starts from the clean exact bitmap
             exact_retired = c->exact_bm[c->cur_exact];
@@ -471,7 +507,13 @@ static int enqueue_score(adsb_ctx *c, Slot &sl, const ScanParams &p, const PassP
         // k_score(i+1) reads the exact bitmap after k_emit(i) has committed pass i's additions to it.
         hipStream_t qs = c->score_stream;
         HIP_TRY(c, hipStreamWaitEvent(qs, sl.recorded, 0));   // edge (4)
-        if (int e = launch_score(p, qs)) return fail(c, (hipError_t)e, "launch_score");
+        if (sl.rx_scored) {
+            // a receivers pass: the map, out of its pinned staging, in stream order in front of the three keyed kernels
+            // (the slot's previous pass read its copy earlier on this very stream)
+            std::memcpy(sl.h_rx_map, sl.rx_map.data(), (size_t)p.n_chunks * sizeof(uint32_t));
+            HIP_TRY(c, hipMemcpyAsync(sl.d_rx_map, sl.h_rx_map, (size_t)p.n_chunks * sizeof(uint32_t), hipMemcpyHostToDevice, qs));
+            if (int e = launch_score_rx(p, sl.rx, qs)) return fail(c, (hipError_t)e, "launch_score_rx");
+        } else if (int e = launch_score(p, qs)) return fail(c, (hipError_t)e, "launch_score");
         ts = qs;
     }
     if (pl.prof > 1) HIP_TRY(c, hipEventRecord(sl.ev[4], ts));
@@ -552,6 +594,44 @@ int resync_exact(adsb_ctx *c)
     return ADSB_OK;
 }
 
+// The keyed set of a receivers context rebuilt from every receiver's host filter (only while nothing is in flight).  With
+// an icao_flush pending the pass about to be planned starts from empty filters: both sets are emptied and none is filled.
+// A rebuild that runs out of probes (more addresses than the capped set takes within its probe bound) leaves the set
+// invalid and c->rx_set_full set: the host scores until the next icao_flush.
+int rebuild_rx_set(adsb_ctx *c)
+{
+    hipStream_t ts = c->score_stream;
+    c->rx_set_rebuilds++;
+    c->rx_set_valid = false;
+    for (auto *st : c->rx_set) HIP_TRY(c, hipMemsetAsync(st, 0xFF, sizeof(unsigned long long) << c->rx_set_alloc_lg, ts));
+    std::vector<unsigned long long> keys;
+    if (!c->flush_pending)
+        for (uint32_t r = 0; r < c->n_receivers; r++)
+            for (uint32_t a : c->rx_filter_of[r]->table())
+                if (a != 0 && a <= 0xFFFFFFu) keys.push_back((unsigned long long)r << 24 | a);   // (DF18 entries match no 24-bit value)
+    uint32_t failed = 0;
+    if (!keys.empty()) {
+        if (keys.size() > c->rx_keys_cap) {
+            if (c->d_rx_keys) (void)hipFree(c->d_rx_keys);
+            c->d_rx_keys = nullptr;
+            c->rx_keys_cap = 0;
+            const size_t alloc = std::max<size_t>(keys.size() + keys.size() / 2, IcaoFilter::kSize);
+            HIP_TRY(c, hipMalloc((void **)&c->d_rx_keys, alloc * sizeof(unsigned long long)));
+            c->rx_keys_cap = alloc;
+        }
+        HIP_TRY(c, hipMemsetAsync(c->d_rx_failed, 0, sizeof(uint32_t), ts));
+        HIP_TRY(c, hipMemcpyAsync(c->d_rx_keys, keys.data(), keys.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ts));
+        if (int e = launch_rx_set_fill(c->d_rx_keys, (uint32_t)keys.size(), c->rx_set[c->cur_rx_set], c->rx_set_lg(), c->rx_probe_max(),
+                                       c->d_rx_failed, ts))
+            return fail(c, (hipError_t)e, "launch_rx_set_fill");
+        HIP_TRY(c, hipMemcpyAsync(&failed, c->d_rx_failed, sizeof(uint32_t), hipMemcpyDeviceToHost, ts));
+    }
+    HIP_TRY(c, hipStreamSynchronize(ts));  // (rare: only after the host scored a pass itself, or a receiver flush)
+    c->rx_set_full = failed != 0;
+    c->rx_set_valid = failed == 0;
+    return ADSB_OK;
+}
+
 // The overflow fallback re-runs a pass against the bitmap in use NOW.  Passes submitted after the
 // overflowed one may have rotated the bitmaps (an icao_flush in between) and the retired one has been
 // cleared, so the addresses the filter held before this pass would be missing from the superset:
@@ -583,21 +663,22 @@ int submit(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, bo
     PassOptions opt;
     opt.inline_tail = inline_tail;
     opt.input_done = input_done;
+    if (c->n_receivers) {
+        // whose buffers these are: the caller's map from this pass's first buffer on (a blocking call cut into passes
+        // hands it on piece by piece), or receiver 0 throughout for a plain call (within the capacity reserved by
+        // adsb_set_receivers: nothing is allocated).  In front of the enqueue: a pass scored on the device takes it along.
+        if (c->rx_call_map) sl.rx_map.assign(c->rx_call_map, c->rx_call_map + n_chunks);
+        else sl.rx_map.assign((size_t)n_chunks, 0u);
+    }
     int rc = enqueue_pass(c, sl, d_src, fmt, n_samples, (uint32_t)n_chunks, opt);
 #ifdef ADSB_TUNING
     c->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - te0).count();
 #endif
     if (rc) return rc;
     if (c->n_receivers) {
-        // whose buffers these are: the caller's map from this pass's first buffer on (a blocking call cut into passes
-        // hands it on piece by piece), or receiver 0 throughout for a plain call; and the receiver flushes asked for
-        // since the previous submission (within the capacity reserved by adsb_set_receivers: nothing is allocated)
-        if (c->rx_call_map) {
-            sl.rx_map.assign(c->rx_call_map, c->rx_call_map + n_chunks);
-            c->rx_call_map += n_chunks;
-        } else {
-            sl.rx_map.assign((size_t)n_chunks, 0u);
-        }
+        if (c->rx_call_map) c->rx_call_map += n_chunks;
+        // ... and the receiver flushes asked for since the previous submission (a pass scored on the device that had to
+        // rebuild its keyed set has applied them already: plan_pass)
         sl.rx_flush.clear();
         sl.rx_flush.swap(c->rx_flush_next);
     }

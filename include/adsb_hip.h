@@ -129,7 +129,8 @@ typedef struct {
  * Input denser than the lists are sized for (several times a busy airspace) is still
  * demodulated exactly, buffer by buffer through worst-case lists allocated on first use
  * (another 10 MB of device and 20 MB of pinned memory; stats.retries).
- * adsb_set_receivers(n) adds 16 KB of ordinary host memory per receiver beyond the first ("Many receivers, one pass"). */
+ * adsb_set_receivers(n) adds 16 KB of ordinary host memory per receiver beyond the first, adsb_set_receiver_scoring what
+ * its paragraph lists ("Many receivers, one pass"). */
 int adsb_create(adsb_ctx **out, int device, size_t max_chunks);
 void adsb_destroy(adsb_ctx *ctx);
 
@@ -421,10 +422,10 @@ uint64_t adsb_selftest_signal_launches(const adsb_ctx *ctx);
  * the device keeps across buffers is the address SUPERSET the address/parity trials are matched against -- with
  * receivers on, the union of all receivers' addresses, which is a superset of each receiver's filter at every moment.
  * A false superset hit costs one trial record that the host replay then scores -1; what differs is that replay, which
- * scores every record against the filter of its buffer's receiver.  Passes are never scored on the device while
- * receivers are on (adsb_host_replays counts every pass); a pass of several thousand records from more than one
- * receiver is replayed by up to six more host threads, a receiver's buffers to one thread, created when the first such
- * pass is collected and joined by adsb_destroy.
+ * scores every record against the filter of its buffer's receiver.  Unless adsb_set_receiver_scoring (below) says
+ * otherwise, passes are never scored on the device while receivers are on (adsb_host_replays counts every pass); a pass
+ * of several thousand records from more than one receiver is replayed by up to six more host threads, a receiver's
+ * buffers to one thread, created when the first such pass is collected and joined by adsb_destroy.
  *
  *   adsb_set_receivers(n)   n = 0: off (default).  ADSB_ERR_BUSY while passes are pending; ADSB_ERR_INVALID for
  *                           n > ADSB_MAX_RECEIVERS and while carry-over is enabled (and adsb_set_carry_over(ctx, 1) is
@@ -449,9 +450,37 @@ uint64_t adsb_selftest_signal_launches(const adsb_ctx *ctx);
  *                           records that score -1 until an adsb_icao_flush retires the superset.
  *   adsb_receiver_filter_table(r)  table A of receiver r's filter, for inspection.  ADSB_ERR_BUSY while passes are in
  *                           flight.
+ *
+ * Scoring on the device, per receiver -- opt-in, off by default; with it off nothing observable changes (no launch, no
+ * memory, the same adsb_host_replays counts).
+ *   adsb_set_receiver_scoring(ctx, enabled)   ADSB_ERR_BUSY while passes are pending, ADSB_ERR_INVALID for a null
+ *                           context, ADSB_OK otherwise -- also with receivers off and on a context created with
+ *                           max_chunks <= 16: the setting is remembered, and it has no effect where no pass is ever
+ *                           ordered on the device (a context of <= 16 buffers, passes of <= 16 buffers, sparse streams).
+ *   adsb_get_receiver_scoring   1 / 0, or ADSB_ERR_INVALID for a null context.
+ * With receivers on and scoring on, a pass the library would order on the device (a large context, more than 16 buffers,
+ * a stream that has left >= 8 trial records per buffer) is scored there too, by kernels of its own that ask "is value v
+ * in the filter of THIS BUFFER'S receiver": a set keyed by (receiver, value) holds the filters as they stand before the
+ * pass, a table keyed the same way the first trial of the pass that adds each pair.  What comes back is the defining
+ * equation above, field for field, signal_level bit for bit, through every _rx call, their _u8 twins,
+ * adsb_ring_submit_rx and the plain calls, in every error-correction mode.  The host's filters remain the authority:
+ * every pass's additions are applied to them at collect, and the host replays the pass itself (adsb_host_replays)
+ * whenever it cannot take the device's result -- a receiver whose table would come within 64 of its 4096 slots, an
+ * insertion into a keyed table that ran out of its constant probe bound, a pass behind one the host scored.
+ *   footprint               reserved the first time the mode is on together with receivers (in a large context).  Device:
+ *                           two keyed sets of 8 x 2^k bytes, 2^k the power of two >= 8192 n_receivers, capped at 2^22
+ *                           slots (64 KB each for one receiver, 4 MiB for 64, 32 MiB from 512 on; more than ~2 million
+ *                           addresses over all receivers do not fit and leave such passes to the host); per pass in
+ *                           flight 4 max_chunks + 4 S bytes and a keyed table the size of the plain one, S the scored
+ *                           message slots of adsb_create's footprint (min(4096 + 1024 max_chunks, 262144)).  Pinned
+ *                           host: per pass in flight 4 max_chunks + 4 S bytes.  max_chunks = 512, 512 receivers: 64 MiB
+ *                           + 4 x 5.2 MB device, 4 x 1.05 MB pinned.
+ *   adsb_icao_flush         switches to the other (empty) keyed set, as it does for the one filter: nothing is drained.
+ *   adsb_icao_flush_receiver   DRAINS the pipeline while scoring is on: the keyed set cannot forget one receiver, so the
+ *                           next pass scored on the device first waits for every pass in flight (their results still
+ *                           come from adsb_collect, in order) and rebuilds the set from the host's filters.
  * Not offered: carry-over with receivers (the scan kernel would need a lead-in source per buffer), valid lengths per
- * buffer, scoring on the device per receiver (a keyed filter set in the scoring kernels: the natural next step for
- * busy batches), receivers in adsb_multi / the shard calls, and adsb_feed. */
+ * buffer, receivers in adsb_multi / the shard calls, and adsb_feed. */
 #define ADSB_MAX_RECEIVERS 16384
 int adsb_set_receivers(adsb_ctx *ctx, uint32_t n_receivers);
 int adsb_get_receivers(const adsb_ctx *ctx);
@@ -486,6 +515,25 @@ int adsb_replay_records_rx(uint32_t *filter_tables, uint32_t n_receivers, const 
  * put back from the union of the receivers' filters (overflow fallback, rematch), [3] 0. */
 int adsb_selftest_rx_tune(adsb_ctx *ctx, uint32_t parallel_min);
 int adsb_selftest_rx_counters(const adsb_ctx *ctx, uint64_t *out4);
+int adsb_set_receiver_scoring(adsb_ctx *ctx, int enabled);
+int adsb_get_receiver_scoring(const adsb_ctx *ctx);
+/* Test hooks of the scoring per receiver (results never depend on them).
+ * counters, out4: [0] passes whose device result the host took, [1] passes scored on the device that the host replayed
+ * itself all the same (result refused or disowned), [2] rebuilds of the keyed set from the host's filters, [3] passes in
+ * which an insertion ran out of probes.
+ * tune: the keyed set shrunk to 2^set_lg slots (4 .. 22, never more than it was allocated with) and its probe bound set
+ * to probe_max (<= 4096), so that a few hundred addresses reach the out-of-probes path; 0 / 0 restores the defaults
+ * (from n_receivers; 64 probes).  ADSB_ERR_BUSY while passes are pending.
+ * set_lookup: fills a scratch set of the context's current geometry with `keys` (none may be all ones) through the device
+ * function the emit kernel inserts with, answers `queries` through the one the score kernel looks up with: out[i] = 1 / 0
+ * for i < n_q, and out[n_q] = the insertions that ran out of probes (`out` holds n_q + 1 words).
+ * adsb_rx_set_home: host only, the slot a key's probes start at in a set of 2^set_lg slots (1 <= set_lg <= 32, else 0);
+ * key = receiver << 24 | value. */
+int adsb_selftest_rx_score_counters(const adsb_ctx *ctx, uint64_t *out4);
+int adsb_selftest_rx_score_tune(adsb_ctx *ctx, uint32_t set_lg, uint32_t probe_max);
+int adsb_selftest_rx_set_lookup(adsb_ctx *ctx, const uint64_t *keys, size_t n_keys, const uint64_t *queries, size_t n_q,
+                                uint32_t *out);
+uint32_t adsb_rx_set_home(uint64_t key, uint32_t set_lg);
 
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167

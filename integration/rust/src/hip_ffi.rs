@@ -176,6 +176,13 @@ unsafe extern "C" {
     pub fn adsb_replay_records_rx(filter_tables: *mut u32, n_receivers: u32, receiver_of_buffer: *const u32, n_buffers: usize, records: *mut AdsbTrial, n: usize, mode: c_int, threads: c_int, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_selftest_rx_tune(ctx: *mut AdsbCtx, parallel_min: u32) -> c_int;
     pub fn adsb_selftest_rx_counters(ctx: *const AdsbCtx, out4: *mut u64) -> c_int;
+    // ... scored on the device, per receiver (opt-in), and its test hooks
+    pub fn adsb_set_receiver_scoring(ctx: *mut AdsbCtx, enabled: c_int) -> c_int;
+    pub fn adsb_get_receiver_scoring(ctx: *const AdsbCtx) -> c_int;
+    pub fn adsb_selftest_rx_score_counters(ctx: *const AdsbCtx, out4: *mut u64) -> c_int;
+    pub fn adsb_selftest_rx_score_tune(ctx: *mut AdsbCtx, set_lg: u32, probe_max: u32) -> c_int;
+    pub fn adsb_selftest_rx_set_lookup(ctx: *mut AdsbCtx, keys: *const u64, n_keys: usize, queries: *const u64, n_q: usize, out: *mut u32) -> c_int;
+    pub fn adsb_rx_set_home(key: u64, set_lg: u32) -> u32;
     pub fn adsb_shard_scan(ctx: *mut AdsbCtx, device_iq: *const c_void, n_samples: usize, addrs_out: *mut u32, cap: usize, n_addrs: *mut usize) -> c_int;
     pub fn adsb_shard_finish(ctx: *mut AdsbCtx, extra_addrs: *const u32, n_extra: usize, records_out: *mut AdsbTrial, cap: usize, n_records: *mut usize) -> c_int;
     pub fn adsb_multi_create(out: *mut *mut AdsbMulti, devices: *const c_int, n_devices: c_int, max_chunks_per_device: usize) -> c_int;
