@@ -143,7 +143,18 @@ void adsb_destroy(adsb_ctx *ctx);
 int adsb_set_stream(adsb_ctx *ctx, void *hip_stream);
 /* HIP-event timing of the kernels: 0 = off, 1 = ms_scan only (default; two events),
  * 2 = also ms_match / ms_records / ms_total_device (an event costs the
- * stream several microseconds, so level 2 slows a call down noticeably). */
+ * stream several microseconds, so level 2 slows a call down noticeably).
+ * Values below 0 count as 0, values above 2 as 2.
+ * The level never changes a result: every entry point returns the same messages, signal records and
+ * filter tables at every level (tests/test_gpu_profiling_levels.py holds levels 0 and 2 to the CPU
+ * oracle).  It does change which code a pass runs through.  At level 2 the kernels are kept apart to be
+ * timed: no pass is a single launch (a context created with max_chunks <= 16 runs scan, match and records
+ * as three launches on one of two scan streams instead of one launch on one of four), a ring slot is never
+ * read in place (it is copied in front of its pass), and adsb_host_rematches does not grow (no pass is
+ * launched unordered and matched again by the host: the stream order does it).  At level 0 the passes are
+ * those of level 1 without their events, and every ms_* field of adsb_stats is 0.
+ * Returns ADSB_ERR_BUSY while passes are pending (submitted and not yet collected) or a shard is parked
+ * between adsb_shard_scan and adsb_shard_finish; the level then stays what it was. */
 int adsb_set_profiling(adsb_ctx *ctx, int level);
 
 /* == icao_filter::icao_flush() (src/icao_filter.rs:11-17) for this context.  Stream-ordered: costs nothing by

@@ -132,7 +132,7 @@ def okey(w):
     return (w["chunk"], w["j"], w["try_phase"], w["score"], w["len"], w["msg"], w["signal_level"])
 
 
-def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, xrng=None):
+def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, xrng=None, level=1):
     """A stream of passes that switches between the host's and the device's ordering / scoring:
     dense passes of 17-30 buffers (thousands of records), the odd sparse or small one, random
     icao_flush, up to three in flight -- every pass against the oracle fed the same sequence."""
@@ -152,11 +152,13 @@ def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, x
 
     def check(got, want, what):
         if [key(m) for m in got] != [okey(w) for w in want]:
-            print(f"MISMATCH dense pipeline {case} (fuzz seed {seed}) at {what}: {len(got)} frames, {len(want)} expected")
+            print(f"MISMATCH dense pipeline {case} (fuzz seed {seed}, profiling level {level}) at {what}: {len(got)} frames, {len(want)} expected")
             sys.exit(1)
 
     orc = Oracle()
     ctx = Context(0, 32)
+    if level != 1:
+        ctx.set_profiling(level)   # (--profiling: before the first pass)
     orc.icao_flush()
     ctx.icao_flush()
     pending = []   # expected outputs of the passes in flight
@@ -200,10 +202,13 @@ def dense_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, x
     modes[("dense_pipeline", False)] = modes.get(("dense_pipeline", False), 0) + 1
     modes[("dense_pipeline:host_replays", False)] = modes.get(("dense_pipeline:host_replays", False), 0) + int(ctx._L.adsb_host_replays(ctx._h))
     modes[("dense_pipeline:passes", False)] = modes.get(("dense_pipeline:passes", False), 0) + int(step)
+    if level != 1:
+        modes[(f"dense_pipeline:level{level}", False)] = modes.get((f"dense_pipeline:level{level}", False), 0) + 1
+        ctx.set_profiling(1)       # (... and back behind the last)
     ctx.close()
 
 
-def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, xrng=None):
+def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, xrng=None, level=1):
     """Cross-pass ordering: a stream of passes of very different sizes -- one to six buffers (their match
     and records run on their own scan stream) between passes of 17-48 (tail stream) -- over captures that
     share a handful of addresses, so that address/parity frames keep depending on what earlier passes
@@ -252,6 +257,8 @@ def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, x
     torch.cuda.synchronize()
     ring_cap = int(rng.choice([6, 24])) * CHUNK
     ctx = Context(0, 48)
+    if level != 1:
+        ctx.set_profiling(level)   # (--profiling: before the first pass)
     ctx.ring_create(ring_cap)
     orc = Oracle()
     orc.icao_flush()
@@ -261,7 +268,8 @@ def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, x
 
     def check(got, want, what):
         if [key(m) for m in got] != [okey(w) for w in want]:
-            print(f"MISMATCH mixed pipeline {case} (fuzz seed {seed}) at {what}: sizes {sizes}, {len(got)} frames, {len(want)} expected")
+            print(f"MISMATCH mixed pipeline {case} (fuzz seed {seed}, profiling level {level}) at {what}: sizes {sizes}, {len(got)} frames, "
+                  f"{len(want)} expected")
             for x, y in zip([okey(w) for w in want], [key(m) for m in got]):
                 if x != y:
                     print(" first difference:", x, y)
@@ -299,6 +307,9 @@ def mixed_pipeline_case(rng, synth, Context, Oracle, torch, modes, case, seed, x
         check(ctx.collect(cap=1 << 18), pending.pop(0), "drain")
     modes[("mixed_pipeline", False)] = modes.get(("mixed_pipeline", False), 0) + 1
     modes[("mixed_pipeline:passes", False)] = modes.get(("mixed_pipeline:passes", False), 0) + steps
+    if level != 1:
+        modes[(f"mixed_pipeline:level{level}", False)] = modes.get((f"mixed_pipeline:level{level}", False), 0) + 1
+        ctx.set_profiling(1)       # (... and back behind the last)
     ctx.close()
 
 
@@ -512,6 +523,11 @@ def main():
     ap.add_argument("--fix", type=float, default=0.0, metavar="P",
                     help="run this fraction of the single-context cases under ADSB_FIX_1BIT, with damaged DF17 / DF18 "
                          "copies, against the restatement (tests/fix_support.py)")
+    ap.add_argument("--profiling", type=float, default=0.0, metavar="P",
+                    help="run this fraction of the cases and of the dense and mixed pipelines at profiling level 0 or 2 "
+                         "(adsb_set_profiling before the first pass, level 1 again after the last): level 2 takes every pass "
+                         "through three launches, level 0 records no event.  (adsb_multi's own contexts have no such call: the "
+                         "--multi sequences run as they always do)")
     args = ap.parse_args()
     import torch
     from dump1090_rs_amd import Context, sharding, synth
@@ -524,6 +540,13 @@ def main():
     rng = np.random.default_rng(args.seed)
     # --formats / --fix draw from a generator of their own: without them every case of a seed is what it always was
     xrng = np.random.default_rng([args.seed, 3000017]) if (args.formats or args.fix > 0) else None
+    # --profiling draws from generators of its own too: the default, 0.0, replays every seed unchanged
+
+    def draw_level(*k):
+        if args.profiling <= 0:
+            return 1
+        g = np.random.default_rng([args.seed, 5000011, *k])
+        return int(g.choice([0, 2])) if g.random() < args.profiling else 1
     ctx = Context(0, args.max_chunks)
     ring_chunks = min(2, args.max_chunks)
     ctx.ring_create(ring_chunks * CHUNK)
@@ -546,6 +569,7 @@ def main():
             api = "device"
         ncuts = int(rng.integers(1, 4))
         cut_draw = rng.integers(1, n, size=ncuts - 1)
+        level = draw_level(0, case)
         if args.only >= 0 and case != args.only:
             continue
         if args.only >= 0 and args.api:
@@ -561,6 +585,10 @@ def main():
             modes[("fix_cases", False)] = modes.get(("fix_cases", False), 0) + 1
         for c in all_ctx:
             c.set_error_correction(1 if fix_case else 0)
+            if level != 1:
+                c.set_profiling(level)   # (--profiling: before the case's first pass, level 1 again behind its last)
+        if level != 1:
+            modes[(f"profiling_level{level}", False)] = modes.get((f"profiling_level{level}", False), 0) + 1
 
         def expected(cuts):
             if fix_case:
@@ -645,7 +673,7 @@ def main():
             merged = sharding.merge_records(recs, [a // CHUNK for a, _ in spans])
             gots = [[key(m) for m in replay_records(merged, cap=1 << 20, mode=1 if fix_case else 0)]]
         if gots != wants:
-            print(f"MISMATCH case {case} (fuzz seed {args.seed}, noise seed {seed}): api={api} carry={carry_mode} fix={fix_case} "
+            print(f"MISMATCH case {case} (fuzz seed {args.seed}, noise seed {seed}): api={api} carry={carry_mode} fix={fix_case} profiling={level} "
                   f"n={n} cuts={cuts} frames want {[len(w) for w in wants]} got {[len(g) for g in gots]}")
             for w, g in zip(wants, gots):
                 for x, y in zip(w, g):
@@ -653,6 +681,9 @@ def main():
                         print(" first difference:", x, y)
                         break
             sys.exit(1)
+        if level != 1:
+            for c in all_ctx:
+                c.set_profiling(1)
     for c in all_ctx:
         c.set_error_correction(0)
     if args.only < 0:
@@ -660,10 +691,10 @@ def main():
             return np.random.default_rng([args.seed, 4000037, *k]) if args.formats else None
         for k in range(args.dense):
             dense_pipeline_case(np.random.default_rng([args.seed, k]), synth, Context, binding.Oracle, torch, modes, k, args.seed,
-                                xrng=fx(0, k))
+                                xrng=fx(0, k), level=draw_level(1, k))
         for k in range(args.mixed):
             mixed_pipeline_case(np.random.default_rng([args.seed, 1000003, k]), synth, Context, binding.Oracle, torch, modes, k, args.seed,
-                                xrng=fx(1, k))
+                                xrng=fx(1, k), level=draw_level(2, k))
         for k in range(args.multi):
             multi_case(np.random.default_rng([args.seed, 2000003, k]), synth, MultiContext, binding.Oracle, torch, modes, k, args.seed,
                        faults=not args.no_multi_faults, xrng=fx(2, k))

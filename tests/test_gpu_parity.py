@@ -1380,6 +1380,15 @@ def test_randomised_soak_all_entry_points(hip_lib, oracle_mod):
     # (+ 20 dense pipelines: device-side order / score; + 40 mixed ones: small and large passes in flight
     # together over shared addresses -- the kind of case that found round 2's cross-stream ordering hole)
     assert "300 cases identical" in r.stdout and "dense_pipeline=20" in r.stdout and "mixed_pipeline=40" in r.stdout and "multi=30" in r.stdout
+    # ... and a short one that draws the profiling level: 0 (no events) or 2 (no pass is one launch) for 0.7 of its cases
+    # and pipelines, before their first pass (tests/test_gpu_profiling_levels.py has the planted scenarios)
+    r = subprocess.run([sys.executable, str(ROOT / "tests" / "fuzz_gpu.py"), "--cases", "60", "--seed", "50", "--dense", "6", "--mixed", "10", "--multi", "0",
+                        "--profiling", "0.7"], capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "60 cases identical" in r.stdout and "dense_pipeline=6" in r.stdout and "mixed_pipeline=10" in r.stdout
+    for drawn in ("profiling_level0=24", "profiling_level2=23", "dense_pipeline:level0=2", "dense_pipeline:level2=4",
+                  "mixed_pipeline:level0=3", "mixed_pipeline:level2=4"):
+        assert drawn in r.stdout, (drawn, r.stdout[-1500:])
 
 
 def test_soak_seed_that_found_the_overlapping_scans_hole(hip_lib, oracle_mod):
