@@ -6,51 +6,30 @@ using namespace adsb::host;
 
 namespace {
 
-// The pass's messages as the device scored them, when they can be taken as they are: scored in the
-// current epoch, whole (checksum), and with the filter nowhere near full -- the one situation whose
-// reference behaviour (icao_filter_add gives up on a full table, src/icao_filter.rs:46-62) the parallel
-// formulation does not reproduce.  Applies the pass's additions to the host's filter, in order.
-bool take_device_result(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vector<adsb_msg> &out)
+// the 64-bit sum of n 8-byte words of mapped host memory that the device may still be writing: the checksum the
+// kernels keep of their records and of their messages
+uint64_t word_sum(const void *p, size_t n)
 {
-    if (!sl.device_scored || sl.score_epoch != c->score_epoch) return false;
-    const ScoreSummary *ss = sl.h_ssum;
-    if (__atomic_load_n(&ss->seq, __ATOMIC_ACQUIRE) != sl.seq || !ss->scored) return false;
-    const size_t nm = ss->n_msgs, na = ss->n_adds;
-    if (nm > c->score.cap || na > c->score.cap) return false;
-    size_t held = 0;
-    for (uint32_t a : c->filter.table()) held += a != 0;
-    if (held + na + 64 >= IcaoFilter::kSize) return false;
-    const uint64_t want = (uint64_t)ss->msg_sum_hi << 32 | ss->msg_sum_lo;
-    bool whole = false;
-    for (int attempt = 0; attempt < 200 && !whole; attempt++) {
-        uint64_t got = 0;
-        const uint64_t *w = reinterpret_cast<const uint64_t *>(sl.h_msgs);
-        for (size_t i = 0; i < 5 * nm; i++) got += __atomic_load_n(&w[i], __ATOMIC_RELAXED);
-        whole = got == want;
-    }
-    if (!whole) return false;
-    const size_t at = out.size();
-    out.insert(out.end(), sl.h_msgs, sl.h_msgs + nm);
-    if (chunk_offset)
-        for (size_t i = at; i < out.size(); i++) out[i].chunk += chunk_offset;
-    const uint64_t before = c->filter.inserts();
-    for (size_t i = 0; i < na; i++) c->filter.add(sl.h_adds[i]);
-    if (c->filter.inserts() != before) c->last_new_insert_seq = sl.scan_seq;
-    return true;
+    const uint64_t *w = static_cast<const uint64_t *>(p);
+    uint64_t got = 0;
+    for (size_t i = 0; i < n; i++) got += __atomic_load_n(&w[i], __ATOMIC_RELAXED);
+    return got;
 }
 
-// The same for a pass of several receivers scored by the keyed kernels (adsb_score_rx.hip): the additions come as (value,
-// receiver) pairs, and the guard holds for EVERY receiver that has an addition in the pass -- held[r] + adds[r] + 64 < 4096,
-// with held[r] kept from pass to pass and counted afresh whenever the host has touched the filters itself.
-bool take_device_result_rx(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vector<adsb_msg> &out)
+// ---- the two things a plain pass and a receivers pass do differently with a device result: the room test, and where
+// the additions go.  A filter that is nearly full is the one situation whose reference behaviour (icao_filter_add gives
+// up on a full table, src/icao_filter.rs:46-62) the parallel formulation does not reproduce. ----
+bool adds_have_room(adsb_ctx *c, size_t na)
 {
-    if (!sl.rx_scored || sl.score_epoch != c->score_epoch) return false;
-    const ScoreSummary *ss = sl.h_ssum;
-    if (__atomic_load_n(&ss->seq, __ATOMIC_ACQUIRE) != sl.seq) return false;
-    if (ss->no_room) c->rx_no_room++;
-    if (!ss->scored) return false;
-    const size_t nm = ss->n_msgs, na = ss->n_adds;
-    if (nm > c->score.cap || na > c->score.cap) return false;
+    size_t held = 0;
+    for (uint32_t a : c->filter.table()) held += a != 0;
+    return held + na + 64 < IcaoFilter::kSize;
+}
+
+// ... for EVERY receiver that has an addition in the pass (sl.h_add_rx: the receiver of each) -- held[r] + adds[r] + 64
+// < 4096, with held[r] kept from pass to pass and counted afresh whenever the host has touched the filters itself
+bool adds_have_room_rx(adsb_ctx *c, const Slot &sl, size_t na)
+{
     if (!c->rx_held_valid) {
         c->rx_held.assign(c->n_receivers, 0u);
         c->rx_pass_adds.assign(c->n_receivers, 0u);
@@ -69,20 +48,19 @@ bool take_device_result_rx(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::ve
         room = room && (size_t)c->rx_held[r] + c->rx_pass_adds[r] + 64 < IcaoFilter::kSize;
         c->rx_pass_adds[r] = 0;
     }
-    if (!room) return false;
-    const uint64_t want = (uint64_t)ss->msg_sum_hi << 32 | ss->msg_sum_lo;
-    bool whole = false;
-    for (int attempt = 0; attempt < 200 && !whole; attempt++) {
-        uint64_t got = 0;
-        const uint64_t *w = reinterpret_cast<const uint64_t *>(sl.h_msgs);
-        for (size_t i = 0; i < 5 * nm; i++) got += __atomic_load_n(&w[i], __ATOMIC_RELAXED);
-        whole = got == want;
-    }
-    if (!whole) return false;
-    const size_t at = out.size();
-    out.insert(out.end(), sl.h_msgs, sl.h_msgs + nm);
-    if (chunk_offset)
-        for (size_t i = at; i < out.size(); i++) out[i].chunk += chunk_offset;
+    return room;
+}
+
+// the pass's additions into the host's filter, in order; true: it took a new address
+bool apply_adds(adsb_ctx *c, const Slot &sl, size_t na)
+{
+    const uint64_t before = c->filter.inserts();
+    for (size_t i = 0; i < na; i++) c->filter.add(sl.h_adds[i]);
+    return c->filter.inserts() != before;
+}
+
+bool apply_adds_rx(adsb_ctx *c, const Slot &sl, size_t na)
+{
     bool gained = false;
     for (size_t i = 0; i < na; i++) {
         const uint32_t r = sl.h_add_rx[i];
@@ -94,8 +72,33 @@ bool take_device_result_rx(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::ve
             gained = true;
         }
     }
-    if (gained) c->last_new_insert_seq = sl.scan_seq;
-    c->rx_scored_taken++;
+    return gained;
+}
+
+// The pass's messages as the device scored them, when they can be taken as they are: scored in the current epoch, with
+// room in the filter (one, or one per receiver: sl.rx_scored, a pass of the keyed kernels of adsb_score_rx.hip, whose
+// additions come as (value, receiver) pairs), and whole (checksum).  Applies the pass's additions to the host's filters.
+bool take_device_result(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vector<adsb_msg> &out)
+{
+    const bool rx = sl.rx_scored;   // (implies device_scored: fill_pass)
+    if (!sl.device_scored || sl.score_epoch != c->score_epoch) return false;
+    const ScoreSummary *ss = sl.h_ssum;
+    if (__atomic_load_n(&ss->seq, __ATOMIC_ACQUIRE) != sl.seq) return false;
+    if (rx && ss->no_room) c->rx_no_room++;   // (counted whether or not the pass says it was scored: it never does then)
+    if (!ss->scored) return false;
+    const size_t nm = ss->n_msgs, na = ss->n_adds;
+    if (nm > c->score.cap || na > c->score.cap) return false;
+    if (!(rx ? adds_have_room_rx(c, sl, na) : adds_have_room(c, na))) return false;
+    const uint64_t want = (uint64_t)ss->msg_sum_hi << 32 | ss->msg_sum_lo;
+    bool whole = false;
+    for (int attempt = 0; attempt < 200 && !whole; attempt++) whole = word_sum(sl.h_msgs, 5 * nm) == want;
+    if (!whole) return false;
+    const size_t at = out.size();
+    out.insert(out.end(), sl.h_msgs, sl.h_msgs + nm);
+    if (chunk_offset)
+        for (size_t i = at; i < out.size(); i++) out[i].chunk += chunk_offset;
+    if (rx ? apply_adds_rx(c, sl, na) : apply_adds(c, sl, na)) c->last_new_insert_seq = sl.scan_seq;
+    c->rx_scored_taken += rx;
     return true;
 }
 
@@ -138,7 +141,19 @@ void flush_host_filters(adsb_ctx *c)
 {
     c->filter.flush();
     for (IcaoFilter &f : c->rx_filters) f.flush();
-    std::fill(c->rx_held.begin(), c->rx_held.end(), 0u);   // (take_device_result_rx's counts, while they are valid: all empty)
+    std::fill(c->rx_held.begin(), c->rx_held.end(), 0u);   // (adds_have_room_rx's counts, while they are valid: all empty)
+}
+
+// adsb_icao_flush_receiver calls that waited for their pass: the host's filters and the counts of what they hold (host
+// only: the device's superset stays one)
+void flush_receivers(adsb_ctx *c, std::vector<uint32_t> &receivers)
+{
+    for (uint32_t r : receivers)
+        if (r < c->rx_filter_of.size()) {
+            c->rx_filter_of[r]->flush();
+            if (r < c->rx_held.size()) c->rx_held[r] = 0;
+        }
+    receivers.clear();
 }
 
 // The records and the summary travel to host memory as separate posted writes; the summary's
@@ -150,10 +165,7 @@ int verify_records(adsb_ctx *c, const Summary *sum, const TrialRecord *rec, size
 {
     const uint64_t want = (uint64_t)sum->rec_sum_hi << 32 | sum->rec_sum_lo;
     for (int attempt = 0; attempt < 200; attempt++) {
-        uint64_t got = 0;
-        const uint64_t *w = reinterpret_cast<const uint64_t *>(rec);
-        for (size_t i = 0; i < 4 * n; i++) got += __atomic_load_n(&w[i], __ATOMIC_RELAXED);
-        if (got == want) return ADSB_OK;
+        if (word_sum(rec, 4 * n) == want) return ADSB_OK;
         for (volatile int spin = 0; spin < 2000; spin++) {}
     }
     if (c) c->last_error = "trial records in host memory do not add up to the checksum of the pass that wrote them";
@@ -311,7 +323,7 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
         if (n >= 8u * (size_t)sl.n_chunks) c->dense_mode = true;
         else if (n < 2u * (size_t)sl.n_chunks) c->dense_mode = false;
     }
-    if (sl.rx_scored ? take_device_result_rx(c, sl, chunk_offset, out) : take_device_result(c, sl, chunk_offset, out)) return 0;
+    if (take_device_result(c, sl, chunk_offset, out)) return 0;
     if (sl.rx_scored) c->rx_scored_refused++;
     if (rec_on_device && n) {
         HIP_TRY(c, hipMemcpy(sl.h_rec, sl.score.rec, n * sizeof(TrialRecord), hipMemcpyDeviceToHost));
@@ -344,6 +356,27 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
     return 0;
 }
 
+// In front of a pass that collect_oldest runs again: every stream drained, so that later passes have their results on the
+// host (they may have rotated the bitmaps behind an icao_flush: the caller puts the filter's addresses back) ...
+static int drain_streams(adsb_ctx *c)
+{
+    for (hipStream_t q : c->scan_stream)
+        if (q) HIP_TRY(c, hipStreamSynchronize(q));
+    HIP_TRY(c, hipStreamSynchronize(c->tail_stream));
+    HIP_TRY(c, hipStreamSynchronize(c->score_stream));
+    return ADSB_OK;
+}
+
+// ... and a pending icao_flush kept out of the redo's sight: it belongs to the next pass submitted
+struct KeepFlushPending {
+    adsb_ctx *c;
+    bool pending;
+    explicit KeepFlushPending(adsb_ctx *ctx) : c(ctx), pending(ctx->flush_pending) { c->flush_pending = false; }
+    ~KeepFlushPending() { c->flush_pending = pending; }
+    KeepFlushPending(const KeepFlushPending &) = delete;
+    KeepFlushPending &operator=(const KeepFlushPending &) = delete;
+};
+
 // Finish the oldest submission: replay it, or -- when a device list overflowed (far
 // denser input than the lists were sized for) -- drain the stream and go chunk by
 // chunk, where the worst case always fits.  Bitmap bits set by the aborted pass or by
@@ -355,13 +388,7 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
     st.n_samples = sl.n_samples;
     st.n_chunks = sl.n_chunks;
     if (sl.flush_before) flush_host_filters(c);  // icao_flush() took effect before this pass
-    // ... and so did the adsb_icao_flush_receiver calls recorded against it (host only: the device's superset stays one)
-    for (uint32_t r : sl.rx_flush)
-        if (r < c->rx_filter_of.size()) {
-            c->rx_filter_of[r]->flush();
-            if (r < c->rx_held.size()) c->rx_held[r] = 0;
-        }
-    sl.rx_flush.clear();
+    flush_receivers(c, sl.rx_flush);             // ... and so did the adsb_icao_flush_receiver calls recorded against it
     int rc = finish_pass(c, sl, 0, st, out);
     if (rc == 2) {
         // a one-launch pass that a pass in flight beside it may have invalidated (finish_pass): once more
@@ -369,28 +396,19 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         // icao_flush: as for the overflow fallback, drain the streams and put the filter's addresses (the
         // state that preceded this pass) back into the bitmap in use.
         c->rematches++;
-        for (hipStream_t q : c->scan_stream)
-            if (q) HIP_TRY(c, hipStreamSynchronize(q));
-        HIP_TRY(c, hipStreamSynchronize(c->tail_stream));
-        HIP_TRY(c, hipStreamSynchronize(c->score_stream));
-        const bool keep_flush = c->flush_pending;
-        c->flush_pending = false;
+        if (int e = drain_streams(c)) return e;
+        const KeepFlushPending keep(c);
         PassOptions redo;   // three launches, blocking, on the input it already read
         redo.redo = redo.inline_tail = redo.no_fuse = true;
         redo.input_done = input_ready_now();
         rc = reseed_bitmap_from_filter(c);
         if (rc == 0) rc = enqueue_pass(c, sl, sl.src, sl.fmt, sl.n_samples, sl.n_chunks, redo);
         if (rc == 0) rc = finish_pass(c, sl, 0, st, out);
-        c->flush_pending = keep_flush;
     }
     if (rc > 0 && sl.fmt == SrcFormat::kMag) {  // a caller-supplied buffer denser than the fast scan's lists: again, the slow way
         st.retries++;
-        for (hipStream_t q : c->scan_stream)
-            if (q) HIP_TRY(c, hipStreamSynchronize(q));
-        HIP_TRY(c, hipStreamSynchronize(c->tail_stream));
-        HIP_TRY(c, hipStreamSynchronize(c->score_stream));
-        const bool keep_flush = c->flush_pending;
-        c->flush_pending = false;
+        if (int e = drain_streams(c)) return e;
+        const KeepFlushPending keep(c);
         Slot tmp;
         rc = fallback_slot(c, sl, tmp);
         if (rc == 0) rc = reseed_bitmap_from_filter(c);
@@ -398,15 +416,10 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
         slow.redo = slow.force_simple = true;
         if (rc == 0) rc = enqueue_pass(c, tmp, sl.src, SrcFormat::kMag, sl.n_samples, 1, slow);
         if (rc == 0) rc = finish_pass(c, tmp, 0, st, out);
-        c->flush_pending = keep_flush;
     } else if (rc > 0) {
         st.retries++;
-        for (hipStream_t q : c->scan_stream)
-            if (q) HIP_TRY(c, hipStreamSynchronize(q));  // later passes have their results on the host
-        HIP_TRY(c, hipStreamSynchronize(c->tail_stream));
-        HIP_TRY(c, hipStreamSynchronize(c->score_stream));
-        const bool keep_flush = c->flush_pending;
-        c->flush_pending = false;
+        if (int e = drain_streams(c)) return e;
+        const KeepFlushPending keep(c);
         Slot tmp;  // same counters, summary and events; one chunk at a time into the worst-case lists
         rc = fallback_slot(c, sl, tmp);
         if (rc == 0) rc = reseed_bitmap_from_filter(c);
@@ -438,7 +451,6 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
             }
             if (rc == 0) rc = finish_pass(c, tmp, ch, st, out);
         }
-        c->flush_pending = keep_flush;
     }
     // (a pass the fallback or the rematch ran again launched no second k_signal_stats: the records are the first enqueue's)
     c->sig_out.clear();

@@ -522,6 +522,8 @@ int deliver(adsb_ctx *c, std::vector<adsb_msg> &msgs, adsb_msg *out, size_t cap,
 bool summary_landed(const Summary *s, uint32_t seq);
 // adsb_icao_flush for the host side: every receiver's filter
 void flush_host_filters(adsb_ctx *c);
+// ... and for adsb_icao_flush_receiver calls whose turn has come: those receivers' filters; empties the list
+void flush_receivers(adsb_ctx *c, std::vector<uint32_t> &receivers);
 
 // adsb_shard.cpp: one shard of a capture in slot k, phase by phase, nothing blocking but shard_phase_wait
 // (and the buffer-by-buffer fallback of a shard that overflows the lists).  Order of calls per slot:

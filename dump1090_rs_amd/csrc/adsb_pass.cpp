@@ -181,12 +181,7 @@ static int plan_pass(adsb_ctx *c, const Slot &sl, SrcFormat fmt, uint32_t n_chun
             // are what made the set invalid, or come behind whatever did: every earlier pass has been replayed by
             // then, so they are applied to the host's filters here, in front of the rebuild.
             if (int rc = park_pending(c)) return rc;
-            for (uint32_t r : c->rx_flush_next)
-                if (r < c->rx_filter_of.size()) {
-                    c->rx_filter_of[r]->flush();
-                    if (r < c->rx_held.size()) c->rx_held[r] = 0;
-                }
-            c->rx_flush_next.clear();
+            flush_receivers(c, c->rx_flush_next);
             if (int rc = rebuild_rx_set(c)) return rc;
         }
         pl.scored = c->rx_set_valid;

@@ -171,6 +171,60 @@ def test_the_ring_on_a_large_context(hip_lib, oracle_mod):
         assert s.since() == {"taken": 4, "refused": 0, "rebuilds": 1, "no_room": 0, "replays": 0}
 
 
+def test_scored_passes_of_either_kind_leave_the_tables_empty_for_the_other(hip_lib, oracle_mod):
+    """One context: two pipelined dense passes with receivers and scoring on (k_score_rx / k_emit_rx), adsb_set_receivers(0)
+    and two plain ones (k_score / k_emit), receivers on again and two more.  Each kind of pass scores against first-adder
+    tables that the kind before it has to have left empty (an entry left behind makes a later trial of that address look
+    like one that comes after its first adder: 1000 for -1); every list equals the model's, which restarts from empty
+    filters at each switch, as adsb_set_receivers documents.
+    The counts of which passes the device scored are those of this test body on the commit that gave k_emit and k_emit_rx
+    one shared body, run against its parent's library, not this build's own."""
+    from dump1090_rs_amd import _lib
+    from dump1090_rs_amd._lib import AdsbError
+    n_receivers = 4
+    maps = random_maps(n_receivers, [N] * 4, 29)
+    zeros = np.zeros(N, dtype=np.uint32)
+    d = on_device(dense())
+
+    def empty_restart(c, n):
+        assert c.receivers() == n
+        if n:
+            assert not any(c.receiver_filter_table(r).any() for r in range(n))
+        else:
+            with pytest.raises(AdsbError) as e:
+                c.receiver_filter_table(0)
+            assert e.value.status == _lib.ADSB_ERR_INVALID
+
+    with Scored(n_receivers) as s:
+        c = s.c
+        rx = lambda k, p: c.submit_iq_device_rx(d.data_ptr(), N * CHUNK, p[2])   # noqa: E731
+        plain = lambda k, p: c.submit_iq_device(d.data_ptr(), N * CHUNK)         # noqa: E731
+        # receivers on, scoring on
+        passes = [(0, N, mp, 0) for mp in maps[:2]]
+        wants, shareds, model = expect_passes(n_receivers, dense(), passes)
+        RS.assert_tells_apart(n_receivers, sum(wants, []), sum(shareds, []))
+        assert run_pipeline(c, passes, rx) == wants
+        tables_equal(c, model, n_receivers)
+        assert s.since() == {"taken": 2, "refused": 0, "rebuilds": 1, "no_room": 0, "replays": 0}
+        # receivers off: a plain context, from an empty filter
+        c.set_receivers(0)
+        empty_restart(c, 0)
+        one = RS.Model(1)
+        want_plain = [one.feed(dense(), zeros) for _ in range(2)]
+        assert want_plain[0] != want_plain[1]
+        assert run_pipeline(c, [(0, N, zeros, 0)] * 2, plain) == want_plain
+        assert s.since() == {"taken": 2, "refused": 0, "rebuilds": 1, "no_room": 0, "replays": 0}   # (k_score / k_emit)
+        # receivers on again: every receiver from an empty filter, the keyed set rebuilt
+        c.set_receivers(n_receivers)
+        empty_restart(c, n_receivers)
+        passes = [(0, N, mp, 0) for mp in maps[2:]]
+        wants, shareds, model = expect_passes(n_receivers, dense(), passes)
+        RS.assert_tells_apart(n_receivers, sum(wants, []), sum(shareds, []))
+        assert run_pipeline(c, passes, rx) == wants
+        tables_equal(c, model, n_receivers)
+        assert s.since() == {"taken": 4, "refused": 0, "rebuilds": 2, "no_room": 0, "replays": 0}
+
+
 # ------------------------------------------------------------------------------------------------- 2. isolation
 X = 0x4B1A2C
 DF17_X = synth.df17_frame(X, 0x58B986D0B3BD25)

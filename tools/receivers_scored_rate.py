@@ -1,11 +1,13 @@
 """What scoring per receiver on the device (adsb_set_receiver_scoring, include/adsb_hip.h) does to a dense many-receiver
 step, against the parent commit's library, whose host-pooled replay is the yardstick.
 
-    python tools/receivers_scored_rate.py --parent-lib PATH [--blocks 6] [--out DIR] [--label TEXT]
+    python tools/receivers_scored_rate.py --parent-lib PATH [--blocks 6] [--out DIR] [--label TEXT] [--parent-scoring]
 
 One process, three contexts of 512 buffers with receivers on, driven through the bare C ABI: the parent commit's library
 (PATH: its libadsb_hip.so, built on this box), this build with scoring on, and this build with scoring off.  (--order: another
-order, or a second context of the parent's library as `parent_again`.)  The input
+order, or a second context of the parent's library as `parent_again`.  --parent-scoring: the parent's contexts score on
+the device too -- for a commit that changes the scoring kernels and not what they do: `on_inside_parent_spread` then says
+whether this build's step with scoring on lies inside the spread of the parent's own blocks.)  The input
 is one resident 512-buffer dense pass (5000 bursts: bench.py's config-5 input); the step is adsb_icao_flush + submit with
 four passes in flight, in blocks of 20 steps between device fences, and the three take turns block by block.  Twice: with
 a map of 512 receivers (one buffer each) and one of 8.
@@ -83,7 +85,7 @@ def run(args, n_receivers):
         h = C.c_void_p()
         assert L.adsb_create(C.byref(h), 0, N_BUF) == 0
         assert L.adsb_set_receivers(h, n_receivers) == 0
-        if name == "scoring_on":
+        if name == "scoring_on" or (args.parent_scoring and name.startswith("parent")):
             assert L.adsb_set_receiver_scoring(h, 1) == 0
         ctx[name] = h
         # into dense mode (one blocking pass), and the reference list: equal to the model, message by message
@@ -136,7 +138,8 @@ def run(args, n_receivers):
     rec = {"tool": "receivers_scored_rate", "label": args.label, "receivers": n_receivers, "buffers": N_BUF, "messages": len(want),
            "steps_per_block": PER_BLOCK, "in_flight": DEPTH, **res,
            "order": list(libs), "parent_spread_ms": [min(p), max(p)], "gain_ms": round(gain, 4), "gain_shown": gain > spread,
-           "off_inside_parent_spread": min(p) <= res["scoring_off"]["ms_per_step"] <= max(p)}
+           "off_inside_parent_spread": min(p) <= res["scoring_off"]["ms_per_step"] <= max(p),
+           "parent_scoring": args.parent_scoring, "on_inside_parent_spread": min(p) <= res["scoring_on"]["ms_per_step"] <= max(p)}
     line = json.dumps(rec)
     print(line, flush=True)
     if args.out:
@@ -153,6 +156,7 @@ def main():
     ap.add_argument("--order", default="parent,scoring_on,scoring_off",
                     help="the contexts in the order they are created and take their turns; `parent_again`: a second context of "
                          "the parent's library (what two contexts of ONE library differ by, by their place alone)")
+    ap.add_argument("--parent-scoring", action="store_true", help="scoring on in the parent's contexts too")
     ap.add_argument("--out")
     ap.add_argument("--label", default="")
     args = ap.parse_args()
