@@ -234,8 +234,7 @@ try {
             // scoring buffers, no message slots in its pinned block)
             const bool scoring = c->n_slots != ADSB_MAX_IN_FLIGHT_SMALL;
             cd.cap = scoring ? std::min<uint32_t>(c->hits_cap, 262144u) : 0u;   // (a 2 GiB shard of a busy sky leaves 135 000)
-            uint32_t hsize = 1;
-            while (hsize < 2 * cd.cap) hsize <<= 1;
+            const uint32_t hsize = score_hash_size(cd.cap);
             cd.hash_mask = hsize - 1;
             if (scoring) {
                 for (auto &bm : c->exact_bm) {

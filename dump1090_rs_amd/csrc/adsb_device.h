@@ -192,6 +192,16 @@ struct ScoreDev {
     ScoreSummary *summary;         // mapped host memory
     uint32_t seq;
 };
+// ScoreDev::hash: where the probes of value v start (masked with hash_mask by whoever probes: score_hash_insert in
+// adsb_tail_dev.h, score_hash_first in adsb_aux.hip), and how many slots a context whose passes score up to `cap` hits
+// gets -- the smallest power of two >= 2 cap, so the table is at most half full and the unbounded probe loops end.
+__host__ __device__ inline uint32_t score_hash_slot(uint32_t v) { return (v * 2654435761u) >> 8; }
+inline uint32_t score_hash_size(uint32_t cap)
+{
+    uint32_t hsize = 1;
+    while (hsize < 2 * cap) hsize <<= 1;
+    return hsize;
+}
 constexpr int kScoreBlocks = 256;  // k_score / k_emit grid: block b owns a contiguous run of hits
 enum ScoreKind : uint32_t { kSkOther = 0, kSkApShort, kSkApLong, kSkDf11Iid0, kSkDf11, kSkDf17, kSkDf18, kSkNone };
 

@@ -57,8 +57,7 @@ __device__ __forceinline__ uint32_t icao_hash_dev(uint32_t a)
     return (uint32_t)h & 4095u;
 }
 
-__device__ __forceinline__ uint32_t score_hash_slot(uint32_t v) { return (v * 2654435761u) >> 8; }
-
+// (score_hash_slot, the home slot of a value: adsb_device.h)
 __device__ __forceinline__ uint32_t score_hash_insert(const ScoreDev &sd, uint32_t v, uint32_t idx)
 {
     const unsigned long long mine = (unsigned long long)v << 32 | idx;
