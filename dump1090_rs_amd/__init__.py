@@ -16,6 +16,8 @@ from .context import (  # noqa: F401
     MODES_SHORT_MSG_BYTES,
     TRAILING_SAMPLES,
     Context,
+    Decimator,
+    default_taps,
     MagnitudeBuffer,
     ModeSMessage,
     replay_records_rx,
@@ -25,6 +27,6 @@ from . import demod_2400, icao_filter, utils  # noqa: F401
 
 __all__ = [
     "MODES_MAG_BUF_SAMPLES", "MODES_LONG_MSG_BYTES", "MODES_SHORT_MSG_BYTES", "TRAILING_SAMPLES",
-    "MagnitudeBuffer", "ModeSMessage", "Context", "default_context",
+    "MagnitudeBuffer", "ModeSMessage", "Context", "default_context", "Decimator", "default_taps",
     "utils", "demod_2400", "icao_filter",
 ]

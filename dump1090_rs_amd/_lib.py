@@ -23,6 +23,7 @@ ADSB_FIX_2BIT = 3
 ADSB_SCORE_FIXED_2BIT = 1100
 ADSB_FAULT_PHASE1, ADSB_FAULT_PHASE2, ADSB_FAULT_HANG, ADSB_FAULT_RECORDS = 1, 2, 3, 4
 ADSB_MAX_RECEIVERS = 16384
+ADSB_DECIM_CS16, ADSB_DECIM_8BIT = 0, 1
 
 
 class AdsbMsg(C.Structure):
@@ -290,6 +291,21 @@ def lib() -> C.CDLL:
                  "adsb_demod_iq_rx", "adsb_demod_iq_device_rx", "adsb_demod_iq_rx_u8", "adsb_demod_iq_device_rx_u8",
                  "adsb_submit_iq_device_rx", "adsb_submit_iq_device_rx_u8", "adsb_ring_submit_rx", "adsb_replay_records_rx",
                  "adsb_selftest_rx_tune", "adsb_selftest_rx_counters"):
+        getattr(L, name).restype = C.c_int
+    # decimation (include/adsb_hip.h)
+    i16p, u32p = C.POINTER(C.c_int16), C.POINTER(u32)
+    L.adsb_decim_create.argtypes = [vp, u32, vp, u32, u32, C.POINTER(vp)]
+    L.adsb_decim_destroy.argtypes = [vp]
+    L.adsb_decim_destroy.restype = None
+    L.adsb_decim_reset.argtypes = [vp]
+    L.adsb_decim_out_count.argtypes = [vp, sz, C.POINTER(sz)]
+    L.adsb_decim_run_device.argtypes = [vp, C.c_int, vp, sz, vp, sz, C.POINTER(sz)]
+    L.adsb_decim_demod_iq.argtypes = [vp, C.c_int, vp, sz, vp, sz, C.POINTER(sz)]
+    L.adsb_decim_default_taps.argtypes = [u32, i16p, sz, u32p, u32p]
+    L.adsb_decim_selftest_tile.argtypes = []
+    L.adsb_decim_selftest_tile.restype = u32
+    for name in ("adsb_decim_create", "adsb_decim_reset", "adsb_decim_out_count", "adsb_decim_run_device",
+                 "adsb_decim_demod_iq", "adsb_decim_default_taps"):
         getattr(L, name).restype = C.c_int
     L.adsb_host_replays.argtypes = [vp]
     L.adsb_host_replays.restype = C.c_uint64

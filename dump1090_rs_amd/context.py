@@ -336,6 +336,11 @@ class Context:
         self._check(self._L.adsb_submit_iq_device(self._h, C.c_void_p(device_ptr), n_samples),
                     "adsb_submit_iq_device")
 
+    def decimator(self, factor: int, taps=None, shift: Optional[int] = None) -> "Decimator":
+        """An integer FIR decimator in front of this context's passes, for IQ sampled at factor x 2.4 MS/s
+        (include/adsb_hip.h, "Decimation").  taps=None: default_taps(factor)."""
+        return Decimator(self, factor, taps, shift)
+
     def collect_raw(self, out_buf, cap: int) -> int:
         n = C.c_size_t()
         self._check(self._L.adsb_collect(self._h, out_buf, cap, C.byref(n)), "adsb_collect")
@@ -600,6 +605,89 @@ class Context:
         s = AdsbStats()
         self._check(self._L.adsb_get_stats(self._h, C.byref(s)), "adsb_get_stats")
         return {name: getattr(s, name) for name, _ in AdsbStats._fields_ if name != "reserved"}
+
+
+def default_taps(factor: int):
+    """adsb_decim_default_taps (host only): (taps int16[8 factor + 1], shift) of a Hamming-windowed sinc with its cutoff at
+    1.2 MHz."""
+    L = _lib.lib()
+    taps = np.empty(8 * int(factor) + 1, dtype=np.int16)
+    n, shift = C.c_uint32(), C.c_uint32()
+    st = L.adsb_decim_default_taps(int(factor), taps.ctypes.data_as(C.POINTER(C.c_int16)), taps.size, C.byref(n), C.byref(shift))
+    if st != _lib.ADSB_OK:
+        raise AdsbError(st, f"adsb_decim_default_taps: {L.adsb_strerror(st).decode()}")
+    return taps[: n.value], int(shift.value)
+
+
+class Decimator:
+    """One adsb_decim: a stateful exact-integer FIR decimator by `factor` on the context's device.  Close it before its
+    context."""
+
+    def __init__(self, ctx: Context, factor: int, taps=None, shift: Optional[int] = None):
+        self._ctx, self._L = ctx, ctx._L
+        self._h = C.c_void_p()
+        if taps is None:
+            taps, default_shift = default_taps(factor)
+            shift = default_shift if shift is None else shift
+        elif shift is None:
+            raise ValueError("taps of the caller's need a shift")
+        t = np.ascontiguousarray(taps, dtype=np.int16)
+        if t.ndim != 1:
+            raise ValueError("the taps are a flat int16 array")
+        self.factor, self.taps, self.shift = int(factor), t, int(shift)
+        self._check(self._L.adsb_decim_create(ctx._h, int(factor), t.ctypes.data, t.size, int(shift), C.byref(self._h)),
+                    "adsb_decim_create")
+
+    def _check(self, st: int, what: str) -> None:
+        self._ctx._check(st, what)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            if self._ctx._h.value:   # (a context that is gone took the device state with it)
+                self._L.adsb_decim_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self) -> None:
+        self._check(self._L.adsb_decim_reset(self._h), "adsb_decim_reset")
+
+    def out_count(self, n_in: int) -> int:
+        n = C.c_size_t()
+        self._check(self._L.adsb_decim_out_count(self._h, int(n_in), C.byref(n)), "adsb_decim_out_count")
+        return n.value
+
+    def run_device(self, ptr_in: int, n_in: int, ptr_out: int, out_cap: int, format: int = _lib.ADSB_DECIM_CS16) -> int:
+        """Device memory to device memory, enqueued without waiting; returns the output count.  AdsbError with status
+        ADSB_ERR_CAPACITY (and the required count in .required) when out_cap is too small: nothing was consumed."""
+        n = C.c_size_t()
+        st = self._L.adsb_decim_run_device(self._h, int(format), C.c_void_p(ptr_in), int(n_in), C.c_void_p(ptr_out), int(out_cap),
+                                           C.byref(n))
+        if st == _lib.ADSB_ERR_CAPACITY:
+            err = AdsbError(st, f"adsb_decim_run_device: {n.value} outputs do not fit {out_cap}")
+            err.required = n.value
+            raise err
+        self._check(st, "adsb_decim_run_device")
+        return n.value
+
+    def demod_iq(self, iq, format: int = _lib.ADSB_DECIM_CS16, cap: Optional[int] = None) -> List[ModeSMessage]:
+        """Host IQ at factor x 2.4 MS/s of any length -> the messages of the decimated stream (blocking)."""
+        a = _as_cu8(iq) if format == _lib.ADSB_DECIM_8BIT else _as_iq(iq)
+        cap = cap or max(4096, a.shape[0] // (256 * self.factor))
+        ptr = a.ctypes.data
+        return self._ctx._collect(
+            lambda out, c, n: self._L.adsb_decim_demod_iq(self._h, int(format), ptr, a.shape[0], out, c, n),
+            "adsb_decim_demod_iq", cap)
 
 
 _default: Optional[Context] = None

@@ -7,6 +7,7 @@
 //   adsb_collect.cpp   waiting for a pass, checksums, the overflow fallback
 //   adsb_replay_host.cpp  the ordered host replay and the other host-only entry points (no HIP: also built by g++ under sanitizers)
 //   adsb_ring.cpp      the pinned streaming ring
+//   adsb_decim.cpp     the decimator in front of the scan: its handle, counts, staging and default taps
 //   adsb_shard.cpp     the two-phase shard calls
 //   adsb_selftest.cpp  stage lists and digests for the tests
 #pragma once
@@ -486,6 +487,10 @@ int run_sync(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, 
              hipEvent_t input_done = nullptr);
 int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<adsb_msg> &out,
                  SrcFormat fmt = SrcFormat::kCs16);
+// the messages of the piece of a long call that starts at sample `off`, and the stats and signal records its pass left in
+// the context, join the call's (adsb_decim.cpp cuts its calls the same way)
+void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, std::vector<adsb_msg> &out, adsb_stats &total,
+                  std::vector<adsb_signal_stats> &sig);
 // T_soapy: the table SoapyRTLSDR widens an RTL-SDR's bytes with, (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f)
 void soapy_u8_table(int16_t *out256);
 int ensure_stage(adsb_ctx *c, size_t bytes);

@@ -409,6 +409,27 @@ struct SigParams {
 };
 uint32_t signal_stats_wg_per_chunk(uint32_t n_chunks);
 int launch_signal_stats(const SigParams &p, SrcFormat fmt, void *stream);
+// Decimation (adsb_decim_*; adsb_decim.hip: k_decim, k_decim_history): one call's inputs -> its outputs and the
+// history the next call starts from.  A kernel of its own in front of the scan, with parameters of its own.
+constexpr uint32_t kDecimTile = 256;        // outputs per workgroup
+constexpr uint32_t kDecimMinFactor = 2, kDecimMaxFactor = 16, kDecimMaxTaps = 512, kDecimMaxShift = 16;
+constexpr uint32_t kDecimHistWords = 512;   // a history buffer: the last n_taps - 1 inputs, widened, at [0, n_taps - 1)
+struct DecimParams {
+    const void *src;            // the call's inputs: CS16 dwords or byte pairs, 16-byte aligned
+    uint64_t n_in;              // ... how many (> 0)
+    const uint32_t *hist_prev;  // the n_taps - 1 inputs in front of the call (zero where the stream had not begun)
+    uint32_t *hist_next;        // ... and in front of the next one (the other buffer)
+    const int32_t *taps;        // device memory, padded with zeros to a multiple of eight
+    const uint16_t *u8_table;   // 8-bit input: the widening table (device memory), else null
+    uint32_t *out;              // CS16 dwords
+    uint64_t n_out;             // outputs of the call (may be 0: only the history moves on)
+    uint32_t factor, n_taps, shift;
+    uint32_t first;             // input index of the call's first output: (-P) mod factor
+    uint32_t row_len;           // decim_row_len(factor, n_taps): dwords per polyphase row in LDS
+    uint32_t recip;             // ceil(2^20 / factor)
+};
+uint32_t decim_row_len(uint32_t factor, uint32_t n_taps);
+int launch_decim(const DecimParams &p, void *stream);
 // self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
 int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 

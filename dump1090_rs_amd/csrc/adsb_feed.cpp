@@ -5,7 +5,12 @@
 // the dump1090 raw format) can consume it.
 //
 //   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K]
-//             [--latency-ms T] [--readers R] [--stats [SECONDS]] <capture.iq | ->
+//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D] <capture.iq | ->
+//
+// --decimate D (2..16): the input is sampled at D x 2.4 MS/s, in the format --format names, and goes through the
+// library's decimator with its default taps (adsb_decim_default_taps) in front of the demodulation: the output lines are
+// those of the decimated stream, cut into 131072-sample buffers as that stream would be.  This path is the blocking call
+// (adsb_decim_demod_iq), K buffers of output per call, not the ring: --latency-ms and --readers do not apply to it.
 //
 // --stats turns the signal statistics on (adsb_set_signal_stats) and prints what a receiver's gain is tuned by to
 // STDERR, every SECONDS (default 1) over the buffers since the last line and once more, as the last line, over the
@@ -309,7 +314,7 @@ int main(int argc, char **argv)
     int device = 0, port = 0, buffers = 64, latency_ms = 100, out_cap = 0, readers = 4;
     bool quiet = false, mem_order = false, cu8 = false, stats = false;
     double stats_seconds = 1.0;
-    int fix = ADSB_FIX_NONE;
+    int fix = ADSB_FIX_NONE, decimate = 0;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -318,6 +323,10 @@ int main(int argc, char **argv)
         else if (a == "--buffers" && i + 1 < argc) buffers = std::atoi(argv[++i]);
         else if (a == "--latency-ms" && i + 1 < argc) latency_ms = std::atoi(argv[++i]);
         else if (a == "--readers" && i + 1 < argc) readers = std::atoi(argv[++i]);
+        else if (a == "--decimate" && i + 1 < argc) {
+            decimate = std::atoi(argv[++i]);
+            if (decimate < 2 || decimate > 16) path = nullptr, i = argc;
+        }
         else if (a == "--out-cap" && i + 1 < argc) out_cap = std::atoi(argv[++i]);  // frames the output array starts with (it grows)
         else if (a == "--stats") {
             stats = true;
@@ -344,7 +353,7 @@ int main(int argc, char **argv)
         else path = argv[i];
     }
     if (!path || buffers < 1) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] <capture.iq | ->\n");
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -365,7 +374,7 @@ int main(int argc, char **argv)
     if ((st = adsb_set_error_correction(ctx, fix)) != ADSB_OK) return die(ctx, "adsb_set_error_correction", st);
     if (stats && (st = adsb_set_signal_stats(ctx, 1)) != ADSB_OK) return die(ctx, "adsb_set_signal_stats", st);
     const size_t slot_samples = (size_t)buffers * ADSB_MODES_MAG_BUF_SAMPLES;
-    if ((st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
+    if (!decimate && (st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
         return die(ctx, "adsb_ring_create", st);
     const size_t bps = cu8 ? 2 : 4;   // bytes per sample
 
@@ -376,6 +385,21 @@ int main(int argc, char **argv)
     SignalFold sig_interval, sig_total;
     std::vector<adsb_signal_stats> sig((size_t)buffers);
     auto t_stats = std::chrono::steady_clock::now();
+    auto emit = [&](size_t n) {   // out[0, n) to stdout and to the clients
+        std::string lines;
+        char line[40];
+        for (size_t i = 0; i < n; i++) {
+            const int len = adsb_format_raw(&out[i], line, sizeof(line));
+            if (len > 0) lines.append(line, (size_t)len);
+        }
+        total_frames += n;
+        if (!quiet && !lines.empty()) {
+            std::fwrite(lines.data(), 1, lines.size(), stdout);
+            std::fflush(stdout);
+        }
+        clients.accept_new();
+        if (!lines.empty()) clients.send_all(lines, latency_ms);
+    };
     auto drain_one = [&]() -> int {
         size_t n = 0;
         int rc = adsb_collect(ctx, out.data(), out.size(), &n);
@@ -395,21 +419,61 @@ int main(int argc, char **argv)
                 t_stats = now;
             }
         }
-        std::string lines;
-        char line[40];
-        for (size_t i = 0; i < n; i++) {
-            const int len = adsb_format_raw(&out[i], line, sizeof(line));
-            if (len > 0) lines.append(line, (size_t)len);
-        }
-        total_frames += n;
-        if (!quiet && !lines.empty()) {
-            std::fwrite(lines.data(), 1, lines.size(), stdout);
-            std::fflush(stdout);
-        }
-        clients.accept_new();
-        if (!lines.empty()) clients.send_all(lines, latency_ms);
+        emit(n);
         return ADSB_OK;
     };
+
+    if (decimate) {
+        // D x 2.4 MS/s: whole calls of `buffers` output buffers' worth of input, so that the decimated stream is cut
+        // where consecutive reads of 131072 samples of it would cut it
+        int16_t taps[8 * 16 + 1];
+        uint32_t n_taps = 0, shift = 0;
+        adsb_decim *dec = nullptr;
+        if ((st = adsb_decim_default_taps((uint32_t)decimate, taps, sizeof(taps) / sizeof(taps[0]), &n_taps, &shift)) != ADSB_OK)
+            return die(ctx, "adsb_decim_default_taps", st);
+        if ((st = adsb_decim_create(ctx, (uint32_t)decimate, taps, n_taps, shift, &dec)) != ADSB_OK) return die(ctx, "adsb_decim_create", st);
+        const size_t call_samples = slot_samples * (size_t)decimate;
+        std::vector<char> in_buf(call_samples * bps);
+        const auto t0 = std::chrono::steady_clock::now();
+        for (bool eof = false; !eof;) {
+            size_t fill = 0;
+            while (!eof && fill < in_buf.size()) {
+                bool idle = false;
+                fill = read_once(in, in_buf.data(), fill, in_buf.size(), -1, &eof, &idle);
+            }
+            const size_t n_in = fill / bps;
+            if (n_in == 0) break;
+            if (!mem_order && !cu8) swap_pairs(in_buf.data(), n_in);
+            size_t n = 0;
+            st = adsb_decim_demod_iq(dec, cu8 ? ADSB_DECIM_8BIT : ADSB_DECIM_CS16, in_buf.data(), n_in, out.data(), out.size(), &n);
+            if (st == ADSB_ERR_CAPACITY) {
+                out.resize(n);
+                st = adsb_fetch_messages(ctx, out.data(), out.size(), &n);
+            }
+            if (st != ADSB_OK) {
+                adsb_decim_destroy(dec);
+                return die(ctx, "adsb_decim_demod_iq", st);
+            }
+            if (stats) {
+                size_t n_sig = 0;
+                if ((st = adsb_fetch_signal_stats(ctx, sig.data(), sig.size(), &n_sig)) != ADSB_OK) {
+                    adsb_decim_destroy(dec);
+                    return die(ctx, "adsb_fetch_signal_stats", st);
+                }
+                for (size_t i = 0; i < n_sig; i++) sig_total.add(sig[i]);
+            }
+            emit(n);
+            total_samples += n_in;
+        }
+        const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::fprintf(stderr, "adsb_feed: %llu samples at %d x 2.4 MS/s, %llu frames in %.3f s (%.1f Msamples/s); %llu clients dropped\n",
+                     total_samples, decimate, total_frames, secs, secs > 0 ? total_samples / secs / 1e6 : 0.0, clients.dropped);
+        if (stats) sig_total.print("whole input");
+        if (in != 0) ::close(in);
+        adsb_decim_destroy(dec);
+        adsb_destroy(ctx);
+        return 0;
+    }
 
     struct stat sb{};
     const bool regular = in != 0 && ::fstat(in, &sb) == 0 && S_ISREG(sb.st_mode);

@@ -694,7 +694,7 @@ int run_sync(adsb_ctx *c, const void *d_src, SrcFormat fmt, uint64_t n_samples, 
 
 // A long stream goes in pieces: the messages of the piece at sample `off` (chunk = buffer of the stream) and the
 // stats its pass left in the context join the call's.
-static void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, std::vector<adsb_msg> &out, adsb_stats &total,
+void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, std::vector<adsb_msg> &out, adsb_stats &total,
                          std::vector<adsb_signal_stats> &sig)
 {
     for (auto &m : part) {

@@ -546,6 +546,68 @@ int adsb_selftest_rx_set_lookup(adsb_ctx *ctx, const uint64_t *keys, size_t n_ke
                                 uint32_t *out);
 uint32_t adsb_rx_set_home(uint64_t key, uint32_t set_lg);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Decimation -- IQ sampled at an integer multiple of 2.4 MS/s.  Every entry point above takes IQ at exactly 2.4 MS/s;
+ * a HackRF, bladeRF, USRP or Airspy runs at 4.8, 9.6, 12, 19.2 or 24 MS/s.  An adsb_decim is a stateful, exact-integer
+ * FIR decimator by an integer factor D that runs on the device in front of the scan, in a kernel of its own: its output
+ * is ordinary CS16 in device memory, which every call above takes.  Nothing else changes.
+ *
+ * Definition.  x[m], m = 0, 1, ..., is the input counted from adsb_decim_create or adsb_decim_reset, complex, `re` then
+ * `im` as in the CS16 calls; x[m] = 0 for m < 0.  With taps h[0..T-1] (int16) and shift s, for n = 0, 1, ... and for re and
+ * im separately:
+ *     acc  = sum over k of h[k] * x[n D - k]
+ *     y[n] = clamp((acc + r) >> s, -32768, 32767),   r = 1 << (s - 1), or 0 when s == 0,   >> arithmetic (a half rounds up)
+ * y is CS16 {re, im}.  D in 2..16, 1 <= T <= 512, s in 0..16, sum |h[k]| <= 65534 (an int32 accumulator then never wraps);
+ * anything else is ADSB_ERR_INVALID.
+ * A call with n_in inputs, P inputs having been consumed before it, produces exactly the y[n] with P <= n D < P + n_in:
+ * ceil((P + n_in) / D) - ceil(P / D) of them, possibly none.  The cut is invisible: the concatenated outputs of any
+ * cutting of a stream into calls -- calls of no input and calls shorter than T - 1 included -- equal the one-call result
+ * bit for bit.  The decimator keeps the last T - 1 inputs (on the device, in two buffers that take turns) and P (on the
+ * host: counts are host arithmetic, no call synchronises to learn one).
+ * 8-bit input (ADSB_DECIM_8BIT): byte b means T8[b], T8 the context's table at the time of the call (adsb_set_u8_table;
+ * T_soapy by default; a HackRF's CS8 is T8[b] = (int8_t)b << 8).  The bytes are widened as they are loaded and the history
+ * is kept widened, so a stream may alternate the formats; x[m < 0] is zero by position, not T8[0].  (adsb_set_u8_table does
+ * not wait for decimator calls still running: synchronise the stream before changing the table under them.)
+ *
+ *   adsb_decim_create        a decimator on the context's device.  Destroy it before the context.
+ *   adsb_decim_reset         the stream starts over (P = 0, zero history); ordered on the stream like a run
+ *   adsb_decim_out_count     host only: how many outputs the next run of n_in inputs would produce
+ *   adsb_decim_run_device    device memory to device memory (both 16-byte aligned, not overlapping).  Enqueues on the stream
+ *                            the context orders its input behind -- the caller's after adsb_set_stream, else the context's
+ *                            own -- and returns without waiting; *n_out is known at once.  The next pass submitted on the
+ *                            context waits for it, so the asynchronous form of the feature is
+ *                                adsb_decim_run_device(d, fmt, in, n_in, y, cap, &n);  adsb_submit_iq_device(ctx, y, n);
+ *                            with no synchronisation in between.  out_cap too small: ADSB_ERR_CAPACITY with the required
+ *                            count in *n_out; nothing is consumed and the state does not change.  Never ADSB_ERR_BUSY:
+ *                            the decimator does not care about pending passes.
+ *   adsb_decim_demod_iq      blocking, host input of any length: exactly what adsb_demod_iq returns on the y this call's
+ *                            input decimates to -- buffers are cut every 131072 OUTPUT samples of the call, the last may
+ *                            be short, `chunk` counts over the call; the filter persists.  Works in pieces of whole
+ *                            output buffers, min(max_chunks, 16) of them at most, through staging the decimator allocates
+ *                            on first use (at most (4 or 2) D + 4 bytes per output sample of a piece) and frees in
+ *                            adsb_decim_destroy.  ADSB_ERR_CAPACITY, adsb_fetch_messages, ADSB_ERR_BUSY and every context
+ *                            mode (error correction, signal statistics, carry-over) are adsb_demod_iq's: the pass
+ *                            underneath is the ordinary one.
+ *   adsb_decim_default_taps  host only: a Hamming-windowed sinc with its cutoff at 1.2 MHz, 8 D + 1 taps, symmetric, scaled
+ *                            to sum 2^15 (shift 15; sum |h| <= 65534).  Computed in double through libm: a property, not
+ *                            bits.  `cap` too small: ADSB_ERR_CAPACITY with the count in *n_taps.
+ * After a HIP failure the decimator's state is undefined until adsb_decim_reset. */
+typedef struct adsb_decim adsb_decim;
+#define ADSB_DECIM_CS16 0
+#define ADSB_DECIM_8BIT 1
+ADSB_MUST_CHECK int adsb_decim_create(adsb_ctx *ctx, uint32_t factor, const int16_t *taps, uint32_t n_taps, uint32_t shift,
+                                      adsb_decim **out);
+extern void adsb_decim_destroy(adsb_decim *d);
+ADSB_MUST_CHECK int adsb_decim_reset(adsb_decim *d);
+ADSB_MUST_CHECK int adsb_decim_out_count(const adsb_decim *d, size_t n_in, size_t *n_out);
+ADSB_MUST_CHECK int adsb_decim_run_device(adsb_decim *d, int format, const void *device_in, size_t n_in, void *device_out_cs16,
+                                          size_t out_cap, size_t *n_out);
+ADSB_MUST_CHECK int adsb_decim_demod_iq(adsb_decim *d, int format, const void *host_iq, size_t n_in, adsb_msg *out, size_t cap,
+                                        size_t *n_out);
+ADSB_MUST_CHECK int adsb_decim_default_taps(uint32_t factor, int16_t *taps, size_t cap, uint32_t *n_taps, uint32_t *shift);
+/* Host only, for the tests: the outputs one workgroup of the decimating kernel takes. */
+uint32_t adsb_decim_selftest_tile(void);
+
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167
  * is one stream with one process-global filter, src/icao_filter.rs:8-9).  Shards run

@@ -120,6 +120,15 @@ pub struct AdsbCtx {
     _private: [u8; 0],
 }
 
+/// An integer FIR decimator in front of the scan, for IQ sampled at a multiple of 2.4 MS/s (`adsb_decim_*`).
+#[repr(C)]
+pub struct AdsbDecim {
+    _private: [u8; 0],
+}
+
+pub const ADSB_DECIM_CS16: i32 = 0;
+pub const ADSB_DECIM_8BIT: i32 = 1;
+
 /// One capture over several GPUs from one process: one handle, one filter (`adsb_multi_*`).
 #[repr(C)]
 pub struct AdsbMulti {
@@ -235,6 +244,7 @@ unsafe extern "C" {
     pub fn adsb_strerror(status: c_int) -> *const c_char;
     pub fn adsb_last_error(ctx: *const AdsbCtx) -> *const c_char;
     pub fn adsb_version() -> *const c_char;
+    pub fn adsb_decim_selftest_tile() -> u32;
 }
 
 // The two calls that take the signal records by pointer (the header marks them ADSB_MUST_CHECK); compared with the
@@ -243,4 +253,17 @@ unsafe extern "C" {
 unsafe extern "C" {
     pub fn adsb_fetch_signal_stats(ctx: *mut AdsbCtx, out: *mut AdsbSignalStats, cap: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_signal_summary(s: *const AdsbSignalStats, n: usize, out: *mut AdsbSignalSummary) -> c_int;
+}
+
+// The decimator's calls, which take its handle (the header marks them ADSB_MUST_CHECK, the destructor `extern`); compared
+// with the header by tests/test_decim_cpu.py.
+#[link(name = "adsb_hip")]
+unsafe extern "C" {
+    pub fn adsb_decim_create(ctx: *mut AdsbCtx, factor: u32, taps: *const i16, n_taps: u32, shift: u32, out: *mut *mut AdsbDecim) -> c_int;
+    pub fn adsb_decim_destroy(d: *mut AdsbDecim);
+    pub fn adsb_decim_reset(d: *mut AdsbDecim) -> c_int;
+    pub fn adsb_decim_out_count(d: *const AdsbDecim, n_in: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_decim_run_device(d: *mut AdsbDecim, format: c_int, device_in: *const c_void, n_in: usize, device_out_cs16: *mut c_void, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_decim_demod_iq(d: *mut AdsbDecim, format: c_int, host_iq: *const c_void, n_in: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_decim_default_taps(factor: u32, taps: *mut i16, cap: usize, n_taps: *mut u32, shift: *mut u32) -> c_int;
 }
