@@ -436,9 +436,7 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
                 // ... which reads CS16: the buffer and the lead-in it takes from src, widened into a staging buffer
                 // first (in stream order in front of the pass; the pass is finished before the next buffer's turn)
                 const uint64_t lead = ch > 0 ? kCarrySamples : 0;
-                if (!c->d_widen)
-                    if (hipError_t e = hipMalloc((void **)&c->d_widen, ((size_t)kChunkSamples + kCarrySamples) * sizeof(uint32_t)))
-                        rc = fail(c, e, "hipMalloc");
+                rc = ensure_widen(c);
                 if (rc == 0)
                     if (int e = launch_widen_u8(sl.src, off - lead, (uint32_t)(n + lead), c->d_u8_table, c->d_widen, c->scan_stream[0]))
                         rc = fail(c, (hipError_t)e, "launch_widen_u8");

@@ -1,4 +1,4 @@
-// adsb_context.cpp -- context lifetime, the stream pool, settings and diagnostics (include/adsb_hip.h).
+// adsb_context.cpp -- context lifetime, the registry, the stream pool, settings and diagnostics (include/adsb_hip.h).
 //
 // The functions of the library mirror the reference's library API for the path (src/utils.rs:43 to_mag,
 // src/demod_2400.rs:115 demodulate2400, src/icao_filter.rs:11 icao_flush); what each one replaces is
@@ -40,7 +40,8 @@ struct DeviceStreams {
     std::vector<hipStream_t> free_own;     // normal priority: a context's own stream (input order, host-pointer copies)
 };
 std::mutex g_streams_mu;
-std::vector<DeviceStreams *> g_device_streams;   // (never freed: the streams live as long as the process)
+// (never freed, not even at exit, so that leak checkers see the pools as reachable: the streams live as long as the process)
+std::vector<DeviceStreams *> &g_device_streams = *new std::vector<DeviceStreams *>;
 
 // A stream with a hardware queue of its own.  The runtime maps the streams of a process onto at most four hardware queues
 // per priority (GPU_MAX_HW_QUEUES): the fifth stream of a priority shares the queue of an earlier one -- whichever has the
@@ -60,17 +61,20 @@ hipError_t dedicated_stream(int device, hipStream_t *out)
     return hipExtStreamCreateWithCUMask(out, (uint32_t)mask.size(), mask.data());
 }
 
-// under g_streams_mu, the device current
+// under g_streams_mu, the device current.  Every stream is made where it is still missing, so a call that failed halfway
+// is completed by the next one.
 int device_streams(adsb_ctx *c, int device, bool small, DeviceStreams **out)
 {
     DeviceStreams *d = nullptr;
     for (DeviceStreams *e : g_device_streams)
         if (e->device == device) d = e;
     if (!d) {
+        int least = 0, greatest = 0;
+        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        g_device_streams.reserve(g_device_streams.size() + 1);
         d = new (std::nothrow) DeviceStreams;
         if (!d) return ADSB_ERR_NOMEM;
-        d->device = device;
-        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&d->least, &d->greatest));
+        d->device = device, d->least = least, d->greatest = greatest;
         g_device_streams.push_back(d);
     }
     // The two scan streams take the highest priority: that pool holds nothing else of this process (the null stream,
@@ -81,27 +85,29 @@ int device_streams(adsb_ctx *c, int device, bool small, DeviceStreams **out)
     // (measurement aid, tuning builds: ADSB_POOL_LARGE=1 the two scan streams of large contexts with a hardware queue each
     // instead of the highest priority, =2 the tail and score streams as well)
     const int large_variant = tuning_env("ADSB_POOL_LARGE") ? std::atoi(tuning_env("ADSB_POOL_LARGE")) : 0;
-    if (!d->high[0])
-        for (auto &q : d->high) {
-            if (large_variant >= 1) HIP_TRY(c, dedicated_stream(device, &q));
-            else HIP_TRY(c, hipStreamCreateWithPriority(&q, hipStreamNonBlocking, d->greatest));
-        }
+    for (auto &q : d->high) {
+        if (q) continue;
+        if (large_variant >= 1) HIP_TRY(c, dedicated_stream(device, &q));
+        else HIP_TRY(c, hipStreamCreateWithPriority(&q, hipStreamNonBlocking, d->greatest));
+    }
     if (!d->n_low) {
         const int n = 2;
         for (int k = 0; k < 4; k++) {
             if (k >= n) d->low[k] = d->low[k % n];
+            else if (d->low[k]) continue;
             else if (large_variant >= 2) HIP_TRY(c, dedicated_stream(device, &d->low[k]));
             else HIP_TRY(c, hipStreamCreateWithPriority(&d->low[k], hipStreamNonBlocking, d->least));
         }
         d->n_low = n;
     }
-    if (small && !d->small[0]) {
+    if (small) {
         // (measurement aid, tuning builds: 0 the two high-priority streams + two more, 1 those two + two of normal
         // priority, 2 four of normal priority, 3 four high-priority ones of its own, 4 four of the lowest priority,
         // 5 four streams with a hardware queue each: hipExtStreamCreateWithCUMask, every CU enabled)
         const int variant = tuning_env("ADSB_POOL_SMALL") ? std::atoi(tuning_env("ADSB_POOL_SMALL")) : 5;
         const int mid = (d->least + d->greatest) / 2;
         for (int k = 0; k < kScanStreams; k++) {
+            if (d->small[k]) continue;
             const bool share = (variant == 0 || variant == 1) && k < 2;
             const int prio = variant == 0 || variant == 3 ? d->greatest : (variant == 4 ? d->least : mid);
             if (share) d->small[k] = d->high[k];
@@ -120,6 +126,259 @@ int device_streams(adsb_ctx *c, int device, bool small, DeviceStreams **out)
     return ADSB_OK;
 }
 
+}  // extern "C"
+
+// ---- the registry (adsb_ctx.h) ----
+static void free_entry(const Registry::Entry &en)
+{
+    if (en.kind == Registry::kDevice) (void)hipFree(en.p);
+    else if (en.kind == Registry::kPinned) (void)hipHostFree(en.p);
+    else (void)hipEventDestroy(static_cast<hipEvent_t>(en.p));
+    *en.home = nullptr;
+}
+
+// (the entry first: a reservation the vector has no room for is never made, so none is ever without its entry)
+hipError_t Registry::add(Kind kind, void **home, size_t arg)
+{
+    entries.push_back({kind, nullptr, home});
+    void *&p = entries.back().p;
+    const hipError_t e = kind == kDevice   ? hipMalloc(&p, arg)
+                         : kind == kPinned ? hipHostMalloc(&p, arg, hipHostMallocMapped | hipHostMallocCoherent)
+                                           : hipEventCreateWithFlags(reinterpret_cast<hipEvent_t *>(&p), (unsigned)arg);
+    if (e != hipSuccess) entries.pop_back();
+    else *home = p;
+    return e;
+}
+
+void Registry::release(void **home)
+{
+    for (size_t k = entries.size(); k-- > 0;)
+        if (entries[k].home == home) {
+            free_entry(entries[k]);
+            entries.erase(entries.begin() + (long)k);
+            return;
+        }
+}
+
+void Registry::release_from(size_t mark)
+{
+    for (; entries.size() > mark; entries.pop_back()) free_entry(entries.back());
+}
+
+// ---- adsb_create, step by step (in this order; adsb_destroy undoes whatever a failed step leaves) ----
+namespace {
+
+// How many passes in flight, streams and list entries a context of c->max_chunks buffers gets (the device is current).
+void size_lists(adsb_ctx *c)
+{
+    const size_t max_chunks = c->max_chunks;
+    // (a context for passes of a few buffers: one launch each, eight in flight -- adsb_ctx.h)
+    c->n_slots = max_chunks <= kInlineTailChunks ? ADSB_MAX_IN_FLIGHT_SMALL : ADSB_MAX_IN_FLIGHT;
+    c->n_bitmaps = c->n_slots + 1;
+    c->n_scan_streams = c->n_slots == ADSB_MAX_IN_FLIGHT_SMALL ? kScanStreams : 2;
+    c->bitmap_lg = c->n_slots == ADSB_MAX_IN_FLIGHT_SMALL ? kSmallBitmapLg : kFullBitmapLg;
+    if (const char *ds = tuning_env("ADSB_DEBUG_STOP")) c->debug_stop = std::atoi(ds);
+    if (const char *st = tuning_env("ADSB_STAGGER")) c->stagger_ticks = (uint32_t)std::atoi(st);
+    // The fast scan's AP list: one private segment per wave of every persistent workgroup (a pass
+    // of n buffers runs min(17 n, resident grid) workgroups of four waves, so a small context only gets
+    // the segments it can ever use), each sized for ~5x the rate pure noise produces (2.3 % of
+    // samples become address/parity entries).  Denser input falls back to buffer-by-buffer
+    // passes through the reference-shaped kernel, whose list (dap) and the hit list hold one
+    // buffer's worst case: every position sliced, five trials each.
+    const uint64_t used_segs = 4 * std::min<uint64_t>((uint64_t)scan_resident_blocks(), max_chunks * (uint64_t)fastgeo::kTilesPerChunk);
+    c->seg_cap = (uint32_t)std::max<uint64_t>(1024, (max_chunks * (uint64_t)kChunkSamples / 8 + used_segs - 1) / used_segs);
+    c->ap_cap = (uint32_t)(used_segs * c->seg_cap);
+    // hit list: ~5x what a busy airspace produces (a frame leaves 3-4 trial records; 1000 frames/s
+    // are ~55 per buffer); more than that is the fallback's business too
+    c->hits_cap = (uint32_t)(4096 + max_chunks * 1024);
+    // device-side scoring (shared by the passes: they go through it one after the other on the tail stream); passes of
+    // more hits than `cap` are scored on the host.  A context for passes of a few buffers never orders or scores on the
+    // device -- its passes are one launch each, replayed by the host in microseconds -- and carries none of it: no exact
+    // bitmaps, no scoring buffers, no message slots in its pinned block.
+    ScoreDev &cd = c->score;   // cap / hash_mask / exact: the context's; the rest per slot
+    const bool scoring = c->n_slots != ADSB_MAX_IN_FLIGHT_SMALL;
+    cd.cap = scoring ? std::min<uint32_t>(c->hits_cap, 262144u) : 0u;   // (a 2 GiB shard of a busy sky leaves 135 000)
+    cd.hash_mask = score_hash_size(cd.cap) - 1;
+}
+
+int take_streams(adsb_ctx *c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (tuning_env("ADSB_STREAM_PRIO") || tuning_env("ADSB_SCORE_PRIO")) {
+        // measurement aid (tuning builds): streams of this context's own, "tail,scan0,scan1" as 0 (least) .. 2
+        int least = 0, greatest = 0;
+        HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        int pt = least, p0 = greatest, p1 = greatest, ps = least;
+        if (const char *e = tuning_env("ADSB_STREAM_PRIO")) {
+            int a = 0, b = 1, d = 2;
+            if (std::sscanf(e, "%d,%d,%d", &a, &b, &d) == 3) {
+                const int lv[3] = {least, (least + greatest) / 2, greatest};
+                pt = lv[a % 3], p0 = lv[b % 3], p1 = lv[d % 3];
+            }
+        }
+        if (const char *e = tuning_env("ADSB_SCORE_PRIO")) ps = std::atoi(e) == 2 ? greatest : (std::atoi(e) == 1 ? (least + greatest) / 2 : least);
+        c->private_streams = true;
+        HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        HIP_TRY(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, pt));
+        for (int k = 0; k < c->n_scan_streams; k++) HIP_TRY(c, hipStreamCreateWithPriority(&c->scan_stream[k], hipStreamNonBlocking, k & 1 ? p1 : p0));
+        HIP_TRY(c, hipStreamCreateWithPriority(&c->score_stream, hipStreamNonBlocking, ps));
+    } else {
+        std::lock_guard<std::mutex> lk(g_streams_mu);
+        DeviceStreams *ds = nullptr;
+        const bool small = c->n_scan_streams == kScanStreams;
+        if (int rc = device_streams(c, c->device, small, &ds)) return rc;
+        for (int k = 0; k < c->n_scan_streams; k++) c->scan_stream[k] = small ? ds->small[k] : ds->high[k];
+        c->tail_stream = ds->low[ds->next_low++ & 3u];
+        c->score_stream = ds->low[ds->next_low++ & 3u];
+        if (!ds->free_own.empty()) {
+            c->own_stream = ds->free_own.back();
+            ds->free_own.pop_back();
+        } else {
+            HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        }
+    }
+    c->stream = c->own_stream;
+    return ADSB_OK;
+}
+
+// The address supersets, every slot's device lists (zero where a pass expects zero), and the events.
+int reserve_lists_and_events(adsb_ctx *c)
+{
+    const size_t max_chunks = c->max_chunks;
+    for (auto &e : c->input_ready) HIP_TRY(c, new_event(c, &e, kQuietEvent));
+    HIP_TRY(c, new_event(c, &c->lazy_ev, kQuietEvent));
+    for (int k = 0; k < c->n_bitmaps; k++) HIP_TRY(c, dev_alloc(c, &c->d_bitmap[k], bitmap_alloc_words(c->bitmap_lg) * sizeof(uint32_t)));
+    const bool fenced = tuning_env("ADSB_DONE_FENCE") != nullptr;  // measurement aid only
+    for (int si = 0; si < c->n_slots; si++) {
+        Slot &sl = c->slot[si];
+        sl.hits_cap = c->hits_cap;
+        const size_t cnt_bytes = (max_chunks * fastgeo::kTilesPerChunk + 1) * sizeof(uint32_t);
+        HIP_TRY(c, dev_alloc(c, &sl.d_ctr, sizeof(Counters)));
+        HIP_TRY(c, dev_alloc(c, &sl.d_hits, (size_t)c->hits_cap * sizeof(uint64_t)));
+        HIP_TRY(c, dev_alloc(c, &sl.d_hit_fields, (size_t)c->hits_cap * kHitFieldWords * sizeof(uint32_t)));
+        HIP_TRY(c, dev_alloc(c, &sl.d_ap, (size_t)c->ap_cap * sizeof(uint64_t)));
+        HIP_TRY(c, dev_alloc(c, &sl.d_order_cnt, cnt_bytes));
+        HIP_TRY(c, hipMemset(sl.d_order_cnt, 0, cnt_bytes));
+        HIP_TRY(c, dev_alloc(c, &sl.d_order_base, (max_chunks + 1) * sizeof(uint32_t)));
+        HIP_TRY(c, dev_alloc(c, &sl.d_order_tmp, (size_t)c->hits_cap * sizeof(uint64_t)));
+        HIP_TRY(c, dev_alloc(c, &sl.d_carry, kCarrySamples * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemset(sl.d_carry, 0, kCarrySamples * sizeof(uint32_t)));
+        HIP_TRY(c, new_event(c, &sl.scanned, kQuietEvent));
+        HIP_TRY(c, new_event(c, &sl.recorded, kQuietEvent));
+        // timing-only events: no system-scope fence when they complete (~10 us each otherwise)
+        for (int k = 2; k < 5; k++) HIP_TRY(c, new_event(c, &sl.ev[k], hipEventDisableSystemFence));
+        // (the slot's summary and records live in the context's one pinned block: mapped + coherent, so the records
+        // kernel's write-through stores are visible to the host when its completion event fires)
+        HIP_TRY(c, new_event(c, &sl.done, fenced ? hipEventDisableTiming : kQuietEvent));
+    }
+    HIP_TRY(c, dev_alloc(c, &c->d_carry_next, kCarrySamples * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(c->d_carry_next, 0, kCarrySamples * sizeof(uint32_t)));
+    for (auto &pair : c->scan_ev)
+        for (auto &e : pair) HIP_TRY(c, new_event(c, &e, hipEventDisableSystemFence));
+    for (auto &e : c->redo_ev) HIP_TRY(c, new_event(c, &e, hipEventDisableSystemFence));
+    if (tuning_env("ADSB_TIMELINE")) {
+        // 1: stamps of 8 blocks x 8 tiles; 2 (with ADSB_DEBUG_STOP=100): per-wave phase totals
+        HIP_TRY(c, dev_alloc(c, &c->d_timeline, kTimelineWords * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemset(c->d_timeline, 0, kTimelineWords * sizeof(unsigned long long)));
+    }
+    return ADSB_OK;
+}
+
+// The two exact bitmaps and every slot's scoring buffers (a context that scores on the device: size_lists).
+int reserve_scoring(adsb_ctx *c)
+{
+    ScoreDev &cd = c->score;
+    if (cd.cap) {
+        for (auto &bm : c->exact_bm) {
+            HIP_TRY(c, dev_alloc(c, &bm, kBitmapAllocWords * sizeof(uint32_t)));
+            HIP_TRY(c, hipMemset(bm, 0, kBitmapAllocWords * sizeof(uint32_t)));
+        }
+        cd.exact = c->exact_bm[0];
+        cd.si = reinterpret_cast<uint32_t *>(cd.exact);  // (non-null: "scoring is available")
+    }
+    const size_t hsize = (size_t)cd.hash_mask + 1;
+    for (int si = 0; si < c->n_slots; si++) {
+        ScoreDev &sd = c->slot[si].score;
+        sd = cd;
+        if (!cd.cap) continue;
+        HIP_TRY(c, dev_alloc(c, &sd.si, (size_t)sd.cap * sizeof(uint32_t)));
+        HIP_TRY(c, dev_alloc(c, &sd.rec, (size_t)sd.cap * sizeof(TrialRecord)));
+        HIP_TRY(c, dev_alloc(c, &sd.flag, (size_t)sd.cap * sizeof(uint32_t)));
+        HIP_TRY(c, dev_alloc(c, &sd.pos, (size_t)sd.cap * sizeof(unsigned long long)));
+        HIP_TRY(c, dev_alloc(c, &sd.slot, (size_t)sd.cap * sizeof(uint32_t)));
+        HIP_TRY(c, dev_alloc(c, &sd.hash, hsize * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemset(sd.hash, 0xFF, hsize * sizeof(unsigned long long)));
+        HIP_TRY(c, dev_alloc(c, &sd.blk, 2 * kScoreBlocks * sizeof(uint32_t)));
+        HIP_TRY(c, dev_alloc(c, &sd.state, sizeof(ScoreState)));
+        HIP_TRY(c, hipMemset(sd.state, 0, sizeof(ScoreState)));
+    }
+    return ADSB_OK;
+}
+
+// The host side of every slot -- summary, score summary, additions, records, messages: mapped, coherent, written by the
+// kernels with write-through stores -- as ONE pinned allocation per context, cut up here.
+// (five separate allocations per slot were forty small pinned regions in a one-buffer context)
+int carve_host_block(adsb_ctx *c)
+{
+    const size_t cap = c->score.cap;
+    const size_t o_ssum = up256(sizeof(Summary)), o_adds = o_ssum + up256(sizeof(ScoreSummary)),
+                 o_rec = o_adds + up256(cap * sizeof(uint32_t)), o_msgs = o_rec + up256((size_t)c->hits_cap * sizeof(TrialRecord)),
+                 per_slot = o_msgs + up256(cap * sizeof(adsb_msg));
+    HIP_TRY(c, pinned_alloc(c, &c->h_block, &c->h_block_dev, per_slot * (size_t)c->n_slots));
+    for (int si = 0; si < c->n_slots; si++) {
+        Slot &sl = c->slot[si];
+        char *h = c->h_block + per_slot * (size_t)si, *d = c->h_block_dev + per_slot * (size_t)si;
+        sl.h_sum = reinterpret_cast<Summary *>(h), sl.h_sum_dev = reinterpret_cast<Summary *>(d);
+        sl.h_ssum = reinterpret_cast<ScoreSummary *>(h + o_ssum), sl.h_ssum_dev = reinterpret_cast<ScoreSummary *>(d + o_ssum);
+        sl.h_adds = reinterpret_cast<uint32_t *>(h + o_adds), sl.h_adds_dev = reinterpret_cast<uint32_t *>(d + o_adds);
+        sl.h_rec = reinterpret_cast<TrialRecord *>(h + o_rec), sl.h_rec_dev = reinterpret_cast<TrialRecord *>(d + o_rec);
+        sl.h_msgs = reinterpret_cast<adsb_msg *>(h + o_msgs), sl.h_msgs_dev = reinterpret_cast<adsb_msg *>(d + o_msgs);
+        std::memset(sl.h_sum, 0, sizeof(Summary));
+        std::memset(sl.h_ssum, 0, sizeof(ScoreSummary));
+    }
+    return ADSB_OK;
+}
+
+// The kernels' lookup tables and the CU8 widening table, built on the host and copied once.
+int upload_tables(adsb_ctx *c)
+{
+    std::vector<uint32_t> tab = build_gf_tables();
+    const std::vector<uint32_t> r16 = build_r16(), ft = build_field_table(fast_plane_bytes()), bits = build_bit_residuals();
+    tab.insert(tab.end(), r16.begin(), r16.end());
+    tab.insert(tab.end(), ft.begin(), ft.end());
+    tab.insert(tab.end(), bits.begin(), bits.end());
+    uint32_t fix_mult = 0;
+    const std::vector<uint32_t> fix = build_fix_table(&fix_mult);
+    tab.insert(tab.end(), fix.begin(), fix.end());
+    tab.push_back(fix_mult);
+    tab.resize(kTabFix2Off, 0u);
+    const std::vector<uint32_t> fix2 = build_fix2_table();
+    tab.insert(tab.end(), fix2.begin(), fix2.end());
+    HIP_TRY(c, dev_alloc(c, &c->d_tables, kTabWords * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpy(c->d_tables, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    int16_t t[256];
+    soapy_u8_table(t);
+    HIP_TRY(c, dev_alloc(c, &c->d_u8_table, 256 * sizeof(uint16_t)));
+    HIP_TRY(c, hipMemcpy(c->d_u8_table, t, sizeof t, hipMemcpyHostToDevice));
+    return ADSB_OK;
+}
+
+// Every bitmap clean and every counter block zero to start with; from then on each pass cleans up for the next (the
+// first pass needs no flush of its own).
+int initial_resets(adsb_ctx *c)
+{
+    for (int k = 0; k < c->n_bitmaps; k++)
+        if (int e = launch_reset(c->slot[k % (uint64_t)c->n_slots].d_ctr, c->d_bitmap[k], c->bitmap_lg, c->stream))
+            return fail(c, (hipError_t)e, "launch_reset");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->flush_pending = false;
+    return ADSB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int adsb_create(adsb_ctx **out, int device, size_t max_chunks)
 try {
     if (!out) return ADSB_ERR_INVALID;
@@ -136,205 +395,16 @@ try {
         if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return ADSB_ERR_NO_DEVICE;
     }
-
+    DeviceGuard on_device(device);  // (scan_resident_blocks() asks the current device; the caller's is put back on the way out)
+    if (on_device.err != hipSuccess) return ADSB_ERR_NO_DEVICE;
     adsb_ctx *c = new (std::nothrow) adsb_ctx;
     if (!c) return ADSB_ERR_NOMEM;
     c->device = device;
     c->max_chunks = max_chunks;
-    // (a context for passes of a few buffers: one launch each, eight in flight -- adsb_ctx.h)
-    c->n_slots = max_chunks <= kInlineTailChunks ? ADSB_MAX_IN_FLIGHT_SMALL : ADSB_MAX_IN_FLIGHT;
-    c->n_bitmaps = c->n_slots + 1;
-    c->n_scan_streams = c->n_slots == ADSB_MAX_IN_FLIGHT_SMALL ? kScanStreams : 2;
-    c->bitmap_lg = c->n_slots == ADSB_MAX_IN_FLIGHT_SMALL ? kSmallBitmapLg : kFullBitmapLg;
-    if (const char *ds = tuning_env("ADSB_DEBUG_STOP")) c->debug_stop = std::atoi(ds);
-    if (const char *st = tuning_env("ADSB_STAGGER")) c->stagger_ticks = (uint32_t)std::atoi(st);
-    // The fast scan's AP list: one private segment per wave of every persistent workgroup (a pass
-    // of n buffers runs min(17 n, resident grid) workgroups of four waves, so a small context only gets
-    // the segments it can ever use), each sized for ~5x the rate pure noise produces (2.3 % of
-    // samples become address/parity entries).  Denser input falls back to buffer-by-buffer
-    // passes through the reference-shaped kernel, whose list (dap) and the hit list hold one
-    // buffer's worst case: every position sliced, five trials each.
-    DeviceGuard on_device(device);  // (scan_resident_blocks() asks the current device; the caller's is put back on the way out)
-    if (on_device.err != hipSuccess) {
-        delete c;
-        return ADSB_ERR_NO_DEVICE;
-    }
-    const uint64_t used_segs = 4 * std::min<uint64_t>((uint64_t)scan_resident_blocks(), max_chunks * (uint64_t)fastgeo::kTilesPerChunk);
-    c->seg_cap = (uint32_t)std::max<uint64_t>(1024, (max_chunks * (uint64_t)kChunkSamples / 8 + used_segs - 1) / used_segs);
-    c->ap_cap = (uint32_t)(used_segs * c->seg_cap);
-    // hit list: ~5x what a busy airspace produces (a frame leaves 3-4 trial records; 1000 frames/s
-    // are ~55 per buffer); more than that is the fallback's business too
-    c->hits_cap = (uint32_t)(4096 + max_chunks * 1024);
-
+    size_lists(c);
     int rc = ADSB_OK;
-    auto body = [&]() -> int {
-        HIP_TRY(c, hipSetDevice(device));
-        if (tuning_env("ADSB_STREAM_PRIO") || tuning_env("ADSB_SCORE_PRIO")) {
-            // measurement aid (tuning builds): streams of this context's own, "tail,scan0,scan1" as 0 (least) .. 2
-            int least = 0, greatest = 0;
-            HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-            int pt = least, p0 = greatest, p1 = greatest, ps = least;
-            if (const char *e = tuning_env("ADSB_STREAM_PRIO")) {
-                int a = 0, b = 1, d = 2;
-                if (std::sscanf(e, "%d,%d,%d", &a, &b, &d) == 3) {
-                    const int lv[3] = {least, (least + greatest) / 2, greatest};
-                    pt = lv[a % 3], p0 = lv[b % 3], p1 = lv[d % 3];
-                }
-            }
-            if (const char *e = tuning_env("ADSB_SCORE_PRIO")) ps = std::atoi(e) == 2 ? greatest : (std::atoi(e) == 1 ? (least + greatest) / 2 : least);
-            c->private_streams = true;
-            HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-            HIP_TRY(c, hipStreamCreateWithPriority(&c->tail_stream, hipStreamNonBlocking, pt));
-            for (int k = 0; k < c->n_scan_streams; k++)
-                HIP_TRY(c, hipStreamCreateWithPriority(&c->scan_stream[k], hipStreamNonBlocking, k & 1 ? p1 : p0));
-            HIP_TRY(c, hipStreamCreateWithPriority(&c->score_stream, hipStreamNonBlocking, ps));
-        } else {
-            std::lock_guard<std::mutex> lk(g_streams_mu);
-            DeviceStreams *ds = nullptr;
-            const bool small = c->n_scan_streams == kScanStreams;
-            if (int rc2 = device_streams(c, device, small, &ds)) return rc2;
-            for (int k = 0; k < c->n_scan_streams; k++) c->scan_stream[k] = small ? ds->small[k] : ds->high[k];
-            c->tail_stream = ds->low[ds->next_low++ & 3u];
-            c->score_stream = ds->low[ds->next_low++ & 3u];
-            if (!ds->free_own.empty()) {
-                c->own_stream = ds->free_own.back();
-                ds->free_own.pop_back();
-            } else {
-                HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-            }
-        }
-        c->stream = c->own_stream;
-        for (auto &e : c->input_ready)
-            HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->lazy_ev, hipEventDisableTiming | hipEventDisableSystemFence));
-        for (int k = 0; k < c->n_bitmaps; k++) HIP_TRY(c, hipMalloc((void **)&c->d_bitmap[k], bitmap_alloc_words(c->bitmap_lg) * sizeof(uint32_t)));
-        for (int si = 0; si < c->n_slots; si++) {
-            Slot &sl = c->slot[si];
-            HIP_TRY(c, hipMalloc((void **)&sl.d_ctr, sizeof(Counters)));
-            sl.hits_cap = c->hits_cap;
-            HIP_TRY(c, hipMalloc((void **)&sl.d_hits, (size_t)c->hits_cap * sizeof(uint64_t)));
-            HIP_TRY(c, hipMalloc((void **)&sl.d_hit_fields, (size_t)c->hits_cap * kHitFieldWords * sizeof(uint32_t)));
-            HIP_TRY(c, hipMalloc((void **)&sl.d_ap, (size_t)c->ap_cap * sizeof(uint64_t)));
-            HIP_TRY(c, hipMalloc((void **)&sl.d_order_cnt, (max_chunks * fastgeo::kTilesPerChunk + 1) * sizeof(uint32_t)));
-            HIP_TRY(c, hipMemset(sl.d_order_cnt, 0, (max_chunks * fastgeo::kTilesPerChunk + 1) * sizeof(uint32_t)));
-            HIP_TRY(c, hipMalloc((void **)&sl.d_order_base, (max_chunks + 1) * sizeof(uint32_t)));
-            HIP_TRY(c, hipMalloc((void **)&sl.d_order_tmp, (size_t)c->hits_cap * sizeof(uint64_t)));
-            HIP_TRY(c, hipEventCreateWithFlags(&sl.scanned, hipEventDisableTiming | hipEventDisableSystemFence));
-            HIP_TRY(c, hipMalloc((void **)&sl.d_carry, kCarrySamples * sizeof(uint32_t)));
-            HIP_TRY(c, hipMemset(sl.d_carry, 0, kCarrySamples * sizeof(uint32_t)));
-        }
-        HIP_TRY(c, hipMalloc((void **)&c->d_carry_next, kCarrySamples * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemset(c->d_carry_next, 0, kCarrySamples * sizeof(uint32_t)));
-        {
-            // device-side scoring state (shared by the passes: they go through it one after the other
-            // on the tail stream); passes of more hits than `cap` are scored on the host
-            ScoreDev &cd = c->score;   // cap / hash_mask / exact: the context's; the rest per slot
-            // (a context for passes of a few buffers never orders or scores on the device -- its passes are one
-            // launch each, replayed by the host in microseconds -- and carries none of this: no exact bitmaps, no
-            // scoring buffers, no message slots in its pinned block)
-            const bool scoring = c->n_slots != ADSB_MAX_IN_FLIGHT_SMALL;
-            cd.cap = scoring ? std::min<uint32_t>(c->hits_cap, 262144u) : 0u;   // (a 2 GiB shard of a busy sky leaves 135 000)
-            const uint32_t hsize = score_hash_size(cd.cap);
-            cd.hash_mask = hsize - 1;
-            if (scoring) {
-                for (auto &bm : c->exact_bm) {
-                    HIP_TRY(c, hipMalloc((void **)&bm, kBitmapAllocWords * sizeof(uint32_t)));
-                    HIP_TRY(c, hipMemset(bm, 0, kBitmapAllocWords * sizeof(uint32_t)));
-                }
-                cd.exact = c->exact_bm[0];
-                cd.si = reinterpret_cast<uint32_t *>(cd.exact);  // (non-null: "scoring is available")
-            }
-            for (int si = 0; si < c->n_slots; si++) {
-                Slot &sl = c->slot[si];
-                ScoreDev &sd = sl.score;
-                sd = cd;
-                HIP_TRY(c, hipEventCreateWithFlags(&sl.recorded, hipEventDisableTiming | hipEventDisableSystemFence));
-                if (!scoring) continue;
-                HIP_TRY(c, hipMalloc((void **)&sd.si, (size_t)sd.cap * sizeof(uint32_t)));
-                HIP_TRY(c, hipMalloc((void **)&sd.rec, (size_t)sd.cap * sizeof(TrialRecord)));
-                HIP_TRY(c, hipMalloc((void **)&sd.flag, (size_t)sd.cap * sizeof(uint32_t)));
-                HIP_TRY(c, hipMalloc((void **)&sd.pos, (size_t)sd.cap * sizeof(unsigned long long)));
-                HIP_TRY(c, hipMalloc((void **)&sd.slot, (size_t)sd.cap * sizeof(uint32_t)));
-                HIP_TRY(c, hipMalloc((void **)&sd.hash, (size_t)hsize * sizeof(unsigned long long)));
-                HIP_TRY(c, hipMemset(sd.hash, 0xFF, (size_t)hsize * sizeof(unsigned long long)));
-                HIP_TRY(c, hipMalloc((void **)&sd.blk, 2 * kScoreBlocks * sizeof(uint32_t)));
-                HIP_TRY(c, hipMalloc((void **)&sd.state, sizeof(ScoreState)));
-                HIP_TRY(c, hipMemset(sd.state, 0, sizeof(ScoreState)));
-            }
-            // The host side of every slot -- summary, score summary, additions, records, messages: mapped, coherent,
-            // written by the kernels with write-through stores -- as ONE pinned allocation per context, cut up here.
-            // (five separate allocations per slot were forty small pinned regions in a one-buffer context)
-            const ScoreDev &sd = cd;
-            auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-            const size_t o_ssum = up(sizeof(Summary)), o_adds = o_ssum + up(sizeof(ScoreSummary)),
-                         o_rec = o_adds + up((size_t)sd.cap * sizeof(uint32_t)),
-                         o_msgs = o_rec + up((size_t)c->hits_cap * sizeof(TrialRecord)),
-                         per_slot = o_msgs + up((size_t)sd.cap * sizeof(adsb_msg));
-            HIP_TRY(c, hipHostMalloc((void **)&c->h_block, per_slot * (size_t)c->n_slots, hipHostMallocMapped | hipHostMallocCoherent));
-            HIP_TRY(c, hipHostGetDevicePointer((void **)&c->h_block_dev, c->h_block, 0));
-            for (int si = 0; si < c->n_slots; si++) {
-                Slot &sl = c->slot[si];
-                char *h = c->h_block + per_slot * (size_t)si, *d = c->h_block_dev + per_slot * (size_t)si;
-                sl.h_sum = reinterpret_cast<Summary *>(h), sl.h_sum_dev = reinterpret_cast<Summary *>(d);
-                sl.h_ssum = reinterpret_cast<ScoreSummary *>(h + o_ssum), sl.h_ssum_dev = reinterpret_cast<ScoreSummary *>(d + o_ssum);
-                sl.h_adds = reinterpret_cast<uint32_t *>(h + o_adds), sl.h_adds_dev = reinterpret_cast<uint32_t *>(d + o_adds);
-                sl.h_rec = reinterpret_cast<TrialRecord *>(h + o_rec), sl.h_rec_dev = reinterpret_cast<TrialRecord *>(d + o_rec);
-                sl.h_msgs = reinterpret_cast<adsb_msg *>(h + o_msgs), sl.h_msgs_dev = reinterpret_cast<adsb_msg *>(d + o_msgs);
-                std::memset(sl.h_sum, 0, sizeof(Summary));
-                std::memset(sl.h_ssum, 0, sizeof(ScoreSummary));
-            }
-        }
-        HIP_TRY(c, hipMalloc((void **)&c->d_tables, kTabWords * sizeof(uint32_t)));
-        {
-            std::vector<uint32_t> tab = build_gf_tables();
-            const std::vector<uint32_t> r16 = build_r16(), ft = build_field_table(fast_plane_bytes()),
-                                        bits = build_bit_residuals();
-            tab.insert(tab.end(), r16.begin(), r16.end());
-            tab.insert(tab.end(), ft.begin(), ft.end());
-            tab.insert(tab.end(), bits.begin(), bits.end());
-            uint32_t fix_mult = 0;
-            const std::vector<uint32_t> fix = build_fix_table(&fix_mult);
-            tab.insert(tab.end(), fix.begin(), fix.end());
-            tab.push_back(fix_mult);
-            tab.resize(kTabFix2Off, 0u);
-            const std::vector<uint32_t> fix2 = build_fix2_table();
-            tab.insert(tab.end(), fix2.begin(), fix2.end());
-            HIP_TRY(c, hipMemcpy(c->d_tables, tab.data(), tab.size() * sizeof(uint32_t),
-                                 hipMemcpyHostToDevice));
-        }
-        HIP_TRY(c, hipMalloc((void **)&c->d_u8_table, 256 * sizeof(uint16_t)));
-        {
-            int16_t t[256];
-            soapy_u8_table(t);
-            HIP_TRY(c, hipMemcpy(c->d_u8_table, t, sizeof t, hipMemcpyHostToDevice));
-        }
-        for (int si = 0; si < c->n_slots; si++) {
-            Slot &sl = c->slot[si];
-            // (the slot's summary and records live in the context's one pinned block: mapped + coherent, so the records
-            // kernel's write-through stores are visible to the host when its completion event fires)
-            // timing-only events: no system-scope fence when they complete (~10 us each otherwise)
-            for (int k = 2; k < 5; k++) HIP_TRY(c, hipEventCreateWithFlags(&sl.ev[k], hipEventDisableSystemFence));
-            const bool fenced = tuning_env("ADSB_DONE_FENCE") != nullptr;  // measurement aid only
-            HIP_TRY(c, hipEventCreateWithFlags(&sl.done, fenced ? hipEventDisableTiming : (hipEventDisableTiming | hipEventDisableSystemFence)));
-        }
-        for (auto &pair : c->scan_ev)
-            for (auto &e : pair) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-        for (auto &e : c->redo_ev) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-        if (tuning_env("ADSB_TIMELINE")) {
-            // 1: stamps of 8 blocks x 8 tiles; 2 (with ADSB_DEBUG_STOP=100): per-wave phase totals
-            HIP_TRY(c, hipMalloc((void **)&c->d_timeline, kTimelineWords * sizeof(unsigned long long)));
-            HIP_TRY(c, hipMemset(c->d_timeline, 0, kTimelineWords * sizeof(unsigned long long)));
-        }
-        // both bitmaps clean and both counter blocks zero to start with; from then on each
-        // pass cleans up for the next (the first pass needs no flush of its own)
-        for (int k = 0; k < c->n_bitmaps; k++)
-            if (int e = launch_reset(c->slot[k % (uint64_t)c->n_slots].d_ctr, c->d_bitmap[k], c->bitmap_lg, c->stream))
-                return fail(c, (hipError_t)e, "launch_reset");
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->flush_pending = false;
-        return (int)ADSB_OK;
-    };
-    rc = body();
+    for (auto step : {take_streams, reserve_lists_and_events, reserve_scoring, carve_host_block, upload_tables, initial_resets})
+        if (rc == ADSB_OK) rc = step(c);
     if (rc != ADSB_OK) {
         std::fprintf(stderr, "adsb_create: %s\n", c->last_error.c_str());
         adsb_destroy(c);
@@ -349,28 +419,219 @@ try {
 namespace adsb {
 namespace host {
 
+// ---- what a tuning build prints at destroy: the host-times table (ADSB_HOST_TIMES; tools/hosttime.py parses it) and the
+// timelines the scan kernels stamp into adsb_ctx::d_timeline (ADSB_TIMELINE) ----
+static void print_host_times(const adsb_ctx *c)
+{
+#ifdef ADSB_TUNING
+    if (tuning_env("ADSB_HOST_TIMES")) {
+        std::fprintf(stderr, "host times over %llu passes: enqueue %.1f us, wait %.1f us, replay %.1f us per pass\n",
+                     (unsigned long long)c->collected, 1e6 * c->t_enqueue / (c->collected ? c->collected : 1),
+                     1e6 * c->t_wait / (c->collected ? c->collected : 1), 1e6 * c->t_replay / (c->collected ? c->collected : 1));
+        static const char *name[HT_COUNT] = {"ring: hipMemcpyAsync", "ring: (unused)", "input-ready record + wait",
+                                             "scan launch", "scanned record + waits", "match (+ order) launch", "records launch",
+                                             "recorded / done records", "collect: wait for the pass", "collect: record checksum",
+                                             "collect: replay"};
+        double all = 0;
+        for (int k = 0; k < HT_COUNT; k++) all += c->ht_s[k];
+        for (int k = 0; k < HT_COUNT; k++)
+            if (c->ht_n[k])
+                std::fprintf(stderr, "  %-32s %8.2f us per pass  (%llu calls, %.2f us each)  %5.1f %%\n", name[k],
+                             1e6 * c->ht_s[k] / (c->collected ? c->collected : 1), (unsigned long long)c->ht_n[k],
+                             1e6 * c->ht_s[k] / c->ht_n[k], 100.0 * c->ht_s[k] / (all > 0 ? all : 1));
+    }
+#endif
+    (void)c;
+}
+
+// ADSB_TIMELINE=3: the stamps of the last one-launch pass (100 MHz wall clock)
+static void dump_onelaunch_timeline(const adsb_ctx *c)
+{
+    unsigned long long t[10] = {};
+    if (hipMemcpy(t, c->d_timeline + 448, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess && t[0]) {
+        if (t[8] > t[4] && t[7] > t[8])
+            std::fprintf(stderr, "  one-launch pass, second look: fill counts in LDS +%.2f us, entries compared +%.2f us, fence +%.2f us\n",
+                         (double)(long long)(t[8] - t[4]) / 100.0, (double)(long long)(t[7] - t[8]) / 100.0,
+                         (double)(long long)(t[5] - t[7]) / 100.0);
+        static const char *name[7] = {"entry", "tables in LDS, first tile requested", "tiles done", "own entries matched",
+                                      "counted in (last workgroup from here on)", "second look done", "records + summary + counters"};
+        for (int k = 1; k < 7; k++)
+            std::fprintf(stderr, "  one-launch pass: %-45s +%6.2f us  (at %6.2f)\n", name[k],
+                         (double)(long long)(t[k] - t[k - 1]) / 100.0, (double)(long long)(t[k] - t[0]) / 100.0);
+    }
+    // ... and of the last sixteen, workgroup by workgroup: when the first and the last workgroup passed each
+    // stage, from the pass's first entry (passes in flight side by side: how they stretch each other)
+    std::vector<unsigned long long> w(16 * 32 * 8);
+    if (hipMemcpy(w.data(), c->d_timeline + 1024, w.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+        unsigned long long origin = ~0ull;
+        for (unsigned long long v : w) if (v && v < origin) origin = v;
+        for (int ps = 0; ps < 16; ps++) {
+            unsigned long long lo[8], hi[8] = {};
+            for (auto &v : lo) v = ~0ull;
+            for (int g = 0; g < 32; g++)
+                for (int k = 0; k < 8; k++) {
+                    const unsigned long long v = w[(ps * 32 + g) * 8 + k];
+                    if (!v) continue;
+                    lo[k] = std::min(lo[k], v);
+                    hi[k] = std::max(hi[k], v);
+                }
+            if (!hi[0]) continue;
+            std::fprintf(stderr, "  pass %2d entered at %8.2f us:", ps, (double)(lo[0] - origin) / 100.0);
+            for (int k = 0; k < 7; k++)
+                if (hi[k]) std::fprintf(stderr, "  s%d %.1f..%.1f", k, (double)(lo[k] - lo[0]) / 100.0, (double)(hi[k] - lo[0]) / 100.0);
+            std::fprintf(stderr, "\n");
+        }
+    }
+}
+
+// ADSB_DEBUG_STOP=100: phase / barrier-wait totals of the last scan, summed over all waves
+static void dump_scan_phases(const adsb_ctx *c)
+{
+    std::vector<unsigned long long> tl(kTimelineWords);
+    if (hipMemcpy(tl.data(), c->d_timeline, kTimelineWords * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+        double sum[8] = {0};
+        int nw = 0;
+        for (size_t w = 0; w < kTimelineWords / 8; w++) {
+            double tot = 0;
+            for (int k = 0; k < 8; k++) tot += (double)tl[w * 8 + k];
+            if (tot == 0) continue;
+            nw++;
+            for (int k = 0; k < 8; k++) sum[k] += (double)tl[w * 8 + k];
+        }
+        double all = 0;
+        for (double v : sum) all += v;
+        static const char *name[8] = {"P1", "wait B1", "P2", "wait B2", "P3-5", "wait B3", "epilogue", "wait B4"};
+        std::fprintf(stderr, "phase accounting over %d waves (clock64 ticks per wave, share):\n", nw);
+        for (int k = 0; k < 8; k++)
+            std::fprintf(stderr, "  %-9s %10.0f  %5.1f %%\n", name[k], sum[k] / (nw ? nw : 1), 100.0 * sum[k] / (all ? all : 1));
+        // ... and how evenly the work fell: a workgroup's total (its waves agree to a barrier wait) and its
+        // wave-private stage, over the workgroups -- the launch ends with the slowest one
+        std::vector<double> tot, late;
+        for (size_t w = 0; w + 3 < kTimelineWords / 8; w += 4) {
+            double t = 0, l = 0;
+            for (int k = 0; k < 8; k++) t += (double)tl[w * 8 + k];
+            for (size_t v = 0; v < 4; v++) l = std::max(l, (double)tl[(w + v) * 8 + 4]);
+            if (t == 0) continue;
+            tot.push_back(t);
+            late.push_back(l);
+        }
+        auto pct = [](std::vector<double> &v, double q) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[(size_t)(q * (double)(v.size() - 1))]; };
+        double mt = 0, ml = 0;
+        for (double v : tot) mt += v;
+        for (double v : late) ml += v;
+        mt /= tot.empty() ? 1 : (double)tot.size();
+        ml /= late.empty() ? 1 : (double)late.size();
+        std::fprintf(stderr, "  per workgroup (wave 0's total): mean %.0f  p50 %.0f  p99 %.0f  max %.0f  (max / mean %.3f)\n", mt, pct(tot, 0.5),
+                     pct(tot, 0.99), pct(tot, 1.0), mt > 0 ? pct(tot, 1.0) / mt : 0.0);
+        std::fprintf(stderr, "  per workgroup (its slowest wave's P3-5): mean %.0f  p50 %.0f  p99 %.0f  max %.0f  (max / mean %.3f)\n", ml,
+                     pct(late, 0.5), pct(late, 0.99), pct(late, 1.0), ml > 0 ? pct(late, 1.0) / ml : 0.0);
+    }
+}
+
+// otherwise: the stamps of the last scan
+static void dump_scan_stamps(const adsb_ctx *c)
+{
+    unsigned long long tl[512];
+    if (hipMemcpy(tl, c->d_timeline, sizeof(tl), hipMemcpyDeviceToHost) == hipSuccess)
+        for (int b = 0; b < 8; b++)
+            for (int it = 0; it < 8; it++) {
+                const unsigned long long *r = tl + (b * 8 + it) * 8;
+                if (!r[0]) continue;
+                std::fprintf(stderr, "timeline block %d tile %d: start %8lld |", b * 128, it,
+                             (long long)(r[0] - tl[0]));
+                for (int k = 1; k < 7; k++) std::fprintf(stderr, " %6lld", (long long)(r[k] - r[k - 1]));
+                std::fprintf(stderr, "  total %lld\n", (long long)(r[6] - r[0]));
+            }
+}
+
 // Signal statistics: per pass in flight max_chunks records in mapped host memory (written once each by k_signal_stats)
 // and as many partials plus a ticket per buffer in device memory, zero between passes.  Reserved the first time the mode
 // is enabled, so that a context that never enables it keeps the footprint include/adsb_hip.h documents.
 int ensure_signal_stats(adsb_ctx *c)
 {
-    if (c->h_sig_block && c->d_sig_block) return ADSB_OK;
-    const size_t rec_bytes = (c->max_chunks * sizeof(adsb_signal_stats) + 255) & ~(size_t)255;
+    if (c->d_sig_block) return ADSB_OK;   // (reserved last)
+    const size_t rec_bytes = up256(c->max_chunks * sizeof(adsb_signal_stats));
     const size_t part_words = c->max_chunks * (size_t)kSigRecordWords, slot_words = (part_words + c->max_chunks + 63) & ~(size_t)63;
-    char *h_dev = nullptr;
-    if (!c->h_sig_block)
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_sig_block, rec_bytes * (size_t)c->n_slots, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(c, hipHostGetDevicePointer((void **)&h_dev, c->h_sig_block, 0));
-    if (!c->d_sig_block) HIP_TRY(c, hipMalloc((void **)&c->d_sig_block, slot_words * (size_t)c->n_slots * sizeof(uint32_t)));
+    Rollback undo{c->mem, c->mem.mark(), false};
+    HIP_TRY(c, pinned_alloc(c, &c->h_sig_block, &c->h_sig_block_dev, rec_bytes * (size_t)c->n_slots));
+    HIP_TRY(c, dev_alloc(c, &c->d_sig_block, slot_words * (size_t)c->n_slots * sizeof(uint32_t)));
     HIP_TRY(c, hipMemset(c->d_sig_block, 0, slot_words * (size_t)c->n_slots * sizeof(uint32_t)));
+    undo.keep = true;
     for (int si = 0; si < c->n_slots; si++) {
         Slot &sl = c->slot[si];
         sl.h_sig = reinterpret_cast<adsb_signal_stats *>(c->h_sig_block + rec_bytes * (size_t)si);
-        sl.h_sig_dev = reinterpret_cast<adsb_signal_stats *>(h_dev + rec_bytes * (size_t)si);
+        sl.h_sig_dev = reinterpret_cast<adsb_signal_stats *>(c->h_sig_block_dev + rec_bytes * (size_t)si);
         sl.d_sig_part = c->d_sig_block + slot_words * (size_t)si;
         sl.d_sig_ticket = sl.d_sig_part + part_words;
     }
     return ADSB_OK;
+}
+
+// The worst-case lists of the buffer-by-buffer fallback (adsb_ctx::Fallback), the first time a pass overflows.
+int ensure_fallback(adsb_ctx *c)
+{
+    auto &fb = c->fb;
+    if (fb.h_rec) return ADSB_OK;   // (reserved last)
+    Rollback undo{c->mem, c->mem.mark(), false};
+    HIP_TRY(c, dev_alloc(c, &fb.d_hits, (size_t)kWorstPerChunk * sizeof(uint64_t)));
+    HIP_TRY(c, dev_alloc(c, &fb.d_dap, (size_t)kWorstPerChunk * sizeof(uint64_t)));
+    HIP_TRY(c, pinned_alloc(c, &fb.h_rec, &fb.h_rec_dev, (size_t)kWorstPerChunk * sizeof(TrialRecord)));
+    return undo.keep = true, ADSB_OK;
+}
+
+// The growers: one buffer each, replaced by a larger one when a call needs more.  The old one goes first (nothing in
+// flight reads it, and the two never add up): a failure leaves the buffer absent and its size zero.
+template <class T>
+static int grow(adsb_ctx *c, T **buf, size_t *have, size_t want, size_t alloc, size_t elem)
+{
+    if (want <= *have) return ADSB_OK;
+    release(c, buf);
+    *have = 0;
+    HIP_TRY(c, dev_alloc(c, buf, alloc * elem));
+    *have = alloc;
+    return ADSB_OK;
+}
+int ensure_stage(adsb_ctx *c, size_t bytes) { return grow(c, &c->d_stage, &c->stage_bytes, bytes, bytes, 1); }
+int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc) { return grow(c, &c->d_addrs, &c->addrs_cap, n, alloc, sizeof(uint32_t)); }
+int ensure_rx_keys(adsb_ctx *c, size_t n)
+{
+    return grow(c, &c->d_rx_keys, &c->rx_keys_cap, n, std::max<size_t>(n + n / 2, IcaoFilter::kSize), sizeof(unsigned long long));
+}
+
+// pinned, mapped staging for host-pointer calls of a few buffers: the pass reads it in place over the
+// link, which saves the copy command and its event
+int ensure_host_stage(adsb_ctx *c, size_t bytes)
+{
+    if (bytes <= c->h_stage_bytes) return ADSB_OK;
+    release(c, &c->h_stage);
+    c->h_stage_dev = nullptr;
+    c->h_stage_bytes = 0;
+    HIP_TRY(c, pinned_alloc(c, &c->h_stage, &c->h_stage_dev, bytes));
+    c->h_stage_bytes = bytes;
+    return ADSB_OK;
+}
+
+// CU8 through the overflow fallback: one buffer and its lead-in widened to CS16
+int ensure_widen(adsb_ctx *c)
+{
+    if (!c->d_widen) HIP_TRY(c, dev_alloc(c, &c->d_widen, ((size_t)kChunkSamples + kCarrySamples) * sizeof(uint32_t)));
+    return ADSB_OK;
+}
+
+// Shard slot k's address lists in mapped host memory: the other shards' addresses (two lists: ShardJob::addr_half) and,
+// for a shard whose scan lists its fresh addresses, that list, its seen-set and the earlier shards' additions.
+int ensure_shard_lists(adsb_ctx *c, int k, bool fresh_list)
+{
+    adsb_ctx::ShardJob &job = c->shard[k];
+    const size_t list_bytes = kShardAddrCap * sizeof(uint32_t);
+    Rollback undo{c->mem, c->mem.mark(), false};
+    if (!job.h_addrs) HIP_TRY(c, pinned_alloc(c, &job.h_addrs, &job.h_addrs_dev, 2 * list_bytes));
+    if (fresh_list && !job.h_earlier) {   // (h_earlier: reserved last)
+        HIP_TRY(c, pinned_alloc(c, &job.h_fresh, &job.h_fresh_dev, list_bytes));
+        HIP_TRY(c, dev_alloc(c, &job.d_fresh_seen, kBitmapAllocWords * sizeof(uint32_t)));   // (also the `earlier` set of a scored shard)
+        HIP_TRY(c, pinned_alloc(c, &job.h_earlier, &job.h_earlier_dev, list_bytes));
+    }
+    return undo.keep = true, ADSB_OK;
 }
 
 // Receivers scored on the device (adsb_set_receiver_scoring): per pass in flight a device copy of the map with its pinned
@@ -388,47 +649,49 @@ uint32_t rx_set_lg_for(uint32_t n_receivers)
 int ensure_rx_scoring(adsb_ctx *c)
 {
     if (!c->score.si || !c->n_receivers) return ADSB_OK;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t hsize = (size_t)c->score.hash_mask + 1, map_bytes = up(c->max_chunks * sizeof(uint32_t)),
-                 per_slot = map_bytes + up((size_t)c->score.cap * sizeof(uint32_t));
-    if (!c->h_rx_block) {
-        char *h_dev = nullptr;
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_rx_block, per_slot * (size_t)c->n_slots, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(c, hipHostGetDevicePointer((void **)&h_dev, c->h_rx_block, 0));
-        uint32_t first_lg = 0;
-        while (((size_t)1 << first_lg) < hsize) first_lg++;
+    const size_t hsize = (size_t)c->score.hash_mask + 1, map_bytes = up256(c->max_chunks * sizeof(uint32_t)),
+                 per_slot = map_bytes + up256((size_t)c->score.cap * sizeof(uint32_t));
+    const uint32_t want_lg = rx_set_lg_for(c->n_receivers);
+    const bool new_slots = !c->d_rx_failed;   // (reserved last of the slots' part)
+    const bool new_sets = !c->rx_set[1] || want_lg != c->rx_set_alloc_lg;   // (absent, or sized for another number of receivers)
+    if (new_sets) {
+        for (auto &st : c->rx_set) release(c, &st);
+        c->rx_set_alloc_lg = 0;
+    }
+    Rollback undo{c->mem, c->mem.mark(), false};
+    if (new_slots) {
+        HIP_TRY(c, pinned_alloc(c, &c->h_rx_block, &c->h_rx_block_dev, per_slot * (size_t)c->n_slots));
         for (int si = 0; si < c->n_slots; si++) {
             Slot &sl = c->slot[si];
-            sl.h_rx_map = reinterpret_cast<uint32_t *>(c->h_rx_block + per_slot * (size_t)si);
-            sl.h_add_rx = reinterpret_cast<uint32_t *>(c->h_rx_block + per_slot * (size_t)si + map_bytes);
-            sl.h_add_rx_dev = reinterpret_cast<uint32_t *>(h_dev + per_slot * (size_t)si + map_bytes);
-            if (!sl.d_rx_map) HIP_TRY(c, hipMalloc((void **)&sl.d_rx_map, c->max_chunks * sizeof(uint32_t)));
-            if (!sl.d_rx_slot) HIP_TRY(c, hipMalloc((void **)&sl.d_rx_slot, (size_t)c->score.cap * sizeof(uint32_t)));
-            if (!sl.d_rx_first) HIP_TRY(c, hipMalloc((void **)&sl.d_rx_first, hsize * sizeof(unsigned long long)));
+            HIP_TRY(c, dev_alloc(c, &sl.d_rx_map, c->max_chunks * sizeof(uint32_t)));
+            HIP_TRY(c, dev_alloc(c, &sl.d_rx_slot, (size_t)c->score.cap * sizeof(uint32_t)));
+            HIP_TRY(c, dev_alloc(c, &sl.d_rx_first, hsize * sizeof(unsigned long long)));
             HIP_TRY(c, hipMemset(sl.d_rx_first, 0xFF, hsize * sizeof(unsigned long long)));
-            sl.rx = RxScoreDev{};
-            sl.rx.rx_map = sl.d_rx_map;
-            sl.rx.first = sl.d_rx_first;
-            sl.rx.first_lg = first_lg;
-            sl.rx.rx_slot = sl.d_rx_slot;
-            sl.rx.out_add_rx = sl.h_add_rx_dev;
         }
+        HIP_TRY(c, dev_alloc(c, &c->d_rx_failed, sizeof(uint32_t)));
     }
-    if (!c->d_rx_failed) HIP_TRY(c, hipMalloc((void **)&c->d_rx_failed, sizeof(uint32_t)));
-    const uint32_t want_lg = rx_set_lg_for(c->n_receivers);
-    if (!c->rx_set[0] || !c->rx_set[1] || want_lg != c->rx_set_alloc_lg) {
-        for (auto &st : c->rx_set) {
-            if (st) (void)hipFree(st);
-            st = nullptr;
-        }
-        c->rx_set_alloc_lg = 0;
-        for (auto &st : c->rx_set) HIP_TRY(c, hipMalloc((void **)&st, sizeof(unsigned long long) << want_lg));
-        c->rx_set_alloc_lg = want_lg;
-        c->cur_rx_set = 0;
+    if (new_sets)
+        for (auto &st : c->rx_set) HIP_TRY(c, dev_alloc(c, &st, sizeof(unsigned long long) << want_lg));
+    undo.keep = true;
+    uint32_t first_lg = 0;
+    while (((size_t)1 << first_lg) < hsize) first_lg++;
+    for (int si = 0; new_slots && si < c->n_slots; si++) {   // (the views, now that nothing can fail)
+        Slot &sl = c->slot[si];
+        sl.h_rx_map = reinterpret_cast<uint32_t *>(c->h_rx_block + per_slot * (size_t)si);
+        sl.h_add_rx = reinterpret_cast<uint32_t *>(c->h_rx_block + per_slot * (size_t)si + map_bytes);
+        sl.h_add_rx_dev = reinterpret_cast<uint32_t *>(c->h_rx_block_dev + per_slot * (size_t)si + map_bytes);
+        sl.rx = RxScoreDev{};
+        sl.rx.rx_map = sl.d_rx_map;
+        sl.rx.first = sl.d_rx_first;
+        sl.rx.first_lg = first_lg;
+        sl.rx.rx_slot = sl.d_rx_slot;
+        sl.rx.out_add_rx = sl.h_add_rx_dev;
     }
+    if (new_sets) c->rx_set_alloc_lg = want_lg, c->cur_rx_set = 0;
     c->rx_set_valid = false;   // (the next scored pass fills them)
     return ADSB_OK;
 }
+
 
 }  // namespace host
 }  // namespace adsb
@@ -438,191 +701,22 @@ extern "C" {
 void adsb_destroy(adsb_ctx *c)
 {
     if (!c) return;
-#ifdef ADSB_TUNING
-    if (tuning_env("ADSB_HOST_TIMES"))
-        std::fprintf(stderr, "host times over %llu passes: enqueue %.1f us, wait %.1f us, replay %.1f us per pass\n",
-                     (unsigned long long)c->collected, 1e6 * c->t_enqueue / (c->collected ? c->collected : 1),
-                     1e6 * c->t_wait / (c->collected ? c->collected : 1), 1e6 * c->t_replay / (c->collected ? c->collected : 1));
-    if (tuning_env("ADSB_HOST_TIMES")) {
-        static const char *name[HT_COUNT] = {"ring: hipMemcpyAsync", "ring: (unused)", "input-ready record + wait",
-                                             "scan launch", "scanned record + waits", "match (+ order) launch", "records launch",
-                                             "recorded / done records", "collect: wait for the pass", "collect: record checksum",
-                                             "collect: replay"};
-        double all = 0;
-        for (int k = 0; k < HT_COUNT; k++) all += c->ht_s[k];
-        for (int k = 0; k < HT_COUNT; k++)
-            if (c->ht_n[k])
-                std::fprintf(stderr, "  %-32s %8.2f us per pass  (%llu calls, %.2f us each)  %5.1f %%\n", name[k],
-                             1e6 * c->ht_s[k] / (c->collected ? c->collected : 1), (unsigned long long)c->ht_n[k],
-                             1e6 * c->ht_s[k] / c->ht_n[k], 100.0 * c->ht_s[k] / (all > 0 ? all : 1));
-    }
-#endif
+    print_host_times(c);
     DeviceGuard on_device(c->device);
+    // nothing the context put on a stream may still be running when its memory goes (shared streams: other contexts'
+    // work on them is waited for too)
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    for (auto &pair : c->scan_ev)
-        for (auto &e : pair)
-            if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->redo_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (Slot &sl : c->slot) {
-        for (int k = 2; k < 5; k++)
-            if (sl.ev[k]) (void)hipEventDestroy(sl.ev[k]);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.scanned) (void)hipEventDestroy(sl.scanned);
-        if (sl.d_ctr) (void)hipFree(sl.d_ctr);
-        if (sl.d_hits) (void)hipFree(sl.d_hits);
-        if (sl.d_hit_fields) (void)hipFree(sl.d_hit_fields);
-        if (sl.d_ap) (void)hipFree(sl.d_ap);
-        if (sl.d_order_cnt) (void)hipFree(sl.d_order_cnt);
-        if (sl.d_order_base) (void)hipFree(sl.d_order_base);
-        if (sl.d_order_tmp) (void)hipFree(sl.d_order_tmp);
-        if (sl.d_carry) (void)hipFree(sl.d_carry);
-    }
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    for (auto &b : c->d_bitmap)
-        if (b) (void)hipFree(b);
     for (hipStream_t q : c->scan_stream)
         if (q) (void)hipStreamSynchronize(q);
-    for (hipEvent_t e : c->input_ready)
-        if (e) (void)hipEventDestroy(e);
-    if (c->lazy_ev) (void)hipEventDestroy(c->lazy_ev);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_block) (void)hipHostFree(c->h_block);
-    if (c->h_sig_block) (void)hipHostFree(c->h_sig_block);
-    if (c->d_sig_block) (void)hipFree(c->d_sig_block);
-    if (c->score_stream) (void)hipStreamSynchronize(c->score_stream);
-    for (Slot &sl : c->slot)
-        for (void *q : {(void *)sl.d_rx_map, (void *)sl.d_rx_slot, (void *)sl.d_rx_first})
-            if (q) (void)hipFree(q);
-    for (auto *st : c->rx_set)
-        if (st) (void)hipFree(st);
-    if (c->d_rx_keys) (void)hipFree(c->d_rx_keys);
-    if (c->d_rx_failed) (void)hipFree(c->d_rx_failed);
-    if (c->h_rx_block) (void)hipHostFree(c->h_rx_block);
-    if (c->tail_stream) (void)hipStreamSynchronize(c->tail_stream);
-    for (Slot &sl : c->slot) {
-        for (void *q : {(void *)sl.score.si, (void *)sl.score.rec, (void *)sl.score.flag, (void *)sl.score.slot, (void *)sl.score.pos,
-                        (void *)sl.score.hash, (void *)sl.score.blk, (void *)sl.score.state})
-            if (q && q != (void *)c->score.exact) (void)hipFree(q);
-        if (sl.recorded) (void)hipEventDestroy(sl.recorded);
+    for (hipStream_t q : {c->tail_stream, c->score_stream})
+        if (q) (void)hipStreamSynchronize(q);
+    if (c->d_timeline) {   // (blocking copies out of it: the streams are idle)
+        if (tuning_env("ADSB_TIMELINE") && std::atoi(tuning_env("ADSB_TIMELINE")) == 3) dump_onelaunch_timeline(c);
+        else if (c->debug_stop == 100) dump_scan_phases(c);
+        else dump_scan_stamps(c);
     }
-    for (uint32_t *bm : c->exact_bm)
-        if (bm) (void)hipFree(bm);
-    if (c->score_stream) (void)hipStreamSynchronize(c->score_stream);
-    if (c->fb.d_hits) (void)hipFree(c->fb.d_hits);
-    if (c->fb.d_dap) (void)hipFree(c->fb.d_dap);
-    if (c->fb.h_rec) (void)hipHostFree(c->fb.h_rec);
+    c->mem.release_all();
     for (const auto &r : c->host_ranges) (void)hipHostUnregister(r.base);
-    if (c->d_tables) (void)hipFree(c->d_tables);
-    if (c->d_u8_table) (void)hipFree(c->d_u8_table);
-    if (c->d_widen) (void)hipFree(c->d_widen);
-    if (c->ring_h_block) (void)hipHostFree(c->ring_h_block);
-    if (c->ring_d_block) (void)hipFree(c->ring_d_block);
-    if (c->d_addrs) (void)hipFree(c->d_addrs);
-    for (auto &j : c->shard) {
-        if (j.h_addrs) (void)hipHostFree(j.h_addrs);
-        if (j.h_fresh) (void)hipHostFree(j.h_fresh);
-        if (j.d_fresh_seen) (void)hipFree(j.d_fresh_seen);
-        if (j.h_earlier) (void)hipHostFree(j.h_earlier);
-        for (hipEvent_t e : j.addr_read)
-            if (e) (void)hipEventDestroy(e);
-    }
-    if (c->d_carry_next) (void)hipFree(c->d_carry_next);
-    if (c->d_timeline && tuning_env("ADSB_TIMELINE") && std::atoi(tuning_env("ADSB_TIMELINE")) == 3) {
-        // profiling aid: the stamps of the last one-launch pass (100 MHz wall clock)
-        unsigned long long t[10] = {};
-        if (hipMemcpy(t, c->d_timeline + 448, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess && t[0]) {
-            if (t[8] > t[4] && t[7] > t[8])
-                std::fprintf(stderr, "  one-launch pass, second look: fill counts in LDS +%.2f us, entries compared +%.2f us, fence +%.2f us\n",
-                             (double)(long long)(t[8] - t[4]) / 100.0, (double)(long long)(t[7] - t[8]) / 100.0,
-                             (double)(long long)(t[5] - t[7]) / 100.0);
-            static const char *name[7] = {"entry", "tables in LDS, first tile requested", "tiles done", "own entries matched",
-                                          "counted in (last workgroup from here on)", "second look done", "records + summary + counters"};
-            for (int k = 1; k < 7; k++)
-                std::fprintf(stderr, "  one-launch pass: %-45s +%6.2f us  (at %6.2f)\n", name[k],
-                             (double)(long long)(t[k] - t[k - 1]) / 100.0, (double)(long long)(t[k] - t[0]) / 100.0);
-        }
-        // ... and of the last sixteen, workgroup by workgroup: when the first and the last workgroup passed each
-        // stage, from the pass's first entry (passes in flight side by side: how they stretch each other)
-        std::vector<unsigned long long> w(16 * 32 * 8);
-        if (hipMemcpy(w.data(), c->d_timeline + 1024, w.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            unsigned long long origin = ~0ull;
-            for (unsigned long long v : w) if (v && v < origin) origin = v;
-            for (int ps = 0; ps < 16; ps++) {
-                unsigned long long lo[8], hi[8] = {};
-                for (auto &v : lo) v = ~0ull;
-                for (int g = 0; g < 32; g++)
-                    for (int k = 0; k < 8; k++) {
-                        const unsigned long long v = w[(ps * 32 + g) * 8 + k];
-                        if (!v) continue;
-                        lo[k] = std::min(lo[k], v);
-                        hi[k] = std::max(hi[k], v);
-                    }
-                if (!hi[0]) continue;
-                std::fprintf(stderr, "  pass %2d entered at %8.2f us:", ps, (double)(lo[0] - origin) / 100.0);
-                for (int k = 0; k < 7; k++)
-                    if (hi[k]) std::fprintf(stderr, "  s%d %.1f..%.1f", k, (double)(lo[k] - lo[0]) / 100.0, (double)(hi[k] - lo[0]) / 100.0);
-                std::fprintf(stderr, "\n");
-            }
-        }
-        (void)hipFree(c->d_timeline);
-    } else if (c->d_timeline && c->debug_stop == 100) {
-        // profiling aid: phase / barrier-wait totals of the last scan, summed over all waves
-        std::vector<unsigned long long> tl(kTimelineWords);
-        if (hipMemcpy(tl.data(), c->d_timeline, kTimelineWords * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            double sum[8] = {0};
-            int nw = 0;
-            for (size_t w = 0; w < kTimelineWords / 8; w++) {
-                double tot = 0;
-                for (int k = 0; k < 8; k++) tot += (double)tl[w * 8 + k];
-                if (tot == 0) continue;
-                nw++;
-                for (int k = 0; k < 8; k++) sum[k] += (double)tl[w * 8 + k];
-            }
-            double all = 0;
-            for (double v : sum) all += v;
-            static const char *name[8] = {"P1", "wait B1", "P2", "wait B2", "P3-5", "wait B3", "epilogue", "wait B4"};
-            std::fprintf(stderr, "phase accounting over %d waves (clock64 ticks per wave, share):\n", nw);
-            for (int k = 0; k < 8; k++)
-                std::fprintf(stderr, "  %-9s %10.0f  %5.1f %%\n", name[k], sum[k] / (nw ? nw : 1), 100.0 * sum[k] / (all ? all : 1));
-            // ... and how evenly the work fell: a workgroup's total (its waves agree to a barrier wait) and its
-            // wave-private stage, over the workgroups -- the launch ends with the slowest one
-            std::vector<double> tot, late;
-            for (size_t w = 0; w + 3 < kTimelineWords / 8; w += 4) {
-                double t = 0, l = 0;
-                for (int k = 0; k < 8; k++) t += (double)tl[w * 8 + k];
-                for (size_t v = 0; v < 4; v++) l = std::max(l, (double)tl[(w + v) * 8 + 4]);
-                if (t == 0) continue;
-                tot.push_back(t);
-                late.push_back(l);
-            }
-            auto pct = [](std::vector<double> &v, double q) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[(size_t)(q * (double)(v.size() - 1))]; };
-            double mt = 0, ml = 0;
-            for (double v : tot) mt += v;
-            for (double v : late) ml += v;
-            mt /= tot.empty() ? 1 : (double)tot.size();
-            ml /= late.empty() ? 1 : (double)late.size();
-            std::fprintf(stderr, "  per workgroup (wave 0's total): mean %.0f  p50 %.0f  p99 %.0f  max %.0f  (max / mean %.3f)\n", mt, pct(tot, 0.5),
-                         pct(tot, 0.99), pct(tot, 1.0), mt > 0 ? pct(tot, 1.0) / mt : 0.0);
-            std::fprintf(stderr, "  per workgroup (its slowest wave's P3-5): mean %.0f  p50 %.0f  p99 %.0f  max %.0f  (max / mean %.3f)\n", ml,
-                         pct(late, 0.5), pct(late, 0.99), pct(late, 1.0), ml > 0 ? pct(late, 1.0) / ml : 0.0);
-        }
-        (void)hipFree(c->d_timeline);
-    } else if (c->d_timeline) {
-        // profiling aid: dump the stamps of the last scan on the way out
-        unsigned long long tl[512];
-        if (hipMemcpy(tl, c->d_timeline, sizeof(tl), hipMemcpyDeviceToHost) == hipSuccess)
-            for (int b = 0; b < 8; b++)
-                for (int it = 0; it < 8; it++) {
-                    const unsigned long long *r = tl + (b * 8 + it) * 8;
-                    if (!r[0]) continue;
-                    std::fprintf(stderr, "timeline block %d tile %d: start %8lld |", b * 128, it,
-                                 (long long)(r[0] - tl[0]));
-                    for (int k = 1; k < 7; k++) std::fprintf(stderr, " %6lld", (long long)(r[k] - r[k - 1]));
-                    std::fprintf(stderr, "  total %lld\n", (long long)(r[6] - r[0]));
-                }
-        (void)hipFree(c->d_timeline);
-    }
     if (c->private_streams) {
         for (hipStream_t q : {c->own_stream, c->tail_stream, c->score_stream})
             if (q) (void)hipStreamDestroy(q);
@@ -875,28 +969,22 @@ try {
     const uint32_t dflt = rx_set_lg_for(c->n_receivers);
     const uint32_t lg = c->rx_tune_lg ? std::min(c->rx_tune_lg, dflt) : dflt, probe_max = c->rx_probe_max();
     const size_t set_bytes = sizeof(unsigned long long) << lg, in_bytes = (n_keys + n_q) * sizeof(unsigned long long);
+    ScratchRegistry scratch;   // (its release waits for whatever an early return leaves on the stream)
     char *d = nullptr;
-    const size_t o_in = set_bytes, o_out = o_in + ((in_bytes + 255) & ~(size_t)255), total = o_out + (n_q + 1) * sizeof(uint32_t);
-    HIP_TRY(c, hipMalloc((void **)&d, total));
-    int rc = ADSB_OK;
-    auto step = [&](hipError_t e, const char *what) {
-        if (rc == ADSB_OK && e != hipSuccess) rc = fail(c, e, what);
-    };
+    const size_t o_in = set_bytes, o_out = o_in + up256(in_bytes), total = o_out + (n_q + 1) * sizeof(uint32_t);
+    HIP_TRY(c, scratch.add(Registry::kDevice, (void **)&d, total));
     unsigned long long *d_set = reinterpret_cast<unsigned long long *>(d), *d_in = reinterpret_cast<unsigned long long *>(d + o_in);
     uint32_t *d_out = reinterpret_cast<uint32_t *>(d + o_out);
-    step(hipMemsetAsync(d_set, 0xFF, set_bytes, c->stream), "hipMemsetAsync");
-    step(hipMemsetAsync(d_out, 0, (n_q + 1) * sizeof(uint32_t), c->stream), "hipMemsetAsync");
-    if (n_keys) step(hipMemcpyAsync(d_in, keys, n_keys * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync");
-    if (n_q) step(hipMemcpyAsync(d_in + n_keys, queries, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync");
     c->own_stream_dirty = true;
-    if (rc == ADSB_OK)
-        if (int e = launch_rx_set_fill(d_in, (uint32_t)n_keys, d_set, lg, probe_max, d_out + n_q, c->stream)) rc = fail(c, (hipError_t)e, "launch_rx_set_fill");
-    if (rc == ADSB_OK)
-        if (int e = launch_rx_set_lookup(d_in + n_keys, (uint32_t)n_q, d_set, lg, probe_max, d_out, c->stream)) rc = fail(c, (hipError_t)e, "launch_rx_set_lookup");
-    step(hipMemcpyAsync(out, d_out, (n_q + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
-    step(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-    (void)hipFree(d);
-    return rc;
+    HIP_TRY(c, hipMemsetAsync(d_set, 0xFF, set_bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_out, 0, (n_q + 1) * sizeof(uint32_t), c->stream));
+    if (n_keys) HIP_TRY(c, hipMemcpyAsync(d_in, keys, n_keys * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    if (n_q) HIP_TRY(c, hipMemcpyAsync(d_in + n_keys, queries, n_q * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    if (int e = launch_rx_set_fill(d_in, (uint32_t)n_keys, d_set, lg, probe_max, d_out + n_q, c->stream)) return fail(c, (hipError_t)e, "launch_rx_set_fill");
+    if (int e = launch_rx_set_lookup(d_in + n_keys, (uint32_t)n_q, d_set, lg, probe_max, d_out, c->stream)) return fail(c, (hipError_t)e, "launch_rx_set_lookup");
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, (n_q + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ADSB_OK;
 } ADSB_ABI_CATCH
 
 uint64_t adsb_host_sorts(const adsb_ctx *c) { return c ? c->host_sorts : 0; }

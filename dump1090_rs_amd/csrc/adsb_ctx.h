@@ -1,7 +1,7 @@
 // adsb_ctx.h -- what the host-side units of libadsb_hip.so share: the context, a pass slot, and the
 // internal entry points between them.  Not part of the ABI (include/adsb_hip.h is).
 //
-//   adsb_context.cpp   create / destroy, the stream pool, settings, diagnostics
+//   adsb_context.cpp   create / destroy, the registry, every lazy reservation (ensure_*), the stream pool, settings, diagnostics
 //   adsb_pass.cpp      one device pass: what is enqueued on which stream, and every cross-stream edge
 //                      (docs/HISTORY.md section 5b lists them), submit, the blocking entry points
 //   adsb_collect.cpp   waiting for a pass, checksums, the overflow fallback
@@ -31,6 +31,26 @@
 #include "mode_s_host.hpp"
 
 using namespace adsb;
+
+// The one owner of what a context (or a decimator handle, or one self-test call) reserves from the runtime.  The
+// pointers in the structs below are views: an entry remembers the variable its reservation was stored into (which must
+// outlive it and not move) and nulls it on release.  (adsb_context.cpp)
+struct Registry {
+    enum Kind : uint8_t { kDevice, kPinned, kEvent };   // device memory / mapped, coherent host memory / an event
+    struct Entry {
+        Kind kind;
+        void *p, **home;
+    };
+    std::vector<Entry> entries;
+    hipError_t add(Kind kind, void **home, size_t bytes_or_flags);   // on failure nothing is registered
+    size_t mark() const { return entries.size(); }   // (holds until the next release(): take it behind those)
+    void release(void **home);          // the entry stored into *home, if any
+    void release_from(size_t mark);     // everything registered since mark(), newest first
+    void release_all() { release_from(0); }
+};
+struct ScratchRegistry : Registry { ~ScratchRegistry() { release_all(); } };   // one call's scratch, behind its device guard
+// a lazy reservation is all or nothing: what was registered since `mark` goes again unless `keep` is set at the end
+struct Rollback { Registry &r; size_t mark; bool keep; ~Rollback() { if (!keep) r.release_from(mark); } };
 
 // One submission in flight: what was asked, and the pinned host side of its results.
 struct Slot {
@@ -143,6 +163,7 @@ struct adsb_ctx {
     int debug_stop = 0;  // ADSB_DEBUG_STOP: profiling aid, breaks results when non-zero
     unsigned long long *d_timeline = nullptr;  // ADSB_TIMELINE=1: 8 blocks x 8 tiles x 8 stamps
     size_t max_chunks = 0;
+    Registry mem;   // owns every device / pinned reservation and every event below (adsb_destroy: release_all)
 
     char *h_block = nullptr, *h_block_dev = nullptr;   // the host side of every slot (summaries, records, messages): one pinned allocation
     void *d_stage = nullptr;  // IQ staging for host-pointer calls (lazy)
@@ -238,7 +259,7 @@ struct adsb_ctx {
     } ring[kSlots];
     size_t ring_samples = 0;
     SrcFormat ring_fmt = SrcFormat::kCs16;   // adsb_ring_create or adsb_ring_create_u8
-    char *ring_h_block = nullptr, *ring_d_block = nullptr;   // all slots' pinned / staging buffers: one allocation each
+    char *ring_h_block = nullptr, *ring_h_block_dev = nullptr, *ring_d_block = nullptr;   // all slots' pinned / staging buffers: one allocation each
 
     bool carry_over = false;  // adsb_set_carry_over: opt-in, not the reference's semantics
     uint32_t *d_carry_next = nullptr;  // the end of the latest submission's input: the next one's lead-in
@@ -312,7 +333,7 @@ struct adsb_ctx {
     // (one mapped pinned block) and partials + tickets (one device block), reserved when the mode is first enabled;
     // the records of the pass collected last / the blocking call returned last (adsb_fetch_signal_stats)
     bool signal_stats = false;
-    char *h_sig_block = nullptr;
+    char *h_sig_block = nullptr, *h_sig_block_dev = nullptr;
     uint32_t *d_sig_block = nullptr;
     std::vector<adsb_signal_stats> sig_out;
     uint64_t sig_launches = 0;   // k_signal_stats launches so far (adsb_selftest_signal_launches)
@@ -342,7 +363,7 @@ struct adsb_ctx {
     uint32_t rx_tune_lg = 0, rx_tune_probe = 0;   // adsb_selftest_rx_score_tune (0: the defaults)
     bool rx_set_valid = false;
     bool rx_set_full = false;                // a rebuild ran out of probes: the host scores until the next icao_flush
-    char *h_rx_block = nullptr;              // every slot's pinned map staging and h_add_rx: one mapped allocation
+    char *h_rx_block = nullptr, *h_rx_block_dev = nullptr;   // every slot's pinned map staging and h_add_rx: one mapped allocation
     unsigned long long *d_rx_keys = nullptr; // the rebuild's keys (grown on demand) and its out-of-probes count
     size_t rx_keys_cap = 0;
     uint32_t *d_rx_failed = nullptr;
@@ -374,6 +395,19 @@ inline int fail(adsb_ctx *c, hipError_t e, const char *what)
         hipError_t e_ = (call);                                           \
         if (e_ != hipSuccess) return ::adsb::host::fail((ctx), e_, #call); \
     } while (0)
+
+// Reservations through the context's registry, each a step for HIP_TRY (another registry: its add() directly)
+template <class T> inline hipError_t dev_alloc(adsb_ctx *c, T **p, size_t bytes) { return c->mem.add(Registry::kDevice, (void **)p, bytes); }
+template <class T> inline void release(adsb_ctx *c, T **p) { c->mem.release((void **)p); }
+template <class T> inline hipError_t pinned_alloc(adsb_ctx *c, T **h, T **h_dev, size_t bytes)
+{
+    hipError_t e = c->mem.add(Registry::kPinned, (void **)h, bytes);
+    if (e == hipSuccess && (e = hipHostGetDevicePointer((void **)h_dev, *h, 0)) != hipSuccess) release(c, h);
+    return e;
+}
+inline hipError_t new_event(adsb_ctx *c, hipEvent_t *ev, unsigned flags) { return c->mem.add(Registry::kEvent, (void **)ev, flags); }
+constexpr unsigned kQuietEvent = hipEventDisableTiming | hipEventDisableSystemFence;   // orders streams, nothing else
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }   // how the pinned blocks are cut into pieces
 
 // Every entry point runs on its context's device and leaves the calling thread's current device as it found it: a
 // host with several GPUs (torch, or a Rust main loop that drives a context per device from one thread) must not find
@@ -429,8 +463,14 @@ struct HostTimer {
 #define HT(c, k) do {} while (0)
 #endif
 
+// adsb_context.cpp: what is reserved on first use -- each all or nothing, and a retry after a failure starts afresh
+int ensure_signal_stats(adsb_ctx *c);               // the signal-statistics storage of every slot, on first enable
+int ensure_fallback(adsb_ctx *c);                   // adsb_ctx::Fallback
+int ensure_widen(adsb_ctx *c);                      // adsb_ctx::d_widen
+int ensure_rx_keys(adsb_ctx *c, size_t n);          // room for n keys in c->d_rx_keys (rebuild_rx_set)
+int ensure_shard_lists(adsb_ctx *c, int k, bool fresh_list);   // ShardJob::h_addrs and, with fresh_list, h_fresh / d_fresh_seen / h_earlier
+
 // adsb_pass.cpp
-int ensure_fallback(adsb_ctx *c);
 int fallback_slot(adsb_ctx *c, const Slot &sl, Slot &tmp);
 inline hipEvent_t input_ready_now() { return reinterpret_cast<hipEvent_t>(static_cast<uintptr_t>(1)); }
 // How enqueue_pass is asked to run a pass (default: a fresh, pipelined pass whose input is complete where `stream` stands).
@@ -471,7 +511,7 @@ void stamp_seq(adsb_ctx *c, Slot &sl, ScanParams &p, bool scored = false);
 // the 24-bit addresses in the host's filter table / room for n addresses in c->d_addrs (`alloc` entries when it has to grow)
 // (with receivers on: the union of all receivers' filters, sorted, each address once)
 std::vector<uint32_t> filter_addresses(const adsb_ctx *c);
-int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc);
+int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc);   // (adsb_context.cpp)
 int resync_exact(adsb_ctx *c);
 // receivers scored on the device: the slots' buffers and the two keyed sets, sized for c->n_receivers (adsb_context.cpp;
 // nothing may be in flight; no-op in a context that never scores on the device or with receivers off); log2 of the slots
@@ -493,6 +533,7 @@ void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, 
                   std::vector<adsb_signal_stats> &sig);
 // T_soapy: the table SoapyRTLSDR widens an RTL-SDR's bytes with, (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f)
 void soapy_u8_table(int16_t *out256);
+// IQ staging for host-pointer calls, in device memory / pinned and mapped, grown on demand (adsb_context.cpp)
 int ensure_stage(adsb_ctx *c, size_t bytes);
 int ensure_host_stage(adsb_ctx *c, size_t bytes);
 
@@ -513,9 +554,6 @@ struct RxCall {
     RxCall(const RxCall &) = delete;
     RxCall &operator=(const RxCall &) = delete;
 };
-
-// adsb_context.cpp: the signal-statistics storage of every slot, on first enable
-int ensure_signal_stats(adsb_ctx *c);
 
 // adsb_collect.cpp
 int verify_records(adsb_ctx *c, const Summary *sum, const TrialRecord *rec, size_t n);

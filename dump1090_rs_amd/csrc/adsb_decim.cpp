@@ -22,6 +22,7 @@ struct adsb_decim {
     size_t in_bytes = 0;
     void *d_out = nullptr;
     size_t out_bytes = 0;
+    Registry mem;   // owns the five buffers above
 };
 
 namespace {
@@ -66,13 +67,12 @@ int run_on_stream(adsb_decim *d, int format, const void *d_in, uint64_t n_in, vo
     return ADSB_OK;
 }
 
-int ensure_buffer(adsb_ctx *c, void **buf, size_t *have, size_t bytes)
+int ensure_buffer(adsb_ctx *c, Registry &mem, void **buf, size_t *have, size_t bytes)
 {
     if (bytes <= *have) return ADSB_OK;
-    if (*buf) HIP_TRY(c, hipFree(*buf));
-    *buf = nullptr;
+    mem.release(buf);
     *have = 0;
-    HIP_TRY(c, hipMalloc(buf, bytes));
+    HIP_TRY(c, mem.add(Registry::kDevice, buf, bytes));
     *have = bytes;
     return ADSB_OK;
 }
@@ -96,8 +96,8 @@ int demod_host(adsb_decim *d, int format, const void *host_iq, size_t n_in, adsb
         const uint64_t n_o = std::min(piece_out, total_out - out_done);
         // the inputs up to the one in front of the next piece's first output; the last piece takes what is left
         const uint64_t n_i = out_done + n_o == total_out ? n_in - in_done : first_output_at(d) + n_o * D;
-        if (int rc = ensure_buffer(c, &d->d_in, &d->in_bytes, std::min<uint64_t>(n_in, (piece_out + 1) * D) * bps)) return rc;
-        if (int rc = ensure_buffer(c, &d->d_out, &d->out_bytes, std::min(piece_out, total_out) * 4)) return rc;
+        if (int rc = ensure_buffer(c, d->mem, &d->d_in, &d->in_bytes, std::min<uint64_t>(n_in, (piece_out + 1) * D) * bps)) return rc;
+        if (int rc = ensure_buffer(c, d->mem, &d->d_out, &d->out_bytes, std::min(piece_out, total_out) * 4)) return rc;
         HIP_TRY(c, hipMemcpyAsync(d->d_in, in + in_done * bps, n_i * bps, hipMemcpyHostToDevice, c->stream));
         if (c->stream == c->own_stream) c->own_stream_dirty = true;
         if (int rc = run_on_stream(d, format, d->d_in, n_i, d->d_out, n_o)) return rc;
@@ -110,7 +110,7 @@ int demod_host(adsb_decim *d, int format, const void *host_iq, size_t n_in, adsb
     if (in_done < n_in) {
         // inputs that reach no output (only a call without any has them): they still enter the history
         const uint64_t n_i = n_in - in_done;
-        if (int rc = ensure_buffer(c, &d->d_in, &d->in_bytes, n_i * bps)) return rc;
+        if (int rc = ensure_buffer(c, d->mem, &d->d_in, &d->in_bytes, n_i * bps)) return rc;
         HIP_TRY(c, hipMemcpyAsync(d->d_in, in + in_done * bps, n_i * bps, hipMemcpyHostToDevice, c->stream));
         if (c->stream == c->own_stream) c->own_stream_dirty = true;
         if (int rc = run_on_stream(d, format, d->d_in, n_i, nullptr, 0)) return rc;
@@ -142,8 +142,8 @@ try {
     d->factor = factor, d->n_taps = n_taps, d->shift = shift;
     std::vector<int32_t> padded((n_taps + 7u) & ~7u, 0);
     for (uint32_t k = 0; k < n_taps; k++) padded[k] = taps[k];
-    hipError_t e = hipMalloc((void **)&d->d_taps, padded.size() * sizeof(int32_t));
-    for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMalloc((void **)&d->d_hist[b], kDecimHistWords * sizeof(uint32_t));
+    hipError_t e = d->mem.add(Registry::kDevice, (void **)&d->d_taps, padded.size() * sizeof(int32_t));
+    for (int b = 0; b < 2 && e == hipSuccess; b++) e = d->mem.add(Registry::kDevice, (void **)&d->d_hist[b], kDecimHistWords * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemcpy(d->d_taps, padded.data(), padded.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipMemset(d->d_hist[b], 0, kDecimHistWords * sizeof(uint32_t));
     if (e != hipSuccess) {
@@ -162,11 +162,7 @@ void adsb_decim_destroy(adsb_decim *d)
         DeviceGuard guard(d->ctx->device);
         // (what the handle put on the stream may still read its buffers)
         (void)hipStreamSynchronize(d->ctx->stream);
-        if (d->d_taps) (void)hipFree(d->d_taps);
-        for (uint32_t *h : d->d_hist)
-            if (h) (void)hipFree(h);
-        if (d->d_in) (void)hipFree(d->d_in);
-        if (d->d_out) (void)hipFree(d->d_out);
+        d->mem.release_all();
     }
     delete d;
 }

@@ -8,18 +8,6 @@ using namespace adsb::host;
 namespace adsb {
 namespace host {
 
-int ensure_fallback(adsb_ctx *c)
-{
-    auto &fb = c->fb;
-    if (fb.h_rec_dev) return ADSB_OK;
-    if (!fb.d_hits) HIP_TRY(c, hipMalloc((void **)&fb.d_hits, (size_t)kWorstPerChunk * sizeof(uint64_t)));
-    if (!fb.d_dap) HIP_TRY(c, hipMalloc((void **)&fb.d_dap, (size_t)kWorstPerChunk * sizeof(uint64_t)));
-    if (!fb.h_rec)
-        HIP_TRY(c, hipHostMalloc((void **)&fb.h_rec, (size_t)kWorstPerChunk * sizeof(TrialRecord), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(c, hipHostGetDevicePointer((void **)&fb.h_rec_dev, fb.h_rec, 0));
-    return ADSB_OK;
-}
-
 // `sl` with the worst-case lists in place of its own: what a one-buffer fallback pass runs on
 // (same counters, AP list, summary, events and carry as the pass it redoes).
 int fallback_slot(adsb_ctx *c, const Slot &sl, Slot &tmp)
@@ -561,17 +549,6 @@ std::vector<uint32_t> filter_addresses(const adsb_ctx *c)
     return addrs;
 }
 
-int ensure_addrs(adsb_ctx *c, size_t n, size_t alloc)
-{
-    if (n <= c->addrs_cap) return ADSB_OK;
-    if (c->d_addrs) (void)hipFree(c->d_addrs);
-    c->d_addrs = nullptr;
-    c->addrs_cap = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_addrs, alloc * sizeof(uint32_t)));
-    c->addrs_cap = alloc;
-    return ADSB_OK;
-}
-
 // The exact bitmap rebuilt from the host's filter table (only while nothing is in flight).
 int resync_exact(adsb_ctx *c)
 {
@@ -606,14 +583,7 @@ int rebuild_rx_set(adsb_ctx *c)
                 if (a != 0 && a <= 0xFFFFFFu) keys.push_back((unsigned long long)r << 24 | a);   // (DF18 entries match no 24-bit value)
     uint32_t failed = 0;
     if (!keys.empty()) {
-        if (keys.size() > c->rx_keys_cap) {
-            if (c->d_rx_keys) (void)hipFree(c->d_rx_keys);
-            c->d_rx_keys = nullptr;
-            c->rx_keys_cap = 0;
-            const size_t alloc = std::max<size_t>(keys.size() + keys.size() / 2, IcaoFilter::kSize);
-            HIP_TRY(c, hipMalloc((void **)&c->d_rx_keys, alloc * sizeof(unsigned long long)));
-            c->rx_keys_cap = alloc;
-        }
+        if (int rc = ensure_rx_keys(c, keys.size())) return rc;
         HIP_TRY(c, hipMemsetAsync(c->d_rx_failed, 0, sizeof(uint32_t), ts));
         HIP_TRY(c, hipMemcpyAsync(c->d_rx_keys, keys.data(), keys.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ts));
         if (int e = launch_rx_set_fill(c->d_rx_keys, (uint32_t)keys.size(), c->rx_set[c->cur_rx_set], c->rx_set_lg(), c->rx_probe_max(),
@@ -736,31 +706,6 @@ int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<
     total.n_samples = n_samples;
     c->stats = total;
     c->sig_out.swap(sig);
-    return ADSB_OK;
-}
-
-// pinned, mapped staging for host-pointer calls of a few buffers: the pass reads it in place over the
-// link, which saves the copy command and its event
-int ensure_host_stage(adsb_ctx *c, size_t bytes)
-{
-    if (bytes <= c->h_stage_bytes) return ADSB_OK;
-    if (c->h_stage) HIP_TRY(c, hipHostFree(c->h_stage));
-    c->h_stage = c->h_stage_dev = nullptr;
-    c->h_stage_bytes = 0;
-    HIP_TRY(c, hipHostMalloc(&c->h_stage, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(c, hipHostGetDevicePointer(&c->h_stage_dev, c->h_stage, 0));
-    c->h_stage_bytes = bytes;
-    return ADSB_OK;
-}
-
-int ensure_stage(adsb_ctx *c, size_t bytes)
-{
-    if (bytes <= c->stage_bytes) return ADSB_OK;
-    if (c->d_stage) HIP_TRY(c, hipFree(c->d_stage));
-    c->d_stage = nullptr;
-    c->stage_bytes = 0;
-    HIP_TRY(c, hipMalloc(&c->d_stage, bytes));
-    c->stage_bytes = bytes;
     return ADSB_OK;
 }
 

@@ -17,39 +17,28 @@ int ring_create(adsb_ctx *c, size_t samples_per_slot, SrcFormat fmt)
     const size_t bps = src_bytes_per_sample(fmt);
     if ((samples_per_slot + kChunkSamples - 1) / kChunkSamples > c->max_chunks) return ADSB_ERR_INVALID;
     ADSB_ON_DEVICE(c);
-    auto body = [&]() -> int {
-        // every slot's pinned buffer from ONE allocation, and every staging buffer from one (slot starts 4 KB aligned):
-        // mapped and coherent -- slots of a few buffers are read in place by the pass itself
-        const size_t stride = (samples_per_slot * bps + 4095) & ~(size_t)4095;
-        char *h_dev = nullptr;
-        HIP_TRY(c, hipHostMalloc((void **)&c->ring_h_block, stride * (size_t)c->n_slots, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(c, hipHostGetDevicePointer((void **)&h_dev, c->ring_h_block, 0));
-        HIP_TRY(c, hipMalloc((void **)&c->ring_d_block, stride * (size_t)c->n_slots));
-        for (int k = 0; k < c->n_slots; k++) {
-            auto &r = c->ring[k];
-            r.h_iq = reinterpret_cast<int16_t *>(c->ring_h_block + stride * (size_t)k);
-            r.h_iq_dev = h_dev + stride * (size_t)k;
-            r.d_iq = c->ring_d_block + stride * (size_t)k;
-        }
-        // One small copy per slot now, on an idle stream.  The runtime sets something up on the first copy between a
-        // pair of buffers; left to the first pipelined submit (a ring that starts with its slots read in place) every
-        // later hipMemcpyAsync of the ring took 12-19 us of the submitting thread instead of 2-5 (measured: 16-buffer
-        // slots, eight in flight, 12.5 Gsample/s instead of 13.2; profiles/r4_ring_copy_ab.txt).
-        const size_t warm = std::min<size_t>(samples_per_slot * bps, 64 << 10);
-        for (int k = 0; k < c->n_slots; k++)
-            HIP_TRY(c, hipMemcpyAsync(c->ring[k].d_iq, c->ring[k].h_iq, warm, hipMemcpyHostToDevice, c->scan_stream[k % c->n_scan_streams]));
-        for (int k = 0; k < c->n_scan_streams; k++) HIP_TRY(c, hipStreamSynchronize(c->scan_stream[k]));
-        return (int)ADSB_OK;
-    };
-    const int rc = body();
-    if (rc != ADSB_OK) {
-        // nothing half-made stays behind: a retry starts from scratch instead of overwriting (and leaking) these
-        for (int k = 0; k < c->n_scan_streams; k++) (void)hipStreamSynchronize(c->scan_stream[k]);
-        if (c->ring_h_block) (void)hipHostFree(c->ring_h_block);
-        if (c->ring_d_block) (void)hipFree(c->ring_d_block);
-        c->ring_h_block = c->ring_d_block = nullptr;
-        for (auto &r : c->ring) r = adsb_ctx::RingSlot{};
-        return rc;
+    // every slot's pinned buffer from ONE allocation, and every staging buffer from one (slot starts 4 KB aligned):
+    // mapped and coherent -- slots of a few buffers are read in place by the pass itself
+    const size_t stride = (samples_per_slot * bps + 4095) & ~(size_t)4095;
+    Rollback undo{c->mem, c->mem.mark(), false};   // nothing half-made stays behind: a retry starts from scratch
+    HIP_TRY(c, pinned_alloc(c, &c->ring_h_block, &c->ring_h_block_dev, stride * (size_t)c->n_slots));
+    HIP_TRY(c, dev_alloc(c, &c->ring_d_block, stride * (size_t)c->n_slots));
+    // One small copy per slot now, on an idle stream.  The runtime sets something up on the first copy between a
+    // pair of buffers; left to the first pipelined submit (a ring that starts with its slots read in place) every
+    // later hipMemcpyAsync of the ring took 12-19 us of the submitting thread instead of 2-5 (measured: 16-buffer
+    // slots, eight in flight, 12.5 Gsample/s instead of 13.2; profiles/r4_ring_copy_ab.txt).
+    // (a failure here: the release waits for the copies already queued, as every hipFree does)
+    const size_t warm = std::min<size_t>(samples_per_slot * bps, 64 << 10);
+    for (int k = 0; k < c->n_slots; k++)
+        HIP_TRY(c, hipMemcpyAsync(c->ring_d_block + stride * (size_t)k, c->ring_h_block + stride * (size_t)k, warm, hipMemcpyHostToDevice,
+                                  c->scan_stream[k % c->n_scan_streams]));
+    for (int k = 0; k < c->n_scan_streams; k++) HIP_TRY(c, hipStreamSynchronize(c->scan_stream[k]));
+    undo.keep = true;
+    for (int k = 0; k < c->n_slots; k++) {
+        auto &r = c->ring[k];
+        r.h_iq = reinterpret_cast<int16_t *>(c->ring_h_block + stride * (size_t)k);
+        r.h_iq_dev = c->ring_h_block_dev + stride * (size_t)k;
+        r.d_iq = c->ring_d_block + stride * (size_t)k;
     }
     c->ring_samples = samples_per_slot;
     c->ring_fmt = fmt;

@@ -22,95 +22,87 @@ int selftest_pass(adsb_ctx *c, const void *d_iq, size_t n_samples, std::vector<u
     const uint32_t dev_cap = (uint32_t)std::min<uint64_t>(n_samples, 1u << 26);  // a list entry per position at most
     uint64_t *d_cand = nullptr;
     uint32_t *d_count = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d_cand, (size_t)dev_cap * sizeof(uint64_t)));
-    if (hipMalloc((void **)&d_count, sizeof(uint32_t)) != hipSuccess) {
-        (void)hipFree(d_cand);
-        return ADSB_ERR_NOMEM;
-    }
-    auto body = [&]() -> int {
-        HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(uint32_t), c->stream));
-        ScanParams p{};
-        p.src = d_iq;
-        p.n_samples = n_samples;
-        p.n_chunks = (uint32_t)n_chunks;
-        p.bitmap = c->d_bitmap[c->cur_bitmap];  // learned addresses only widen the superset
-        p.bitmap_lg = c->bitmap_lg;
-        p.hits = sl.d_hits;
-        p.hits_cap = sl.hits_cap;
-        p.ap = sl.d_ap;
-        p.ap_cap = c->ap_cap;
-        p.seg_cap = c->seg_cap;
-        p.tables = c->d_tables;
-        p.ctr = sl.d_ctr;
-        p.summary = sl.h_sum_dev;
-        p.cand_out = d_cand;
-        p.cand_count = d_count;
-        p.cand_cap = dev_cap;
-        if (int e = launch_scan(p, SrcFormat::kCs16, c->stream)) return fail(c, (hipError_t)e, "launch_scan");
-        Counters ctr;
-        uint32_t count = 0;
-        HIP_TRY(c, hipMemcpyAsync(&ctr, sl.d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const bool overflow = ctr.overflow != 0 || count > dev_cap;
-        bool inconsistent = false;
-        if (!overflow) {
-            std::vector<uint64_t> all(count);
-            if (count) HIP_TRY(c, hipMemcpy(all.data(), d_cand, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            for (uint64_t e : all) {
-                const uint32_t stage = (uint32_t)(e >> 28) & 3u;
-                const bool gate = ((e >> 30) & 1u) != 0;
-                const uint64_t pos = (e >> 32) << 32 | (e & 0x0FFFFFFFu);
-                if (stage >= 1 && pre) pre->push_back(pos);
-                if (stage >= 2 && snr) snr->push_back(pos);
-                if (gate && cands) cands->push_back(pos);
-                // the production gates (gate_eval) and the reference's own sequence (preamble_stage) must agree
-                inconsistent = inconsistent || (gate != (stage == 3));
-            }
-            for (auto *v : {pre, snr, cands})
-                if (v) std::sort(v->begin(), v->end());
-            if (aps) {
-                const std::vector<uint32_t> tab = build_gf_tables();
-                const uint32_t *x56 = tab.data() + kTabX56 * 256;
-                std::vector<uint64_t> seg(c->seg_cap);
-                for (int g = 0; g < kApWaveSegs; g++) {
-                    const uint32_t k = ctr.seg_ap[g];
-                    if (!k) continue;
-                    HIP_TRY(c, hipMemcpy(seg.data(), sl.d_ap + (size_t)g * c->seg_cap, (size_t)k * sizeof(uint64_t),
-                                         hipMemcpyDeviceToHost));
-                    for (uint32_t i = 0; i < k; i++) {
-                        const uint64_t e = seg[i];
-                        const uint32_t code = entry_code(e);
-                        uint32_t v = entry_value(e);
-                        if (code >= 5 && code < 10) v = x56[v & 255u] ^ x56[256 + ((v >> 8) & 255u)] ^ x56[512 + (v >> 16)];
-                        aps->push_back(pack_entry(v, entry_tp(e), entry_j(e), entry_chunk(e)));
-                    }
+    ScratchRegistry scratch;   // (its release waits for whatever an early return leaves on the stream)
+    HIP_TRY(c, scratch.add(Registry::kDevice, (void **)&d_cand, (size_t)dev_cap * sizeof(uint64_t)));
+    HIP_TRY(c, scratch.add(Registry::kDevice, (void **)&d_count, sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(uint32_t), c->stream));
+    ScanParams p{};
+    p.src = d_iq;
+    p.n_samples = n_samples;
+    p.n_chunks = (uint32_t)n_chunks;
+    p.bitmap = c->d_bitmap[c->cur_bitmap];  // learned addresses only widen the superset
+    p.bitmap_lg = c->bitmap_lg;
+    p.hits = sl.d_hits;
+    p.hits_cap = sl.hits_cap;
+    p.ap = sl.d_ap;
+    p.ap_cap = c->ap_cap;
+    p.seg_cap = c->seg_cap;
+    p.tables = c->d_tables;
+    p.ctr = sl.d_ctr;
+    p.summary = sl.h_sum_dev;
+    p.cand_out = d_cand;
+    p.cand_count = d_count;
+    p.cand_cap = dev_cap;
+    if (int e = launch_scan(p, SrcFormat::kCs16, c->stream)) return fail(c, (hipError_t)e, "launch_scan");
+    Counters ctr;
+    uint32_t count = 0;
+    HIP_TRY(c, hipMemcpyAsync(&ctr, sl.d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const bool overflow = ctr.overflow != 0 || count > dev_cap;
+    bool inconsistent = false;
+    if (!overflow) {
+        std::vector<uint64_t> all(count);
+        if (count) HIP_TRY(c, hipMemcpy(all.data(), d_cand, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t e : all) {
+            const uint32_t stage = (uint32_t)(e >> 28) & 3u;
+            const bool gate = ((e >> 30) & 1u) != 0;
+            const uint64_t pos = (e >> 32) << 32 | (e & 0x0FFFFFFFu);
+            if (stage >= 1 && pre) pre->push_back(pos);
+            if (stage >= 2 && snr) snr->push_back(pos);
+            if (gate && cands) cands->push_back(pos);
+            // the production gates (gate_eval) and the reference's own sequence (preamble_stage) must agree
+            inconsistent = inconsistent || (gate != (stage == 3));
+        }
+        for (auto *v : {pre, snr, cands})
+            if (v) std::sort(v->begin(), v->end());
+        if (aps) {
+            const std::vector<uint32_t> tab = build_gf_tables();
+            const uint32_t *x56 = tab.data() + kTabX56 * 256;
+            std::vector<uint64_t> seg(c->seg_cap);
+            for (int g = 0; g < kApWaveSegs; g++) {
+                const uint32_t k = ctr.seg_ap[g];
+                if (!k) continue;
+                HIP_TRY(c, hipMemcpy(seg.data(), sl.d_ap + (size_t)g * c->seg_cap, (size_t)k * sizeof(uint64_t),
+                                     hipMemcpyDeviceToHost));
+                for (uint32_t i = 0; i < k; i++) {
+                    const uint64_t e = seg[i];
+                    const uint32_t code = entry_code(e);
+                    uint32_t v = entry_value(e);
+                    if (code >= 5 && code < 10) v = x56[v & 255u] ^ x56[256 + ((v >> 8) & 255u)] ^ x56[512 + (v >> 16)];
+                    aps->push_back(pack_entry(v, entry_tp(e), entry_j(e), entry_chunk(e)));
                 }
-                std::sort(aps->begin(), aps->end());
             }
+            std::sort(aps->begin(), aps->end());
         }
-        // put the slot back: the records kernel zeroes this pass's counters on its way out
-        p.cand_out = nullptr;
-        sl.seq = c->next_seq++;
-        if (c->next_seq == 0) c->next_seq = 1;
-        sl.h_sum->seq = 0;
-        p.seq = sl.seq;
-        if (int e = launch_records(p, SrcFormat::kCs16, sl.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (overflow) {
-            c->last_error = "selftest: the pass overflowed the fast scan's lists";
-            return ADSB_ERR_HIP;
-        }
-        if (inconsistent) {
-            c->last_error = "selftest: the scan's gates and the reference's sequence of tests disagree on a position";
-            return ADSB_ERR_HIP;
-        }
-        return ADSB_OK;
-    };
-    const int rc = body();
-    (void)hipFree(d_cand);
-    (void)hipFree(d_count);
-    return rc;
+    }
+    // put the slot back: the records kernel zeroes this pass's counters on its way out
+    p.cand_out = nullptr;
+    sl.seq = c->next_seq++;
+    if (c->next_seq == 0) c->next_seq = 1;
+    sl.h_sum->seq = 0;
+    p.seq = sl.seq;
+    if (int e = launch_records(p, SrcFormat::kCs16, sl.h_rec_dev, c->stream)) return fail(c, (hipError_t)e, "launch_records");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (overflow) {
+        c->last_error = "selftest: the pass overflowed the fast scan's lists";
+        return ADSB_ERR_HIP;
+    }
+    if (inconsistent) {
+        c->last_error = "selftest: the scan's gates and the reference's sequence of tests disagree on a position";
+        return ADSB_ERR_HIP;
+    }
+    return ADSB_OK;
 }
 
 int hand_out(const std::vector<uint64_t> &a, uint64_t *out_a, size_t cap_a, size_t *n_a, const std::vector<uint64_t> &b,
@@ -159,18 +151,14 @@ try {
     if (n == 0) return ADSB_OK;
     ADSB_ON_DEVICE(c);
     uint32_t *d_buf = nullptr;   // the residuals, then the answers
-    HIP_TRY(c, hipMalloc((void **)&d_buf, 2 * n * sizeof(uint32_t)));
-    const auto body = [&]() -> int {
-        HIP_TRY(c, hipMemcpyAsync(d_buf, residuals, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        if (int e = launch_fix_lookup(c->d_tables, d_buf, (uint32_t)n, (uint32_t)mode, d_buf + n, c->stream))
-            return fail(c, (hipError_t)e, "launch_fix_lookup");
-        HIP_TRY(c, hipMemcpyAsync(out, d_buf + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return ADSB_OK;
-    };
-    const int rc = body();
-    (void)hipFree(d_buf);
-    return rc;
+    ScratchRegistry scratch;
+    HIP_TRY(c, scratch.add(Registry::kDevice, (void **)&d_buf, 2 * n * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpyAsync(d_buf, residuals, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (int e = launch_fix_lookup(c->d_tables, d_buf, (uint32_t)n, (uint32_t)mode, d_buf + n, c->stream))
+        return fail(c, (hipError_t)e, "launch_fix_lookup");
+    HIP_TRY(c, hipMemcpyAsync(out, d_buf + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ADSB_OK;
 } ADSB_ABI_CATCH
 
 int adsb_selftest_stage_lists(adsb_ctx *c, const void *d_iq, size_t n_samples, uint64_t *cand, size_t cand_cap,

@@ -86,21 +86,12 @@ int shard_begin(adsb_ctx *c, int k, const void *d_iq, uint64_t n_samples, bool f
     if (job.active || sl.busy || sl.parked) return ADSB_ERR_BUSY;
     const uint64_t n_chunks = (n_samples + kChunkSamples - 1) / kChunkSamples;
     if (n_chunks > c->max_chunks || n_chunks > kMaxChunks) return ADSB_ERR_INVALID;
-    if (!job.h_addrs) {   // (two lists: ShardJob::addr_half)
-        HIP_TRY(c, hipHostMalloc((void **)&job.h_addrs, 2 * kShardAddrCap * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(c, hipHostGetDevicePointer((void **)&job.h_addrs_dev, job.h_addrs, 0));
-    }
     // (adsb_multi's shards in contexts of more than 16 buffers: the scan lists the addresses its trials can add -- all the
     // exchange needs -- and phase 1 is the scan alone; adsb_device.h: ScanParams::fresh.  Contexts for passes of a few
     // buffers read them out of their handful of records.)
     fresh_list = fresh_list && c->bitmap_lg == kFullBitmapLg;
-    if (fresh_list && !job.h_fresh) {
-        HIP_TRY(c, hipHostMalloc((void **)&job.h_fresh, kShardAddrCap * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(c, hipHostGetDevicePointer((void **)&job.h_fresh_dev, job.h_fresh, 0));
-        HIP_TRY(c, hipMalloc((void **)&job.d_fresh_seen, kBitmapAllocWords * sizeof(uint32_t)));   // (also the `earlier` set of a scored shard)
-        HIP_TRY(c, hipHostMalloc((void **)&job.h_earlier, kShardAddrCap * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(c, hipHostGetDevicePointer((void **)&job.h_earlier_dev, job.h_earlier, 0));
-    }
+    if (!job.h_addrs || (fresh_list && !job.h_earlier))
+        if (int rc = ensure_shard_lists(c, k, fresh_list)) return rc;
     job.fresh_list = fresh_list;
     ScanParams p{};
     p.src = d_iq;
@@ -419,7 +410,7 @@ int shard_match(adsb_ctx *c, int k, const uint32_t *extra, size_t n_extra, const
                 return fail(c, (hipError_t)e, "launch_set_addresses");
             if (used_half >= 0) {
                 if (!job.addr_read[used_half])
-                    HIP_TRY(c, hipEventCreateWithFlags(&job.addr_read[used_half], hipEventDisableTiming | hipEventDisableSystemFence));
+                    HIP_TRY(c, new_event(c, &job.addr_read[used_half], kQuietEvent));
                 HIP_TRY(c, hipEventRecord(job.addr_read[used_half], qs));
             }
         }
