@@ -96,6 +96,102 @@ def random_iq(rng, n: int, run: int = 0) -> np.ndarray:
     return x
 
 
+def grid_taps(D: int):
+    """The tap counts every factor is run at (tests/test_gpu_decim_edges.py, "every factor")."""
+    return sorted({1, D + 1, 8 * D + 1, 505, 511, 512} | ({D - 1} if D > 1 else set()))
+
+
+def row_ceiling(D: int, T: int, tile: int) -> int:
+    """ceil((tile D + T + 15) / D): a row of the kernel's polyphase store before it is made odd (decim_row_len)."""
+    return -(-(tile * D + T + 15) // D)
+
+
+def rail_for(hk: int, polarity: int, lo: int = -32768, hi: int = 32767) -> int:
+    """The rail that gives h[k] x the sign of `polarity`."""
+    return hi if polarity * int(hk) > 0 else lo
+
+
+def worst_case_iq(h, D: int, n0: int, n: int, polarity: int, seed: int = 0, lo: int = -32768, hi: int = 32767,
+                  dtype=np.int16) -> np.ndarray:
+    """Full-range random (n, 2) samples in which x[n0 D - k] = polarity sign(h[k]) rail (lo or hi) on both components
+    for every k with n0 D - k >= 0: output n0's accumulator is the extreme these taps allow, positive for polarity 1
+    and negative for -1.  (A zero tap's sample stays random.)  lo, hi, dtype: bytes 0 and 255 for the 8-bit format."""
+    rng = np.random.default_rng([seed, D, n0, n, polarity % 3, len(h)])
+    x = rng.integers(lo, hi + 1, size=(n, 2), dtype=np.int64).astype(dtype)
+    assert 0 <= n0 * D < n
+    for k, hk in enumerate(np.asarray(h, dtype=np.int64)):
+        m = n0 * D - k
+        if m >= 0 and hk:
+            x[m] = rail_for(hk, polarity, lo, hi)
+    return x
+
+
+def worst_case_acc(h, D: int, n0: int, polarity: int, lo: int = -32768, hi: int = 32767) -> int:
+    """The bound the taps and the rails give output n0's accumulator: sum of h[k] (its rail) over the taps whose sample
+    lies in the stream (n0 D - k >= 0).  Python integers."""
+    return sum(int(hk) * rail_for(hk, polarity, lo, hi) for k, hk in enumerate(np.asarray(h, dtype=np.int64))
+               if n0 * D - k >= 0)
+
+
+WORST_D = (2, 7, 16)   # the factors of the accumulator leg
+
+
+def worst_case_sets(seed: int = 4000):
+    """(name, taps, shifts) of the accumulator leg: random taps of full weight, all positive, all negative, and the
+    sets that hold the tap -32768."""
+    rng = np.random.default_rng(seed)
+    sets =[("random %d" % T, random_taps(rng, T), (0, 15, 16)) for T in (2, 17, 512)]
+    sets.append(("positive", np.full(62, 65534 // 62, np.int16), (0, 15, 16)))       # 62 x 1057
+    sets.append(("negative", np.full(434, -(65534 // 434), np.int16), (0, 15, 16)))  # 434 x -151
+    sets.append(("-32768 32766", np.array([-32768, 32766], np.int16), (0, 15, 16)))
+    sets.append(("-32768", np.array([-32768], np.int16), (0,)))
+    sets.append(("32767 -32767", np.array([32767, -32767], np.int16), (0,)))
+    return sets
+
+
+def rail_u8_table() -> np.ndarray:
+    """An 8-bit table that reaches both int16 rails, linear in between: T8[b] = 257 b - 32768."""
+    t = (257 * np.arange(256, dtype=np.int64) - 32768).astype(np.int16)
+    assert t[0] == -32768 and t[255] == 32767
+    return t
+
+
+def worst_case_outputs(D: int, tile: int):
+    """(n0 of the accumulator leg, inputs of its streams): lane 0 and the last lane of the first tile, lane 0 of the
+    second, and a lane of the ragged third of a stream of 2 tile + 37 outputs (its length no multiple of D)."""
+    return (0, tile - 1, tile, 2 * tile + 20), (2 * tile + 36) * D + (1 if D == 2 else 2)
+
+
+def decimate_window(x_window, first_output: int, count: int, h, D: int, s: int) -> np.ndarray:
+    """Outputs first_output .. first_output + count - 1 of a stream from a window of its inputs: x_window[0] is input
+    max(first_output D - (T - 1), 0) of the stream and the window reaches input (first_output + count - 1) D."""
+    x = np.asarray(x_window, dtype=np.int64).reshape(-1, 2)
+    h = np.asarray(h, dtype=np.int64)
+    T = len(h)
+    lo = max(first_output * D - (T - 1), 0)
+    n = np.arange(first_output, first_output + count)
+    assert count == 0 or lo + len(x) > n[-1] * D
+    xp = np.concatenate([np.zeros((T - 1, 2), np.int64), x])   # xp[m - lo + T - 1] = x[m]
+    acc = np.zeros((count, 2), np.int64)
+    for k in range(T):
+        idx = n * D - k - lo + T - 1
+        assert (idx >= (T - 1 if lo > 0 else 0)).all()   # (behind a window that starts inside the stream: no padding)
+        acc += h[k] * xp[idx]
+    return _finish(acc, s)
+
+
+def window_inputs(first_output: int, count: int, T: int, D: int):
+    """[lo, hi): the inputs decimate_window needs for these outputs."""
+    return max(first_output * D - (T - 1), 0), (first_output + count - 1) * D + 1
+
+
+def tile_base(blk: int, first: int, D: int, T: int, tile: int) -> int:
+    """The input index k_decim's tile `blk` puts its buffer resource at: the 8-sample boundary below (the first input the
+    tile needs) - 8, or 0."""
+    i0 = first + blk * tile * D - (T - 1)
+    return max((i0 - 8) & ~7, 0)
+
+
 def hamming_sinc_taps(D: int) -> np.ndarray:
     """What adsb_decim_default_taps describes -- 8 D + 1 taps of a Hamming-windowed sinc with its cutoff at 1.2 MHz,
     round(h * 32768) -- from numpy, so that an expectation built on it does not hang on the library's libm."""

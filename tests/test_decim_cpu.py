@@ -144,3 +144,95 @@ def test_random_taps_hit_the_bound():
     for T in (1, 2, 3, 17, 512):
         h = ds.random_taps(rng, T).astype(np.int64)
         assert np.abs(h).sum() == min(65534, 32767 * T) and len(h) == T
+
+
+# ----------------------------------------------------------------------------------------------- the edge tests' inputs
+def test_worst_case_inputs_reach_the_accumulators_limit():
+    """tests/test_gpu_decim_edges.py, "the accumulator at its limit": by the int64 restatement alone, output n0's
+    accumulator is the bound the taps and the rails give, it fits an int32 with the rounding term added, and for taps of
+    full weight over a whole window it lies within 2^17 of 2^31."""
+    t = 256
+    sets = ds.worst_case_sets()
+    assert [name for name, _, _ in sets] == ["random 2", "random 17", "random 512", "positive", "negative",
+                                             "-32768 32766", "-32768", "32767 -32767"]
+    assert [int(np.abs(h.astype(np.int64)).sum()) for _, h, _ in sets] == [65534] * 6 + [32768, 65534]
+    full_windows = 0
+    for D in ds.WORST_D:
+        outputs, n = ds.worst_case_outputs(D, t)
+        assert n % D and -(-n // D) == 2 * t + 37
+        for name, h, shifts in sets:
+            T, h64 = len(h), h.astype(np.int64)
+            weight = int(np.abs(h64).sum())
+            for n0 in outputs:
+                for pol in (1, -1):
+                    x = ds.worst_case_iq(h, D, n0, n, pol).astype(np.int64)
+                    ks = [k for k in range(T) if n0 * D - k >= 0]
+                    acc = sum(int(h64[k]) * x[n0 * D - k] for k in ks)   # (python integers: no width at all)
+                    bound = ds.worst_case_acc(h, D, n0, pol)
+                    assert int(acc[0]) == int(acc[1]) == bound, (D, name, n0, pol)
+                    assert bound * pol > 0
+                    assert abs(bound) == sum(abs(int(h64[k])) * (32767 if pol * h64[k] > 0 else 32768) for k in ks)
+                    for s in shifts:
+                        r = (1 << (s - 1)) if s else 0
+                        assert abs(bound + r) < 2 ** 31
+                        want = min(max((bound + r) >> s, -32768), 32767)
+                        assert ds.decimate(x, h, D, s)[n0].tolist() == [want, want]
+                    if weight == 65534 and len(ks) == T:
+                        assert abs(bound) >= 2 ** 31 - 2 ** 17, (D, name, n0, pol)
+                        full_windows += 1
+            # every set has an output with its whole window inside the stream
+            assert any(n0 * D >= T - 1 for n0 in outputs)
+    assert full_windows >= 7 * 2 * 2 * len(ds.WORST_D)
+    # the tap -32768 against the sample -32768: 2^30, which clamps
+    x = ds.worst_case_iq([-32768], 2, 3, 10, 1)
+    assert x[6].tolist() == [-32768, -32768] and ds.decimate(x, [-32768], 2, 0)[3].tolist() == [32767, 32767]
+    assert ds.worst_case_acc([-32768], 2, 3, 1) == 2 ** 30 and ds.worst_case_acc([-32768], 2, 3, -1) == -32768 * 32767
+    # through bytes and a table with both rails the same accumulators come out
+    table = ds.rail_u8_table()
+    assert np.array_equal(np.diff(table.astype(np.int64)), np.full(255, 257))
+    for name, h, _ in sets:
+        if name in ("positive", "negative", "random 512"):
+            for pol in (1, -1):
+                b = ds.worst_case_iq(h, 7, t, (t + 5) * 7, pol, lo=0, hi=255, dtype=np.uint8)
+                assert b.dtype == np.uint8
+                x = table[b].astype(np.int64)
+                acc = sum(int(hk) * x[t * 7 - k] for k, hk in enumerate(h.astype(np.int64)))
+                assert int(acc[0]) == int(acc[1]) == ds.worst_case_acc(h, 7, t, pol)
+
+
+def test_the_factor_grid_meets_both_parities_of_the_row_length(hip_lib):
+    """decim_row_len makes ceil((tile D + T + 15) / D) odd with `| 1`: over the grid of "every factor" the ceiling is
+    even (the bump does something) and odd (it does nothing), and so it is for most single factors."""
+    t = int(hip_lib.adsb_decim_selftest_tile())
+    assert t == 256
+    both = 0
+    seen = set()
+    for D in range(2, 17):
+        taps = ds.grid_taps(D)
+        assert set(taps) >= {1, D - 1, D + 1, 8 * D + 1, 505, 511, 512} and min(taps) == 1 and max(taps) == 512
+        par = {ds.row_ceiling(D, T, t) % 2 for T in taps}
+        seen |= par
+        both += par == {0, 1}
+        # the row holds every local sample of a tile: tile D + T - 1 + 15 of them at most, D to a column
+        assert all((ds.row_ceiling(D, T, t) | 1) * D >= t * D + T - 1 + 15 for T in taps)
+    assert seen == {0, 1} and both >= 8
+
+
+def test_decimate_window_agrees_with_decimate():
+    rng = np.random.default_rng(77)
+    for D, T, s in [(2, 1, 0), (3, 17, 15), (16, 17, 15), (5, 512, 16)]:
+        h = ds.random_taps(rng, T)
+        x = ds.random_iq(rng, 700 * D + 3, run=T)
+        want = ds.decimate(x, h, D, s)
+        for first, count in [(0, 1), (0, 40), (1, 5), (T // D, 9), (T // D + 1, 300), (len(want) - 3, 3), (len(want) - 1, 1)]:
+            lo, hi = ds.window_inputs(first, count, T, D)
+            assert 0 <= lo < hi <= len(x)
+            assert lo == 0 or lo == first * D - (T - 1)
+            assert np.array_equal(ds.decimate_window(x[lo:hi], first, count, h, D, s), want[first:first + count]), (D, T, first)
+        # a window one sample short is refused, not padded
+        lo, hi = ds.window_inputs(T // D + 1, 5, T, D)
+        with pytest.raises(AssertionError):
+            ds.decimate_window(x[lo:hi - 1], T // D + 1, 5, h, D, s)
+    # the tile origin the large call's windows are chosen from: 8-sample boundaries, never in front of the call
+    assert ds.tile_base(0, 0, 16, 17, 256) == 0 and ds.tile_base(1, 0, 16, 17, 256) == 4096 - 16 - 8
+    assert ds.tile_base(1, 3, 2, 17, 256) == (3 + 512 - 16 - 8) & ~7 == 488
