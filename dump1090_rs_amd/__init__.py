@@ -18,6 +18,9 @@ from .context import (  # noqa: F401
     Context,
     Decimator,
     default_taps,
+    Resampler,
+    default_resampler_taps,
+    ratio_for_rate,
     MagnitudeBuffer,
     ModeSMessage,
     replay_records_rx,
@@ -28,5 +31,6 @@ from . import demod_2400, icao_filter, utils  # noqa: F401
 __all__ = [
     "MODES_MAG_BUF_SAMPLES", "MODES_LONG_MSG_BYTES", "MODES_SHORT_MSG_BYTES", "TRAILING_SAMPLES",
     "MagnitudeBuffer", "ModeSMessage", "Context", "default_context", "Decimator", "default_taps",
+    "Resampler", "default_resampler_taps", "ratio_for_rate",
     "utils", "demod_2400", "icao_filter",
 ]

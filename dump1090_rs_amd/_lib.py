@@ -307,6 +307,23 @@ def lib() -> C.CDLL:
     for name in ("adsb_decim_create", "adsb_decim_reset", "adsb_decim_out_count", "adsb_decim_run_device",
                  "adsb_decim_demod_iq", "adsb_decim_default_taps"):
         getattr(L, name).restype = C.c_int
+    # resampling (include/adsb_hip.h)
+    u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
+    L.adsb_resamp_create.argtypes = [vp, u32, u32, vp, u32, u32, C.POINTER(vp)]
+    L.adsb_resamp_destroy.argtypes = [vp]
+    L.adsb_resamp_destroy.restype = None
+    L.adsb_resamp_reset.argtypes = [vp]
+    L.adsb_resamp_out_count.argtypes = [vp, sz, C.POINTER(sz)]
+    L.adsb_resamp_run_device.argtypes = [vp, C.c_int, vp, sz, vp, sz, C.POINTER(sz)]
+    L.adsb_resamp_demod_iq.argtypes = [vp, C.c_int, vp, sz, vp, sz, C.POINTER(sz)]
+    L.adsb_resamp_default_taps.argtypes = [u32, u32, i16p, sz, u32p, u32p]
+    L.adsb_resamp_ratio_for_rate.argtypes = [u32, u32p, u32p]
+    L.adsb_resamp_plan.argtypes = [u32, u32, u64, u64, u64p, u64p]
+    L.adsb_resamp_selftest_tile.argtypes = [u32, u32]
+    L.adsb_resamp_selftest_tile.restype = u32
+    for name in ("adsb_resamp_create", "adsb_resamp_reset", "adsb_resamp_out_count", "adsb_resamp_run_device",
+                 "adsb_resamp_demod_iq", "adsb_resamp_default_taps", "adsb_resamp_ratio_for_rate", "adsb_resamp_plan"):
+        getattr(L, name).restype = C.c_int
     L.adsb_host_replays.argtypes = [vp]
     L.adsb_host_replays.restype = C.c_uint64
     L.adsb_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]

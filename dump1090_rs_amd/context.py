@@ -341,6 +341,11 @@ class Context:
         (include/adsb_hip.h, "Decimation").  taps=None: default_taps(factor)."""
         return Decimator(self, factor, taps, shift)
 
+    def resampler(self, up: int, down: int, taps=None, shift: Optional[int] = None) -> "Resampler":
+        """An exact-integer up / down resampler in front of this context's passes, for IQ sampled at 2.4 MS/s x down / up
+        (include/adsb_hip.h, "Resampling").  taps=None: default_resampler_taps(up, down)."""
+        return Resampler(self, up, down, taps, shift)
+
     def collect_raw(self, out_buf, cap: int) -> int:
         n = C.c_size_t()
         self._check(self._L.adsb_collect(self._h, out_buf, cap, C.byref(n)), "adsb_collect")
@@ -688,6 +693,105 @@ class Decimator:
         return self._ctx._collect(
             lambda out, c, n: self._L.adsb_decim_demod_iq(self._h, int(format), ptr, a.shape[0], out, c, n),
             "adsb_decim_demod_iq", cap)
+
+
+def default_resampler_taps(up: int, down: int):
+    """adsb_resamp_default_taps (host only): (taps int16[8 max(up, down) + 1], shift) of a Hamming-windowed sinc over the
+    zero-stuffed rate with its cutoff at half the lower of the two rates."""
+    L = _lib.lib()
+    taps = np.zeros(8 * max(int(up), int(down), 1) + 1, dtype=np.int16)
+    n, shift = C.c_uint32(), C.c_uint32()
+    st = L.adsb_resamp_default_taps(int(up), int(down), taps.ctypes.data_as(C.POINTER(C.c_int16)), taps.size, C.byref(n),
+                                    C.byref(shift))
+    if st != _lib.ADSB_OK:
+        raise AdsbError(st, f"adsb_resamp_default_taps: {L.adsb_strerror(st).decode()}")
+    return taps[: n.value], int(shift.value)
+
+
+def ratio_for_rate(rate_hz: int):
+    """adsb_resamp_ratio_for_rate (host only): (up, down) that bring rate_hz to 2.4 MS/s.  AdsbError (ADSB_ERR_INVALID,
+    with the terms in .ratio) where the ratio is outside what a resampler takes."""
+    L = _lib.lib()
+    up, down = C.c_uint32(), C.c_uint32()
+    if not 0 < int(rate_hz) < 1 << 32:
+        raise AdsbError(_lib.ADSB_ERR_INVALID, f"adsb_resamp_ratio_for_rate: {rate_hz} Hz")
+    st = L.adsb_resamp_ratio_for_rate(int(rate_hz), C.byref(up), C.byref(down))
+    if st != _lib.ADSB_OK:
+        err = AdsbError(st, f"adsb_resamp_ratio_for_rate: {rate_hz} Hz needs {up.value}/{down.value}")
+        err.ratio = (up.value, down.value)
+        raise err
+    return up.value, down.value
+
+
+class Resampler:
+    """One adsb_resamp: a stateful exact-integer polyphase FIR resampler by up / down on the context's device.  Close it
+    before its context."""
+
+    def __init__(self, ctx: Context, up: int, down: int, taps=None, shift: Optional[int] = None):
+        self._ctx, self._L = ctx, ctx._L
+        self._h = C.c_void_p()
+        if taps is None:
+            taps, default_shift = default_resampler_taps(up, down)
+            shift = default_shift if shift is None else shift
+        elif shift is None:
+            raise ValueError("taps of the caller's need a shift")
+        t = np.ascontiguousarray(taps, dtype=np.int16)
+        if t.ndim != 1:
+            raise ValueError("the taps are a flat int16 array")
+        self.up, self.down, self.taps, self.shift = int(up), int(down), t, int(shift)
+        self._check(self._L.adsb_resamp_create(ctx._h, int(up), int(down), t.ctypes.data, t.size, int(shift), C.byref(self._h)),
+                    "adsb_resamp_create")
+
+    def _check(self, st: int, what: str) -> None:
+        self._ctx._check(st, what)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            if self._ctx._h.value:   # (a context that is gone took the device state with it)
+                self._L.adsb_resamp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self) -> None:
+        self._check(self._L.adsb_resamp_reset(self._h), "adsb_resamp_reset")
+
+    def out_count(self, n_in: int) -> int:
+        n = C.c_size_t()
+        self._check(self._L.adsb_resamp_out_count(self._h, int(n_in), C.byref(n)), "adsb_resamp_out_count")
+        return n.value
+
+    def run_device(self, ptr_in: int, n_in: int, ptr_out: int, out_cap: int, format: int = _lib.ADSB_DECIM_CS16) -> int:
+        """Device memory to device memory, enqueued without waiting; returns the output count.  AdsbError with status
+        ADSB_ERR_CAPACITY (and the required count in .required) when out_cap is too small: nothing was consumed."""
+        n = C.c_size_t()
+        st = self._L.adsb_resamp_run_device(self._h, int(format), C.c_void_p(ptr_in), int(n_in), C.c_void_p(ptr_out), int(out_cap),
+                                            C.byref(n))
+        if st == _lib.ADSB_ERR_CAPACITY:
+            err = AdsbError(st, f"adsb_resamp_run_device: {n.value} outputs do not fit {out_cap}")
+            err.required = n.value
+            raise err
+        self._check(st, "adsb_resamp_run_device")
+        return n.value
+
+    def demod_iq(self, iq, format: int = _lib.ADSB_DECIM_CS16, cap: Optional[int] = None) -> List[ModeSMessage]:
+        """Host IQ at 2.4 MS/s x down / up of any length -> the messages of the resampled stream (blocking)."""
+        a = _as_cu8(iq) if format == _lib.ADSB_DECIM_8BIT else _as_iq(iq)
+        cap = cap or max(4096, a.shape[0] * self.up // (256 * self.down))
+        ptr = a.ctypes.data
+        return self._ctx._collect(
+            lambda out, c, n: self._L.adsb_resamp_demod_iq(self._h, int(format), ptr, a.shape[0], out, c, n),
+            "adsb_resamp_demod_iq", cap)
 
 
 _default: Optional[Context] = None

@@ -8,6 +8,7 @@
 //   adsb_replay_host.cpp  the ordered host replay and the other host-only entry points (no HIP: also built by g++ under sanitizers)
 //   adsb_ring.cpp      the pinned streaming ring
 //   adsb_decim.cpp     the decimator in front of the scan: its handle, counts, staging and default taps
+//   adsb_resamp.cpp    the L/M resampler in front of the scan: its handle, counts, staging, default taps and ratios
 //   adsb_shard.cpp     the two-phase shard calls
 //   adsb_selftest.cpp  stage lists and digests for the tests
 #pragma once

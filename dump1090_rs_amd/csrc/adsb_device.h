@@ -430,6 +430,32 @@ struct DecimParams {
 };
 uint32_t decim_row_len(uint32_t factor, uint32_t n_taps);
 int launch_decim(const DecimParams &p, void *stream);
+// Resampling (adsb_resamp_*; adsb_resamp.hip: k_resamp, k_resamp_history): one call's inputs -> its outputs at up / down
+// times the rate and the history the next call starts from.  A kernel of its own beside the decimator's.
+constexpr uint32_t kResampMaxRatio = 128, kResampMaxTaps = 4096, kResampMaxPhaseTaps = 512, kResampMaxShift = 16;
+constexpr uint32_t kResampHistWords = 512;     // a history buffer: the last K - 1 inputs, widened, at [0, K - 1)
+constexpr uint32_t kResampLdsWords = 16384;    // 64 KB per workgroup at most
+struct ResampParams {
+    const void *src;            // the call's inputs: CS16 dwords or byte pairs, 16-byte aligned
+    uint64_t n_in;              // ... how many (> 0)
+    const uint32_t *hist_prev;  // the K - 1 inputs in front of the call (zero where the stream had not begun)
+    uint32_t *hist_next;        // ... and in front of the next one (the other buffer)
+    const int32_t *taps;        // device memory in polyphase order: [phase p][j] = h[p + j up], k_pad to a phase, zero-padded
+    const uint16_t *u8_table;   // 8-bit input: the widening table (device memory), else null
+    uint32_t *out;              // CS16 dwords (4-byte aligned; 16-byte aligned: 16-byte stores)
+    uint64_t n_out;             // outputs of the call (may be 0: only the history moves on)
+    uint32_t up, down;          // L, M
+    uint32_t k_taps, k_pad;     // K = ceil(T / L), and K rounded up to a multiple of eight
+    uint32_t shift;
+    uint32_t p0, q0;            // the call's first output n0: (n0 M) mod L, and floor(n0 M / L) - P (its newest input, in the call)
+    uint32_t rows;              // R = resamp_rows(up, down): a workgroup takes up x R outputs
+    uint32_t row_len;           // resamp_row_len(down, rows, k_taps): dwords per polyphase row in LDS
+    uint32_t recip_up, recip_down;   // ceil(2^32 / L), ceil(2^32 / M) (unused where the divisor is 1)
+};
+uint32_t resamp_rows(uint32_t up, uint32_t down);
+uint32_t resamp_row_len(uint32_t down, uint32_t rows, uint32_t k_taps);
+uint32_t resamp_lds_words(uint32_t up, uint32_t down, uint32_t rows, uint32_t k_taps);
+int launch_resamp(const ResampParams &p, void *stream);
 // self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
 int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 

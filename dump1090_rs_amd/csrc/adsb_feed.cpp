@@ -5,12 +5,18 @@
 // the dump1090 raw format) can consume it.
 //
 //   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K]
-//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D] <capture.iq | ->
+//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] <capture.iq | ->
 //
 // --decimate D (2..16): the input is sampled at D x 2.4 MS/s, in the format --format names, and goes through the
 // library's decimator with its default taps (adsb_decim_default_taps) in front of the demodulation: the output lines are
 // those of the decimated stream, cut into 131072-sample buffers as that stream would be.  This path is the blocking call
 // (adsb_decim_demod_iq), K buffers of output per call, not the ring: --latency-ms and --readers do not apply to it.
+//
+// --resample L/M: the input is sampled at 2.4 MS/s x M / L (an Airspy at 10 MS/s: 6/25; include/adsb_hip.h, "Resampling")
+// and goes through the library's resampler with its default taps (adsb_resamp_default_taps) the same way, through
+// adsb_resamp_demod_iq.  A call takes the input of K output buffers, K rounded up to a multiple of L's odd part so that
+// the input of a call is a whole number of samples and every call ends on a buffer boundary of the resampled stream.
+// Not together with --decimate.
 //
 // --stats turns the signal statistics on (adsb_set_signal_stats) and prints what a receiver's gain is tuned by to
 // STDERR, every SECONDS (default 1) over the buffers since the last line and once more, as the last line, over the
@@ -315,6 +321,7 @@ int main(int argc, char **argv)
     bool quiet = false, mem_order = false, cu8 = false, stats = false;
     double stats_seconds = 1.0;
     int fix = ADSB_FIX_NONE, decimate = 0;
+    unsigned res_up = 0, res_down = 0;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -326,6 +333,13 @@ int main(int argc, char **argv)
         else if (a == "--decimate" && i + 1 < argc) {
             decimate = std::atoi(argv[++i]);
             if (decimate < 2 || decimate > 16) path = nullptr, i = argc;
+        }
+        else if (a == "--resample" && i + 1 < argc) {
+            char tail = 0;
+            uint32_t n_taps = 0;
+            if (std::sscanf(argv[++i], "%u/%u%c", &res_up, &res_down, &tail) != 2 ||
+                adsb_resamp_default_taps(res_up, res_down, nullptr, 0, &n_taps, nullptr) != ADSB_ERR_CAPACITY)
+                path = nullptr, i = argc;
         }
         else if (a == "--out-cap" && i + 1 < argc) out_cap = std::atoi(argv[++i]);  // frames the output array starts with (it grows)
         else if (a == "--stats") {
@@ -352,8 +366,8 @@ int main(int argc, char **argv)
         else if (a == "--help" || a == "-h") path = nullptr, i = argc;
         else path = argv[i];
     }
-    if (!path || buffers < 1) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D] <capture.iq | ->\n");
+    if (!path || buffers < 1 || (decimate && res_up)) {
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -374,7 +388,8 @@ int main(int argc, char **argv)
     if ((st = adsb_set_error_correction(ctx, fix)) != ADSB_OK) return die(ctx, "adsb_set_error_correction", st);
     if (stats && (st = adsb_set_signal_stats(ctx, 1)) != ADSB_OK) return die(ctx, "adsb_set_signal_stats", st);
     const size_t slot_samples = (size_t)buffers * ADSB_MODES_MAG_BUF_SAMPLES;
-    if (!decimate && (st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
+    const bool blocking = decimate || res_up;   // through the decimator or the resampler: the blocking call, not the ring
+    if (!blocking && (st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
         return die(ctx, "adsb_ring_create", st);
     const size_t bps = cu8 ? 2 : 4;   // bytes per sample
 
@@ -423,16 +438,33 @@ int main(int argc, char **argv)
         return ADSB_OK;
     };
 
-    if (decimate) {
-        // D x 2.4 MS/s: whole calls of `buffers` output buffers' worth of input, so that the decimated stream is cut
-        // where consecutive reads of 131072 samples of it would cut it
-        int16_t taps[8 * 16 + 1];
+    if (blocking) {
+        // D x 2.4 MS/s, or 2.4 MS/s x M / L: whole calls of the input of `buffers` output buffers (--resample: of the
+        // next multiple of L's odd part), so that the decimated or resampled stream is cut where consecutive reads of
+        // 131072 samples of it would cut it
+        int16_t taps[8 * 128 + 1];
         uint32_t n_taps = 0, shift = 0;
         adsb_decim *dec = nullptr;
-        if ((st = adsb_decim_default_taps((uint32_t)decimate, taps, sizeof(taps) / sizeof(taps[0]), &n_taps, &shift)) != ADSB_OK)
-            return die(ctx, "adsb_decim_default_taps", st);
-        if ((st = adsb_decim_create(ctx, (uint32_t)decimate, taps, n_taps, shift, &dec)) != ADSB_OK) return die(ctx, "adsb_decim_create", st);
-        const size_t call_samples = slot_samples * (size_t)decimate;
+        adsb_resamp *res = nullptr;
+        size_t call_samples = 0;
+        if (decimate) {
+            if ((st = adsb_decim_default_taps((uint32_t)decimate, taps, sizeof(taps) / sizeof(taps[0]), &n_taps, &shift)) != ADSB_OK)
+                return die(ctx, "adsb_decim_default_taps", st);
+            if ((st = adsb_decim_create(ctx, (uint32_t)decimate, taps, n_taps, shift, &dec)) != ADSB_OK) return die(ctx, "adsb_decim_create", st);
+            call_samples = slot_samples * (size_t)decimate;
+        } else {
+            if ((st = adsb_resamp_default_taps(res_up, res_down, taps, sizeof(taps) / sizeof(taps[0]), &n_taps, &shift)) != ADSB_OK)
+                return die(ctx, "adsb_resamp_default_taps", st);
+            if ((st = adsb_resamp_create(ctx, res_up, res_down, taps, n_taps, shift, &res)) != ADSB_OK) return die(ctx, "adsb_resamp_create", st);
+            // 2.4 MS/s x M / L: K 131072 M / L inputs give K output buffers; a whole number where L's odd part divides K
+            unsigned odd = res_up;
+            while (odd % 2 == 0) odd /= 2;
+            const size_t k = ((size_t)buffers + odd - 1) / odd * odd;
+            call_samples = k * ADSB_MODES_MAG_BUF_SAMPLES / res_up * res_down;
+            sig.resize(k);
+            if (out_cap <= 0) out.resize(k * 4096);
+        }
+        const auto destroy = [&] { adsb_decim_destroy(dec), adsb_resamp_destroy(res); };
         std::vector<char> in_buf(call_samples * bps);
         const auto t0 = std::chrono::steady_clock::now();
         for (bool eof = false; !eof;) {
@@ -445,19 +477,21 @@ int main(int argc, char **argv)
             if (n_in == 0) break;
             if (!mem_order && !cu8) swap_pairs(in_buf.data(), n_in);
             size_t n = 0;
-            st = adsb_decim_demod_iq(dec, cu8 ? ADSB_DECIM_8BIT : ADSB_DECIM_CS16, in_buf.data(), n_in, out.data(), out.size(), &n);
+            const int fmt = cu8 ? ADSB_DECIM_8BIT : ADSB_DECIM_CS16;
+            st = dec ? adsb_decim_demod_iq(dec, fmt, in_buf.data(), n_in, out.data(), out.size(), &n)
+                     : adsb_resamp_demod_iq(res, fmt, in_buf.data(), n_in, out.data(), out.size(), &n);
             if (st == ADSB_ERR_CAPACITY) {
                 out.resize(n);
                 st = adsb_fetch_messages(ctx, out.data(), out.size(), &n);
             }
             if (st != ADSB_OK) {
-                adsb_decim_destroy(dec);
-                return die(ctx, "adsb_decim_demod_iq", st);
+                destroy();
+                return die(ctx, dec ? "adsb_decim_demod_iq" : "adsb_resamp_demod_iq", st);
             }
             if (stats) {
                 size_t n_sig = 0;
                 if ((st = adsb_fetch_signal_stats(ctx, sig.data(), sig.size(), &n_sig)) != ADSB_OK) {
-                    adsb_decim_destroy(dec);
+                    destroy();
                     return die(ctx, "adsb_fetch_signal_stats", st);
                 }
                 for (size_t i = 0; i < n_sig; i++) sig_total.add(sig[i]);
@@ -466,11 +500,15 @@ int main(int argc, char **argv)
             total_samples += n_in;
         }
         const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        std::fprintf(stderr, "adsb_feed: %llu samples at %d x 2.4 MS/s, %llu frames in %.3f s (%.1f Msamples/s); %llu clients dropped\n",
-                     total_samples, decimate, total_frames, secs, secs > 0 ? total_samples / secs / 1e6 : 0.0, clients.dropped);
+        if (dec)
+            std::fprintf(stderr, "adsb_feed: %llu samples at %d x 2.4 MS/s, %llu frames in %.3f s (%.1f Msamples/s); %llu clients dropped\n",
+                         total_samples, decimate, total_frames, secs, secs > 0 ? total_samples / secs / 1e6 : 0.0, clients.dropped);
+        else
+            std::fprintf(stderr, "adsb_feed: %llu samples resampled by %u/%u to 2.4 MS/s, %llu frames in %.3f s (%.1f Msamples/s); %llu clients dropped\n",
+                         total_samples, res_up, res_down, total_frames, secs, secs > 0 ? total_samples / secs / 1e6 : 0.0, clients.dropped);
         if (stats) sig_total.print("whole input");
         if (in != 0) ::close(in);
-        adsb_decim_destroy(dec);
+        destroy();
         adsb_destroy(ctx);
         return 0;
     }

@@ -608,6 +608,84 @@ ADSB_MUST_CHECK int adsb_decim_default_taps(uint32_t factor, int16_t *taps, size
 /* Host only, for the tests: the outputs one workgroup of the decimating kernel takes. */
 uint32_t adsb_decim_selftest_tile(void);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Resampling -- IQ sampled at a rate that is no integer multiple of 2.4 MS/s: an Airspy at 2.5, 3, 6 or 10 MS/s, a
+ * HackRF at 8, 10 or 20 MS/s, an RTL-SDR at 2.0, 2.56 or 3.2 MS/s, a USRP B2xx at 12.5 MS/s.  An adsb_resamp is a
+ * stateful, exact-integer polyphase FIR resampler by a ratio L / M (`up` / `down`) that runs on the device in front of
+ * the scan, in a kernel of its own beside the decimator's: its output is ordinary CS16 in device memory, which every call
+ * above takes.  Nothing else changes.
+ *
+ * Definition.  An adsb_resamp turns input at rate f into output at rate f L / M.  x[m], m = 0, 1, ..., is the input
+ * counted from adsb_resamp_create or adsb_resamp_reset, complex, `re` then `im`; x[m] = 0 for m < 0.  With prototype taps
+ * h[0..T-1] (int16) and shift s, for n = 0, 1, ... and for re and im separately:
+ *     p = (n M) mod L,   q = floor(n M / L)
+ *     acc  = sum over j >= 0 with p + j L < T of  h[p + j L] * x[q - j]
+ *     y[n] = clamp((acc + r) >> s, -32768, 32767),   r = 1 << (s - 1), or 0 when s == 0,   >> arithmetic (a half rounds up)
+ * -- zero-stuffing by L, the FIR h, then keeping every M-th sample, with the zero products left out.  K = ceil(T / L) is
+ * the most taps one output uses.  Accepted: 1 <= L <= 128 and 1 <= M <= 128 with gcd(L, M) = 1, L <= 2 M (upsampling
+ * beyond 2 x has no use here), M <= 16 L (the decimator's reach), 1 <= T <= 4096 with K <= 512, s in 0..16, and for every
+ * phase p the sum over j of |h[p + j L]| <= 65534 (an int32 accumulator then never wraps); anything else is
+ * ADSB_ERR_INVALID.  With L = 1 the definition is the decimator's with D = M; L = M = 1 is a plain FIR.
+ * Counts.  A call of n_in inputs, P inputs having been consumed before it, produces exactly the y[n] whose newest input
+ * lies in the call, P <= floor(n M / L) < P + n_in: the n with
+ *     ceil(P L / M) <= n < ceil((P + n_in) L / M)
+ * possibly none.  The cut is invisible: the concatenated outputs of any cutting of a stream into calls -- calls of no
+ * input and calls shorter than K - 1 included -- equal the one-call result bit for bit.  The resampler keeps the last
+ * K - 1 inputs (on the device, widened, in two buffers that take turns) and P (on the host: counts are 64-bit host
+ * arithmetic, no call synchronises to learn one).
+ * 8-bit input (ADSB_DECIM_8BIT, or its alias ADSB_RESAMP_8BIT) works as in the decimator: byte b means T8[b], T8 the
+ * context's table at the time of the call; the bytes are widened as they are loaded and the history is kept widened, so a
+ * stream may alternate the formats; x[m < 0] is zero by position, not T8[0].  (Synchronise the stream before changing the
+ * table under calls still running.)
+ *
+ *   adsb_resamp_create          a resampler on the context's device.  Destroy it before the context.
+ *   adsb_resamp_reset           the stream starts over (P = 0, zero history); ordered on the stream like a run
+ *   adsb_resamp_out_count       host only: how many outputs the next run of n_in inputs would produce
+ *   adsb_resamp_run_device      device memory to device memory (both 16-byte aligned, not overlapping), as
+ *                               adsb_decim_run_device: enqueues on the stream the context orders its input behind and
+ *                               returns without waiting; *n_out is known at once; the next pass submitted on the context
+ *                               waits for it.  out_cap too small: ADSB_ERR_CAPACITY with the required count in *n_out;
+ *                               nothing is consumed and the state does not change.  Never ADSB_ERR_BUSY.
+ *   adsb_resamp_demod_iq        blocking, host input of any length: exactly what adsb_demod_iq returns on the y this call's
+ *                               input resamples to -- buffers are cut every 131072 OUTPUT samples of the call, the last
+ *                               may be short, `chunk` counts over the call; the filter persists.  Works in pieces of whole
+ *                               output buffers, min(max_chunks, 16) of them at most, through staging the resampler
+ *                               allocates on first use and frees in adsb_resamp_destroy.  (Where L > M two consecutive
+ *                               outputs can share their newest input; a piece may then produce one output more than its
+ *                               buffers hold, which is carried to the front of the next piece.)  ADSB_ERR_CAPACITY,
+ *                               adsb_fetch_messages, ADSB_ERR_BUSY and every context mode are adsb_demod_iq's: the pass
+ *                               underneath is the ordinary one.
+ *   adsb_resamp_default_taps    host only: a Hamming-windowed sinc over the zero-stuffed rate with its cutoff at half the
+ *                               lower of the two rates, 8 max(L, M) + 1 taps, symmetric, scaled so that the prototype
+ *                               sums to L 2^14 -- every phase to about 2^14 -- with shift 14 (at 2^15 the centre tap would
+ *                               not fit an int16 where L > M).  Computed in double through libm: a property, not bits.
+ *                               `cap` too small: ADSB_ERR_CAPACITY with the count in *n_taps.
+ *   adsb_resamp_ratio_for_rate  host only: the ratio that brings rate_hz to 2.4 MS/s, up = 2 400 000 / g and
+ *                               down = rate_hz / g with g their greatest common divisor; ADSB_ERR_INVALID (with the
+ *                               terms still written) where the ratio is outside the limits above.
+ *   adsb_resamp_plan            host only, no handle: the count formula above -- the first output ceil(consumed L / M)
+ *                               and the number of outputs of a call of n_in inputs behind `consumed` (both < 2^56).
+ * After a HIP failure the resampler's state is undefined until adsb_resamp_reset. */
+typedef struct adsb_resamp adsb_resamp;
+#define ADSB_RESAMP_CS16 ADSB_DECIM_CS16
+#define ADSB_RESAMP_8BIT ADSB_DECIM_8BIT
+ADSB_MUST_CHECK int adsb_resamp_create(adsb_ctx *ctx, uint32_t up, uint32_t down, const int16_t *taps, uint32_t n_taps,
+                                       uint32_t shift, adsb_resamp **out);
+extern void adsb_resamp_destroy(adsb_resamp *r);
+ADSB_MUST_CHECK int adsb_resamp_reset(adsb_resamp *r);
+ADSB_MUST_CHECK int adsb_resamp_out_count(const adsb_resamp *r, size_t n_in, size_t *n_out);
+ADSB_MUST_CHECK int adsb_resamp_run_device(adsb_resamp *r, int format, const void *device_in, size_t n_in,
+                                           void *device_out_cs16, size_t out_cap, size_t *n_out);
+ADSB_MUST_CHECK int adsb_resamp_demod_iq(adsb_resamp *r, int format, const void *host_iq, size_t n_in, adsb_msg *out,
+                                         size_t cap, size_t *n_out);
+ADSB_MUST_CHECK int adsb_resamp_default_taps(uint32_t up, uint32_t down, int16_t *taps, size_t cap, uint32_t *n_taps,
+                                             uint32_t *shift);
+ADSB_MUST_CHECK int adsb_resamp_ratio_for_rate(uint32_t rate_hz, uint32_t *up, uint32_t *down);
+ADSB_MUST_CHECK int adsb_resamp_plan(uint32_t up, uint32_t down, uint64_t consumed, uint64_t n_in, uint64_t *first_n,
+                                     uint64_t *n_out);
+/* Host only, for the tests: the outputs one workgroup of the resampling kernel takes at this ratio (0: not a ratio). */
+uint32_t adsb_resamp_selftest_tile(uint32_t up, uint32_t down);
+
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167
  * is one stream with one process-global filter, src/icao_filter.rs:8-9).  Shards run

@@ -129,6 +129,15 @@ pub struct AdsbDecim {
 pub const ADSB_DECIM_CS16: i32 = 0;
 pub const ADSB_DECIM_8BIT: i32 = 1;
 
+/// An exact-integer L/M resampler in front of the scan, for IQ at 2.5, 3, 6, 8, 10, 20 MS/s and the like (`adsb_resamp_*`).
+#[repr(C)]
+pub struct AdsbResamp {
+    _private: [u8; 0],
+}
+
+pub const ADSB_RESAMP_CS16: i32 = ADSB_DECIM_CS16;
+pub const ADSB_RESAMP_8BIT: i32 = ADSB_DECIM_8BIT;
+
 /// One capture over several GPUs from one process: one handle, one filter (`adsb_multi_*`).
 #[repr(C)]
 pub struct AdsbMulti {
@@ -245,6 +254,7 @@ unsafe extern "C" {
     pub fn adsb_last_error(ctx: *const AdsbCtx) -> *const c_char;
     pub fn adsb_version() -> *const c_char;
     pub fn adsb_decim_selftest_tile() -> u32;
+    pub fn adsb_resamp_selftest_tile(up: u32, down: u32) -> u32;
 }
 
 // The two calls that take the signal records by pointer (the header marks them ADSB_MUST_CHECK); compared with the
@@ -266,4 +276,19 @@ unsafe extern "C" {
     pub fn adsb_decim_run_device(d: *mut AdsbDecim, format: c_int, device_in: *const c_void, n_in: usize, device_out_cs16: *mut c_void, out_cap: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_decim_demod_iq(d: *mut AdsbDecim, format: c_int, host_iq: *const c_void, n_in: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
     pub fn adsb_decim_default_taps(factor: u32, taps: *mut i16, cap: usize, n_taps: *mut u32, shift: *mut u32) -> c_int;
+}
+
+// The resampler's calls (the header marks them ADSB_MUST_CHECK, the destructor `extern`); compared with the header by
+// tests/test_resamp_cpu.py.
+#[link(name = "adsb_hip")]
+unsafe extern "C" {
+    pub fn adsb_resamp_create(ctx: *mut AdsbCtx, up: u32, down: u32, taps: *const i16, n_taps: u32, shift: u32, out: *mut *mut AdsbResamp) -> c_int;
+    pub fn adsb_resamp_destroy(r: *mut AdsbResamp);
+    pub fn adsb_resamp_reset(r: *mut AdsbResamp) -> c_int;
+    pub fn adsb_resamp_out_count(r: *const AdsbResamp, n_in: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_resamp_run_device(r: *mut AdsbResamp, format: c_int, device_in: *const c_void, n_in: usize, device_out_cs16: *mut c_void, out_cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_resamp_demod_iq(r: *mut AdsbResamp, format: c_int, host_iq: *const c_void, n_in: usize, out: *mut AdsbMsg, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_resamp_default_taps(up: u32, down: u32, taps: *mut i16, cap: usize, n_taps: *mut u32, shift: *mut u32) -> c_int;
+    pub fn adsb_resamp_ratio_for_rate(rate_hz: u32, up: *mut u32, down: *mut u32) -> c_int;
+    pub fn adsb_resamp_plan(up: u32, down: u32, consumed: u64, n_in: u64, first_n: *mut u64, n_out: *mut u64) -> c_int;
 }
