@@ -21,6 +21,8 @@ from .context import (  # noqa: F401
     Resampler,
     default_resampler_taps,
     ratio_for_rate,
+    mixer_table,
+    mixer_for_shift,
     MagnitudeBuffer,
     ModeSMessage,
     replay_records_rx,
@@ -31,6 +33,6 @@ from . import demod_2400, icao_filter, utils  # noqa: F401
 __all__ = [
     "MODES_MAG_BUF_SAMPLES", "MODES_LONG_MSG_BYTES", "MODES_SHORT_MSG_BYTES", "TRAILING_SAMPLES",
     "MagnitudeBuffer", "ModeSMessage", "Context", "default_context", "Decimator", "default_taps",
-    "Resampler", "default_resampler_taps", "ratio_for_rate",
+    "Resampler", "default_resampler_taps", "ratio_for_rate", "mixer_table", "mixer_for_shift",
     "utils", "demod_2400", "icao_filter",
 ]

@@ -324,6 +324,17 @@ def lib() -> C.CDLL:
     for name in ("adsb_resamp_create", "adsb_resamp_reset", "adsb_resamp_out_count", "adsb_resamp_run_device",
                  "adsb_resamp_demod_iq", "adsb_resamp_default_taps", "adsb_resamp_ratio_for_rate", "adsb_resamp_plan"):
         getattr(L, name).restype = C.c_int
+    # frequency shift (include/adsb_hip.h)
+    L.adsb_mix_set_decim.argtypes = [vp, vp, u32]
+    L.adsb_mix_set_resamp.argtypes = [vp, vp, u32]
+    L.adsb_mix_get_decim.argtypes = [vp]
+    L.adsb_mix_get_resamp.argtypes = [vp]
+    L.adsb_mix_table.argtypes = [u32, u32, i16p, sz]
+    L.adsb_mix_for_shift.argtypes = [u32, u32, C.c_int32, u32p, u32p]
+    for name in ("adsb_mix_get_decim", "adsb_mix_get_resamp"):
+        getattr(L, name).restype = u32
+    for name in ("adsb_mix_set_decim", "adsb_mix_set_resamp", "adsb_mix_table", "adsb_mix_for_shift"):
+        getattr(L, name).restype = C.c_int
     L.adsb_host_replays.argtypes = [vp]
     L.adsb_host_replays.restype = C.c_uint64
     L.adsb_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]

@@ -336,15 +336,23 @@ class Context:
         self._check(self._L.adsb_submit_iq_device(self._h, C.c_void_p(device_ptr), n_samples),
                     "adsb_submit_iq_device")
 
-    def decimator(self, factor: int, taps=None, shift: Optional[int] = None) -> "Decimator":
+    def decimator(self, factor: int, taps=None, shift: Optional[int] = None, shift_hz: Optional[int] = None) -> "Decimator":
         """An integer FIR decimator in front of this context's passes, for IQ sampled at factor x 2.4 MS/s
-        (include/adsb_hip.h, "Decimation").  taps=None: default_taps(factor)."""
-        return Decimator(self, factor, taps, shift)
+        (include/adsb_hip.h, "Decimation").  taps=None: default_taps(factor).  shift_hz: for an offset-tuned radio, how
+        far the spectrum is to be moved ("Frequency shift"): the mixer of mixer_for_shift(1, factor, shift_hz) is set."""
+        d = Decimator(self, factor, taps, shift)
+        if shift_hz is not None:
+            d.set_mixer(mixer_table(*mixer_for_shift(1, factor, shift_hz)))
+        return d
 
-    def resampler(self, up: int, down: int, taps=None, shift: Optional[int] = None) -> "Resampler":
+    def resampler(self, up: int, down: int, taps=None, shift: Optional[int] = None, shift_hz: Optional[int] = None) -> "Resampler":
         """An exact-integer up / down resampler in front of this context's passes, for IQ sampled at 2.4 MS/s x down / up
-        (include/adsb_hip.h, "Resampling").  taps=None: default_resampler_taps(up, down)."""
-        return Resampler(self, up, down, taps, shift)
+        (include/adsb_hip.h, "Resampling").  taps=None: default_resampler_taps(up, down).  shift_hz: as for decimator(),
+        with mixer_for_shift(up, down, shift_hz)."""
+        r = Resampler(self, up, down, taps, shift)
+        if shift_hz is not None:
+            r.set_mixer(mixer_table(*mixer_for_shift(up, down, shift_hz)))
+        return r
 
     def collect_raw(self, out_buf, cap: int) -> int:
         n = C.c_size_t()
@@ -612,6 +620,45 @@ class Context:
         return {name: getattr(s, name) for name, _ in AdsbStats._fields_ if name != "reserved"}
 
 
+def mixer_table(k: int, period: int):
+    """adsb_mix_table (host only): the (period, 2) int16 table {c, s} of a shift by k / period cycles per sample, amplitude
+    2^14 (include/adsb_hip.h, "Frequency shift")."""
+    L = _lib.lib()
+    if not (0 <= int(k) < 1 << 32 and 0 <= int(period) < 1 << 32):
+        raise AdsbError(_lib.ADSB_ERR_INVALID, f"adsb_mix_table: {k}/{period}")
+    table = np.zeros((max(int(period), 1), 2), dtype=np.int16)
+    st = L.adsb_mix_table(int(k), int(period), table.ctypes.data_as(C.POINTER(C.c_int16)), table.shape[0])
+    if st != _lib.ADSB_OK:
+        raise AdsbError(st, f"adsb_mix_table: {L.adsb_strerror(st).decode()}")
+    return table
+
+
+def mixer_for_shift(up: int, down: int, shift_hz: int):
+    """adsb_mix_for_shift (host only): (k, period) of the table that moves the spectrum of a stream at 2.4 MS/s x down / up
+    (a decimator: up = 1, down = factor) by shift_hz, signed.  AdsbError (ADSB_ERR_INVALID, with the terms in .terms)
+    where the period is beyond 256."""
+    L = _lib.lib()
+    k, period = C.c_uint32(), C.c_uint32()
+    if not (0 <= int(up) < 1 << 32 and 0 <= int(down) < 1 << 32 and -(1 << 31) <= int(shift_hz) < 1 << 31):
+        raise AdsbError(_lib.ADSB_ERR_INVALID, f"adsb_mix_for_shift: {up}/{down}, {shift_hz} Hz")
+    st = L.adsb_mix_for_shift(int(up), int(down), int(shift_hz), C.byref(k), C.byref(period))
+    if st != _lib.ADSB_OK:
+        err = AdsbError(st, f"adsb_mix_for_shift: {shift_hz} Hz at {up}/{down} needs {k.value}/{period.value}")
+        err.terms = (k.value, period.value)
+        raise err
+    return k.value, period.value
+
+
+def _set_mixer(handle, call, what: str, table) -> None:
+    if table is None:
+        handle._check(call(handle._h, None, 0), what)
+        return
+    t = np.ascontiguousarray(table, dtype=np.int16)
+    if t.ndim != 2 or t.shape[1] != 2:
+        raise ValueError("a mixer's table is (period, 2) int16: {c, s} pairs")
+    handle._check(call(handle._h, t.ctypes.data, t.shape[0]), what)
+
+
 def default_taps(factor: int):
     """adsb_decim_default_taps (host only): (taps int16[8 factor + 1], shift) of a Hamming-windowed sinc with its cutoff at
     1.2 MHz."""
@@ -666,6 +713,15 @@ class Decimator:
 
     def reset(self) -> None:
         self._check(self._L.adsb_decim_reset(self._h), "adsb_decim_reset")
+
+    def set_mixer(self, table) -> None:
+        """adsb_mix_set_decim: the (period, 2) int16 table {c, s} the inputs consumed from now on are mixed with (None:
+        no mixer)."""
+        _set_mixer(self, self._L.adsb_mix_set_decim, "adsb_mix_set_decim", table)
+
+    @property
+    def mixer_period(self) -> int:
+        return int(self._L.adsb_mix_get_decim(self._h))
 
     def out_count(self, n_in: int) -> int:
         n = C.c_size_t()
@@ -765,6 +821,15 @@ class Resampler:
 
     def reset(self) -> None:
         self._check(self._L.adsb_resamp_reset(self._h), "adsb_resamp_reset")
+
+    def set_mixer(self, table) -> None:
+        """adsb_mix_set_resamp: the (period, 2) int16 table {c, s} the inputs consumed from now on are mixed with
+        (None: no mixer)."""
+        _set_mixer(self, self._L.adsb_mix_set_resamp, "adsb_mix_set_resamp", table)
+
+    @property
+    def mixer_period(self) -> int:
+        return int(self._L.adsb_mix_get_resamp(self._h))
 
     def out_count(self, n_in: int) -> int:
         n = C.c_size_t()

@@ -9,6 +9,7 @@
 //   adsb_ring.cpp      the pinned streaming ring
 //   adsb_decim.cpp     the decimator in front of the scan: its handle, counts, staging and default taps
 //   adsb_resamp.cpp    the L/M resampler in front of the scan: its handle, counts, staging, default taps and ratios
+//   adsb_mix.cpp       the mixer of a decimator or resampler: its table on the device, the table and shift helpers
 //   adsb_shard.cpp     the two-phase shard calls
 //   adsb_selftest.cpp  stage lists and digests for the tests
 #pragma once
@@ -532,6 +533,30 @@ int demod_device(adsb_ctx *c, const void *d_iq, uint64_t n_samples, std::vector<
 // the context, join the call's (adsb_decim.cpp cuts its calls the same way)
 void append_piece(const adsb_ctx *c, std::vector<adsb_msg> &part, uint64_t off, std::vector<adsb_msg> &out, adsb_stats &total,
                   std::vector<adsb_signal_stats> &sig);
+// A decimator's or resampler's mixer (include/adsb_hip.h, "Frequency shift"; adsb_mix.cpp): the table in device
+// memory, reserved in the handle's registry on first use, and its period (0: off).  mixer_of is how adsb_mix.cpp reaches
+// a handle's (each handle's unit defines its own); mixer_params is what a launch is handed at P = consumed.
+struct Mixer {
+    uint2 *d_table = nullptr;
+    uint32_t period = 0;
+};
+struct MixerOwner {
+    adsb_ctx *ctx;
+    Registry *mem;
+    Mixer *mix;
+};
+MixerOwner mixer_of(adsb_decim *d);
+MixerOwner mixer_of(adsb_resamp *r);
+inline MixParams mixer_params(const Mixer &m, uint64_t consumed)
+{
+    MixParams p{};
+    if (!m.period) return p;
+    p.table = m.d_table;
+    p.period = m.period;
+    p.phase = (uint32_t)(consumed % m.period);
+    p.recip = (uint32_t)(((1ull << 32) + m.period - 1u) / m.period);
+    return p;
+}
 // T_soapy: the table SoapyRTLSDR widens an RTL-SDR's bytes with, (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f)
 void soapy_u8_table(int16_t *out256);
 // IQ staging for host-pointer calls, in device memory / pinned and mapped, grown on demand (adsb_context.cpp)

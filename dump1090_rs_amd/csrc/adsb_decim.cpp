@@ -1,6 +1,7 @@
 // adsb_decim.cpp -- the host side of the decimator (include/adsb_hip.h, "Decimation"): the handle and its argument
 // checks, the count arithmetic (all of it on the host: no call synchronises to learn a count), the staging and the piece
-// loop of adsb_decim_demod_iq, and the default taps.  The kernels are adsb_decim.hip's.
+// loop of adsb_decim_demod_iq, and the default taps.  The kernels are adsb_decim.hip's.  (The mixer's host side is
+// adsb_mix.cpp's: this unit hands it its handle's mixer, and a launch the mixer's parameters.)
 #include <cmath>
 
 #include "adsb_ctx.h"
@@ -22,8 +23,15 @@ struct adsb_decim {
     size_t in_bytes = 0;
     void *d_out = nullptr;
     size_t out_bytes = 0;
-    Registry mem;   // owns the five buffers above
+    Mixer mix;
+    Registry mem;   // owns the five buffers above and the mixer's table
 };
+
+namespace adsb {
+namespace host {
+MixerOwner mixer_of(adsb_decim *d) { return {d->ctx, &d->mem, &d->mix}; }
+}  // namespace host
+}  // namespace adsb
 
 namespace {
 
@@ -59,6 +67,7 @@ int run_on_stream(adsb_decim *d, int format, const void *d_in, uint64_t n_in, vo
     p.first = first_output_at(d);
     p.row_len = decim_row_len(d->factor, d->n_taps);
     p.recip = ((1u << 20) + d->factor - 1u) / d->factor;
+    p.mix = mixer_params(d->mix, d->consumed);
     if (int e = launch_decim(p, c->stream)) return fail(c, (hipError_t)e, "launch_decim");
     // (the next pass reads what this put on the context's own stream: order_behind_input)
     if (c->stream == c->own_stream) c->own_stream_dirty = true;
@@ -176,6 +185,8 @@ try {
     d->consumed = 0;
     return ADSB_OK;
 } ADSB_ABI_CATCH
+
+uint32_t adsb_mix_get_decim(const adsb_decim *d) { return d ? d->mix.period : 0; }
 
 int adsb_decim_out_count(const adsb_decim *d, size_t n_in, size_t *n_out)
 {

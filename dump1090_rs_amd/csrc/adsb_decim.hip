@@ -18,12 +18,17 @@
 //     multiply samples that exist.)
 //   * re and im stay packed in their dword: one v_dot2_i32_i16 per half, against {h, 0} and {0, h};
 //   * CU8 input is widened as it is stored to LDS, through a copy of the context's table in LDS, and masked by
-//     position: a sample in front of the stream is zero, not T[0].
+//     position: a sample in front of the stream is zero, not T[0];
+//   * MIX (include/adsb_hip.h, "Frequency shift"): a sample is mixed with its table entry between the widening and the
+//     store to LDS -- the samples of the call, not the history's, which holds mixed ones.  The workgroup reduces its
+//     tile's origin mod N once, a load its first sample's phase by a multiplication, and the phase then steps with a wrap
+//     per sample; the table comes through cached global loads (adsb_mix_dev.h) and takes no LDS.
 // No scratch, no spills; LDS per workgroup: 4 (D row_len) bytes, row_len = ceil((256 D + T + 15) / D) | 1 -- 2.3 KB
 // at D = 2 with 17 taps, 18.6 KB at D = 16 with 512 -- plus 512 bytes of table for CU8: eight workgroups (32 waves)
 // fit a CU's LDS in every case.
 #include "../../include/adsb_hip.h"
 #include "adsb_dev_common.h"
+#include "adsb_mix_dev.h"
 
 namespace adsb {
 
@@ -52,7 +57,7 @@ __device__ __forceinline__ int round_clamp(int acc, uint32_t shift, int round)
     return min(max((acc + round) >> shift, -32768), 32767);
 }
 
-template <bool U8>
+template <bool U8, bool MIX>
 __global__ __launch_bounds__(kThreadsDecim) void k_decim(DecimParams p)
 {
     extern __shared__ uint32_t lds[];
@@ -89,6 +94,9 @@ __global__ __launch_bounds__(kThreadsDecim) void k_decim(DecimParams p)
         tab[tid] = p.u8_table[tid];
         __syncthreads();
     }
+    // the table entry of local sample 0 (the tile's origin a0 = first + block tile D - (H + e), reduced mod N)
+    uint32_t t0 = 0;
+    if constexpr (MIX) t0 = mix_tile_phase(p.mix.phase, p.first, blockIdx.x, kDecimTile * D, H + e, p.mix.period);
 #pragma unroll
     for (int i = 0; i < kLoads; i++) {
         const uint32_t l = (uint32_t)(kPerLoad * (tid + i * kThreadsDecim));
@@ -103,6 +111,14 @@ __global__ __launch_bounds__(kThreadsDecim) void k_decim(DecimParams p)
                 v[c] = (ii >= 0 && ii < (long long)p.n_in) ? widen_u8_pair(tab, b2) : 0u;
             } else {
                 v[c] = w[c];
+            }
+        }
+        if constexpr (MIX) {   // (in front of the call and behind its end the samples are zero, and stay zero)
+            uint32_t t = mix_mod(t0 + l, p.mix.period, p.mix.recip);
+#pragma unroll
+            for (int c = 0; c < kPerLoad; c++) {
+                v[c] = mix_sample(v[c], p.mix.table[t]);
+                if (++t == p.mix.period) t = 0;
             }
         }
         if (a0 + (long long)l < 0) {   // in front of the call: the history (the first tiles only)
@@ -159,8 +175,9 @@ __global__ __launch_bounds__(kThreadsDecim) void k_decim(DecimParams p)
 }
 
 // the last H inputs of the stream so far, widened: from the call's input, or from the previous history where the
-// call was shorter than the history (k_update_carry's rule)
-template <bool U8>
+// call was shorter than the history (k_update_carry's rule).  MIX: what comes from the call's input is mixed, what
+// comes from the previous history is mixed already.
+template <bool U8, bool MIX>
 __global__ __launch_bounds__(512) void k_decim_history(DecimParams p)
 {
     const long long H = (long long)p.n_taps - 1, i = threadIdx.x, n = (long long)p.n_in;
@@ -169,13 +186,25 @@ __global__ __launch_bounds__(512) void k_decim_history(DecimParams p)
     uint32_t v;
     if (idx < 0) {
         v = p.hist_prev[i + n];
-    } else if constexpr (U8) {
-        const uint8_t *s = (const uint8_t *)p.src;
-        v = widen_u8_pair(p.u8_table, (uint32_t)s[2 * idx] | (uint32_t)s[2 * idx + 1] << 8);
     } else {
-        v = ((const uint32_t *)p.src)[idx];
+        if constexpr (U8) {
+            const uint8_t *s = (const uint8_t *)p.src;
+            v = widen_u8_pair(p.u8_table, (uint32_t)s[2 * idx] | (uint32_t)s[2 * idx + 1] << 8);
+        } else {
+            v = ((const uint32_t *)p.src)[idx];
+        }
+        if constexpr (MIX) v = mix_sample(v, p.mix.table[((unsigned long long)idx + p.mix.phase) % p.mix.period]);
     }
     p.hist_next[i] = v;
+}
+
+// the mixer's table from the kernel's arguments: entry t = {c, s} -> {c, -s}, {s, c}
+__global__ __launch_bounds__(256) void k_mix_store(MixTable t, uint32_t period, uint2 *table)
+{
+    const uint32_t i = threadIdx.x;
+    if (i >= period) return;
+    const uint32_t cs = t.cs[i], c = cs & 0xFFFFu, s = cs >> 16;
+    table[i] = make_uint2(c | ((0u - s) << 16), s | (c << 16));
 }
 
 }  // namespace
@@ -191,22 +220,37 @@ int launch_decim(const DecimParams &p, void *stream)
         p.first >= p.factor || p.row_len != decim_row_len(p.factor, p.n_taps) ||
         p.recip != ((1u << 20) + p.factor - 1u) / p.factor || !p.src || !p.n_in || !p.hist_prev || !p.hist_next || !p.taps)
         return (int)hipErrorInvalidValue;
+    if (!mix_params_ok(p.mix)) return (int)hipErrorInvalidValue;
     // every output of the call has its input inside it
     if (p.n_out && (!p.out || (unsigned long long)p.first + (p.n_out - 1) * (unsigned long long)p.factor >= p.n_in))
         return (int)hipErrorInvalidValue;
     const unsigned long long blocks = (p.n_out + kDecimTile - 1) / kDecimTile;
     if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-    const bool u8 = p.u8_table != nullptr;
+    const bool u8 = p.u8_table != nullptr, mix = p.mix.period != 0;
     if (blocks) {
         const size_t lds_bytes = ((size_t)p.factor * p.row_len + (u8 ? 128u : 0u)) * 4u;
-        if (u8) hipLaunchKernelGGL(k_decim<true>, dim3((uint32_t)blocks), dim3(kThreadsDecim), lds_bytes, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(k_decim<false>, dim3((uint32_t)blocks), dim3(kThreadsDecim), lds_bytes, (hipStream_t)stream, p);
+        const auto kernel = u8 ? (mix ? k_decim<true, true> : k_decim<true, false>) : (mix ? k_decim<false, true> : k_decim<false, false>);
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kThreadsDecim), lds_bytes, (hipStream_t)stream, p);
         if (hipError_t e = hipGetLastError()) return (int)e;
     }
     if (p.n_taps > 1) {
-        if (u8) hipLaunchKernelGGL(k_decim_history<true>, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(k_decim_history<false>, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
+        const auto kernel = u8 ? (mix ? k_decim_history<true, true> : k_decim_history<true, false>)
+                               : (mix ? k_decim_history<false, true> : k_decim_history<false, false>);
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
     }
+    return (int)hipGetLastError();
+}
+
+bool mix_params_ok(const MixParams &m)
+{
+    if (m.period == 0) return true;
+    return m.period <= kMixMaxPeriod && m.table && m.phase < m.period && m.recip == (uint32_t)(((1ull << 32) + m.period - 1u) / m.period);
+}
+
+int launch_mix_store(const MixTable &t, uint32_t period, uint2 *d_table, void *stream)
+{
+    if (period < 1 || period > kMixMaxPeriod || !d_table) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mix_store, dim3(1), dim3(256), 0, (hipStream_t)stream, t, period, d_table);
     return (int)hipGetLastError();
 }
 

@@ -409,6 +409,19 @@ struct SigParams {
 };
 uint32_t signal_stats_wg_per_chunk(uint32_t n_chunks);
 int launch_signal_stats(const SigParams &p, SrcFormat fmt, void *stream);
+// Frequency shift (adsb_mix_*; adsb_mix_dev.h): the table a decimator or resampler mixes its input with on the way
+// in, as the MIX instantiations of its kernels read it.  k_mix_store (adsb_decim.hip) writes the table from its kernel
+// arguments: ordered on the stream, and the caller's table is copied when the launch returns.
+constexpr uint32_t kMixMaxPeriod = 256;
+struct MixParams {
+    const uint2 *table;         // device memory, [period]: .x = {c, -s}, .y = {s, c} as int16 pairs; null: no mixer
+    uint32_t period;            // N, 1 .. 256 (0: no mixer)
+    uint32_t phase;             // P mod N: the table entry of the call's first input
+    uint32_t recip;             // ceil(2^32 / N) (unused where N is 1)
+};
+struct MixTable { uint32_t cs[kMixMaxPeriod]; };   // {c, s} as int16 pairs, c in the low half
+bool mix_params_ok(const MixParams &m);
+int launch_mix_store(const MixTable &t, uint32_t period, uint2 *d_table, void *stream);
 // Decimation (adsb_decim_*; adsb_decim.hip: k_decim, k_decim_history): one call's inputs -> its outputs and the
 // history the next call starts from.  A kernel of its own in front of the scan, with parameters of its own.
 constexpr uint32_t kDecimTile = 256;        // outputs per workgroup
@@ -427,6 +440,7 @@ struct DecimParams {
     uint32_t first;             // input index of the call's first output: (-P) mod factor
     uint32_t row_len;           // decim_row_len(factor, n_taps): dwords per polyphase row in LDS
     uint32_t recip;             // ceil(2^20 / factor)
+    MixParams mix;              // the mixer (period 0: none)
 };
 uint32_t decim_row_len(uint32_t factor, uint32_t n_taps);
 int launch_decim(const DecimParams &p, void *stream);
@@ -451,6 +465,7 @@ struct ResampParams {
     uint32_t rows;              // R = resamp_rows(up, down): a workgroup takes up x R outputs
     uint32_t row_len;           // resamp_row_len(down, rows, k_taps): dwords per polyphase row in LDS
     uint32_t recip_up, recip_down;   // ceil(2^32 / L), ceil(2^32 / M) (unused where the divisor is 1)
+    MixParams mix;              // the mixer (period 0: none)
 };
 uint32_t resamp_rows(uint32_t up, uint32_t down);
 uint32_t resamp_row_len(uint32_t down, uint32_t rows, uint32_t k_taps);

@@ -5,7 +5,7 @@
 // the dump1090 raw format) can consume it.
 //
 //   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K]
-//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] <capture.iq | ->
+//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] <capture.iq | ->
 //
 // --decimate D (2..16): the input is sampled at D x 2.4 MS/s, in the format --format names, and goes through the
 // library's decimator with its default taps (adsb_decim_default_taps) in front of the demodulation: the output lines are
@@ -17,6 +17,10 @@
 // adsb_resamp_demod_iq.  A call takes the input of K output buffers, K rounded up to a multiple of L's odd part so that
 // the input of a call is a whole number of samples and every call ends on a buffer boundary of the resampled stream.
 // Not together with --decimate.
+//
+// --shift HZ (signed; only with --decimate or --resample): the radio was offset-tuned, and the spectrum is moved by HZ on
+// its way into the filter (include/adsb_hip.h, "Frequency shift": adsb_mix_for_shift, adsb_mix_table, adsb_mix_set_*).  A
+// radio tuned 2.4 MHz below 1090 MHz: --shift -2400000.  A shift whose table would be longer than 256 is a usage error.
 //
 // --stats turns the signal statistics on (adsb_set_signal_stats) and prints what a receiver's gain is tuned by to
 // STDERR, every SECONDS (default 1) over the buffers since the last line and once more, as the last line, over the
@@ -322,6 +326,9 @@ int main(int argc, char **argv)
     double stats_seconds = 1.0;
     int fix = ADSB_FIX_NONE, decimate = 0;
     unsigned res_up = 0, res_down = 0;
+    bool shifted = false;
+    long shift_hz = 0;
+    uint32_t mix_k = 0, mix_period = 0;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -340,6 +347,12 @@ int main(int argc, char **argv)
             if (std::sscanf(argv[++i], "%u/%u%c", &res_up, &res_down, &tail) != 2 ||
                 adsb_resamp_default_taps(res_up, res_down, nullptr, 0, &n_taps, nullptr) != ADSB_ERR_CAPACITY)
                 path = nullptr, i = argc;
+        }
+        else if (a == "--shift" && i + 1 < argc) {
+            char *end = nullptr;
+            shift_hz = std::strtol(argv[++i], &end, 10);
+            shifted = true;
+            if (end == argv[i] || *end != 0 || shift_hz < -2147483647L || shift_hz > 2147483647L) path = nullptr, i = argc;
         }
         else if (a == "--out-cap" && i + 1 < argc) out_cap = std::atoi(argv[++i]);  // frames the output array starts with (it grows)
         else if (a == "--stats") {
@@ -366,8 +379,12 @@ int main(int argc, char **argv)
         else if (a == "--help" || a == "-h") path = nullptr, i = argc;
         else path = argv[i];
     }
-    if (!path || buffers < 1 || (decimate && res_up)) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] <capture.iq | ->\n");
+    // --shift: only in front of a filter, and only where a table of 256 entries at most does it
+    const bool shift_ok = !shifted || ((decimate != 0) != (res_up != 0) &&
+                                       adsb_mix_for_shift(decimate ? 1u : res_up, decimate ? (uint32_t)decimate : res_down, (int32_t)shift_hz,
+                                                          &mix_k, &mix_period) == ADSB_OK);
+    if (!path || buffers < 1 || (decimate && res_up) || !shift_ok) {
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -465,6 +482,15 @@ int main(int argc, char **argv)
             if (out_cap <= 0) out.resize(k * 4096);
         }
         const auto destroy = [&] { adsb_decim_destroy(dec), adsb_resamp_destroy(res); };
+        if (shifted) {
+            int16_t table[2 * ADSB_MIX_MAX_PERIOD];
+            if ((st = adsb_mix_table(mix_k, mix_period, table, ADSB_MIX_MAX_PERIOD)) == ADSB_OK)
+                st = dec ? adsb_mix_set_decim(dec, table, mix_period) : adsb_mix_set_resamp(res, table, mix_period);
+            if (st != ADSB_OK) {
+                destroy();
+                return die(ctx, "adsb_mix_table / adsb_mix_set", st);
+            }
+        }
         std::vector<char> in_buf(call_samples * bps);
         const auto t0 = std::chrono::steady_clock::now();
         for (bool eof = false; !eof;) {

@@ -23,8 +23,15 @@ struct adsb_resamp {
     size_t in_bytes = 0;
     void *d_out = nullptr;
     size_t out_bytes = 0;
-    Registry mem;   // owns the five buffers above
+    Mixer mix;
+    Registry mem;   // owns the five buffers above and the mixer's table
 };
+
+namespace adsb {
+namespace host {
+MixerOwner mixer_of(adsb_resamp *r) { return {r->ctx, &r->mem, &r->mix}; }
+}  // namespace host
+}  // namespace adsb
 
 namespace {
 
@@ -85,6 +92,7 @@ int run_on_stream(adsb_resamp *r, int format, const void *d_in, uint64_t n_in, v
     p.row_len = resamp_row_len(M, p.rows, r->k_taps);
     p.recip_up = (uint32_t)(((1ull << 32) + L - 1u) / L);
     p.recip_down = (uint32_t)(((1ull << 32) + M - 1u) / M);
+    p.mix = mixer_params(r->mix, r->consumed);
     if (int e = launch_resamp(p, c->stream)) return fail(c, (hipError_t)e, "launch_resamp");
     // (the next pass reads what this put on the context's own stream: order_behind_input)
     if (c->stream == c->own_stream) c->own_stream_dirty = true;
@@ -235,6 +243,8 @@ try {
     r->consumed = 0;
     return ADSB_OK;
 } ADSB_ABI_CATCH
+
+uint32_t adsb_mix_get_resamp(const adsb_resamp *r) { return r ? r->mix.period : 0; }
 
 int adsb_resamp_out_count(const adsb_resamp *r, size_t n_in, size_t *n_out)
 {

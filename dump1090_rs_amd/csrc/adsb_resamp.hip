@@ -18,7 +18,9 @@
 //     needs) - 8, through a resource that spans [max(that, 0), n_in) of the call's input: the hardware range check returns
 //     zero for whatever lies in front of the call or past its end.  Inputs in front of the call come from the history
 //     buffer instead (the first K - 1 inputs of the first tiles); 8-bit input is widened as it is stored to LDS, through
-//     a copy of the context's table in LDS, and masked by position: a sample in front of the stream is zero, not T8[0].
+//     a copy of the context's table in LDS, and masked by position: a sample in front of the stream is zero, not T8[0];
+//   * MIX (include/adsb_hip.h, "Frequency shift"): as in k_decim, a sample of the call is mixed with its table entry
+//     between the widening and the store to LDS; the table comes through cached global loads (adsb_mix_dev.h), no LDS.
 // The host hands over the call's first output already reduced (p0, q0): the kernel works in offsets that fit 32 bits
 // beside one 64-bit tile base.  R (resamp_rows) depends on the ratio alone: the largest of 1024 .. 64 with L R <= 2048
 // whose LDS, counted with K = 512, leaves room for eight workgroups per CU (20 KB) and whose L R / 64 units divide evenly
@@ -27,6 +29,7 @@
 // is then partly idle: ratios with both terms near 128).  No scratch, no spills.
 #include "../../include/adsb_hip.h"
 #include "adsb_dev_common.h"
+#include "adsb_mix_dev.h"
 
 namespace adsb {
 
@@ -53,7 +56,7 @@ __device__ __forceinline__ int round_clamp_r(int acc, uint32_t shift, int round)
     return min(max((acc + round) >> shift, -32768), 32767);
 }
 
-template <bool U8>
+template <bool U8, bool MIX>
 __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
 {
     extern __shared__ uint32_t lds[];
@@ -82,6 +85,9 @@ __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
         tab[tid] = p.u8_table[tid];
         __syncthreads();
     }
+    // the table entry of local sample 0 (the tile's origin a0 = q0 + block R M - (H + e), reduced mod N)
+    uint32_t t0 = 0;
+    if constexpr (MIX) t0 = mix_tile_phase(p.mix.phase, p.q0, blockIdx.x, R * M, H + e, p.mix.period);
     for (uint32_t lb = 0; lb < ltot; lb += (uint32_t)(kBatch * kPerLoad * kThreadsResamp)) {
         u32x4r pre[kBatch];
 #pragma unroll
@@ -107,6 +113,14 @@ __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
                     v[c] = (ii >= 0 && ii < (long long)p.n_in) ? widen_u8_pair(tab, b2) : 0u;
                 } else {
                     v[c] = w[c];
+                }
+            }
+            if constexpr (MIX) {   // (in front of the call and behind its end the samples are zero, and stay zero)
+                uint32_t t = mix_mod(t0 + l, p.mix.period, p.mix.recip);
+#pragma unroll
+                for (int c = 0; c < kPerLoad; c++) {
+                    v[c] = mix_sample(v[c], p.mix.table[t]);
+                    if (++t == p.mix.period) t = 0;
                 }
             }
             if (a0 + (long long)l < 0) {   // in front of the call: the history (the first tiles only)
@@ -187,8 +201,9 @@ __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
 }
 
 // the last H = K - 1 inputs of the stream so far, widened: from the call's input, or from the previous history where
-// the call was shorter than the history (k_decim_history's rule)
-template <bool U8>
+// the call was shorter than the history (k_decim_history's rule).  MIX: what comes from the call's input is mixed, what
+// comes from the previous history is mixed already.
+template <bool U8, bool MIX>
 __global__ __launch_bounds__(512) void k_resamp_history(ResampParams p)
 {
     const long long H = (long long)p.k_taps - 1, i = threadIdx.x, n = (long long)p.n_in;
@@ -197,11 +212,14 @@ __global__ __launch_bounds__(512) void k_resamp_history(ResampParams p)
     uint32_t v;
     if (idx < 0) {
         v = p.hist_prev[i + n];
-    } else if constexpr (U8) {
-        const uint8_t *s = (const uint8_t *)p.src;
-        v = widen_u8_pair(p.u8_table, (uint32_t)s[2 * idx] | (uint32_t)s[2 * idx + 1] << 8);
     } else {
-        v = ((const uint32_t *)p.src)[idx];
+        if constexpr (U8) {
+            const uint8_t *s = (const uint8_t *)p.src;
+            v = widen_u8_pair(p.u8_table, (uint32_t)s[2 * idx] | (uint32_t)s[2 * idx + 1] << 8);
+        } else {
+            v = ((const uint32_t *)p.src)[idx];
+        }
+        if constexpr (MIX) v = mix_sample(v, p.mix.table[((unsigned long long)idx + p.mix.phase) % p.mix.period]);
     }
     p.hist_next[i] = v;
 }
@@ -244,6 +262,7 @@ int launch_resamp(const ResampParams &p, void *stream)
         p.recip_up != (uint32_t)(((1ull << 32) + p.up - 1u) / p.up) || p.recip_down != (uint32_t)(((1ull << 32) + p.down - 1u) / p.down) ||
         !p.src || !p.n_in || !p.hist_prev || !p.hist_next || !p.taps)
         return (int)hipErrorInvalidValue;
+    if (!mix_params_ok(p.mix)) return (int)hipErrorInvalidValue;
     const uint32_t lds_words = resamp_lds_words(p.up, p.down, p.rows, p.k_taps);
     if (lds_words > kResampLdsWords) return (int)hipErrorInvalidValue;
     // the call's first output has its newest input inside the call (then every tile's first output has)
@@ -253,16 +272,17 @@ int launch_resamp(const ResampParams &p, void *stream)
     if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     // ... and so has its last: floor((p0 + (n_out - 1) M) / L) + q0 < n_in  (n_out < 2^31 tiles of 2^13 at most: 64 bits do)
     if (p.n_out && ((p.n_out - 1) * p.down + p.p0) / p.up + p.q0 >= p.n_in) return (int)hipErrorInvalidValue;
-    const bool u8 = p.u8_table != nullptr;
+    const bool u8 = p.u8_table != nullptr, mix = p.mix.period != 0;
     if (blocks) {
         const size_t lds_bytes = (size_t)lds_words * 4u;
-        if (u8) hipLaunchKernelGGL(k_resamp<true>, dim3((uint32_t)blocks), dim3(kThreadsResamp), lds_bytes, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(k_resamp<false>, dim3((uint32_t)blocks), dim3(kThreadsResamp), lds_bytes, (hipStream_t)stream, p);
+        const auto kernel = u8 ? (mix ? k_resamp<true, true> : k_resamp<true, false>) : (mix ? k_resamp<false, true> : k_resamp<false, false>);
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kThreadsResamp), lds_bytes, (hipStream_t)stream, p);
         if (hipError_t e = hipGetLastError()) return (int)e;
     }
     if (p.k_taps > 1) {
-        if (u8) hipLaunchKernelGGL(k_resamp_history<true>, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(k_resamp_history<false>, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
+        const auto kernel = u8 ? (mix ? k_resamp_history<true, true> : k_resamp_history<true, false>)
+                               : (mix ? k_resamp_history<false, true> : k_resamp_history<false, false>);
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
     }
     return (int)hipGetLastError();
 }

@@ -686,6 +686,52 @@ ADSB_MUST_CHECK int adsb_resamp_plan(uint32_t up, uint32_t down, uint64_t consum
 /* Host only, for the tests: the outputs one workgroup of the resampling kernel takes at this ratio (0: not a ratio). */
 uint32_t adsb_resamp_selftest_tile(uint32_t up, uint32_t down);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Frequency shift -- offset-tuned IQ.  A HackRF, bladeRF, Airspy or USRP is a zero-IF receiver: its DC spike and LO
+ * leakage sit exactly on the tuned frequency, and the demodulator works on magnitudes.  Such a radio is therefore tuned a
+ * megahertz or two beside 1090 MHz at its higher rate and the signal is mixed back digitally; the decimating low-pass
+ * then removes the spike, which now lies beside the band.  A decimator or a resampler may carry a MIXER that does this on
+ * the device, on the samples' way into the filter: no kernel of its own, no second pass over the high-rate input.
+ *
+ * Definition.  A mixer is a table w[0..N-1] of int16 pairs (c, s), 1 <= N <= ADSB_MIX_MAX_PERIOD (256), every
+ * |c|, |s| <= 32767 (the value -32768 is ADSB_ERR_INVALID).  With a mixer set, the x[m] in the decimator's or resampler's
+ * definition is replaced by x'[m]; m is the sample's index in the stream counted from create or reset, the P the handle
+ * keeps:
+ *     t   = m mod N
+ *     re' = clamp((x.re * c[t] - x.im * s[t] + 8192) >> 14, -32768, 32767)
+ *     im' = clamp((x.re * s[t] + x.im * c[t] + 8192) >> 14, -32768, 32767)      >> arithmetic (a half rounds up)
+ * -- x[m] (c + i s) / 2^14.  Everything after it is unchanged: taps, shift, counts, and "the cut is invisible", which now
+ * covers the mixer's phase too.  x'[m] = 0 for m < 0.  8-bit input is widened through the context's table first, then
+ * mixed.  The history holds mixed samples, so the mixer may be set, changed or cleared between calls; the table is applied
+ * by absolute m, whatever was set before.  The int32 accumulator cannot wrap: 2 * 32768 * 32767 + 8192 < 2^31.  With
+ * amplitude 2^14 and the shift of 14 a table entry (16384, 0) is the identity, and the tables of N = 1, 2, 4 are exact
+ * rotations by 0, 180 and 90 degrees.
+ *
+ *   adsb_mix_set_decim   }  cs_pairs: `period` pairs {c, s}.  Ordered on the stream like *_reset: applies to the inputs
+ *   adsb_mix_set_resamp  }  consumed after the call.  The table is copied during the call.  NULL with period 0 turns the
+ *                             mixer off.  An invalid table is ADSB_ERR_INVALID and changes nothing.  Never ADSB_ERR_BUSY.
+ *   adsb_mix_get_decim   }  the period; 0 when the mixer is off
+ *   adsb_mix_get_resamp  }
+ *                          (All six calls carry the adsb_mix_ prefix: the adsb_decim_* and adsb_resamp_* families are
+ *                          what they were.)
+ *   adsb_mix_table         host only: the table of a shift by k / N cycles per sample, c[t] = lround(16384 cos(2 pi k t / N))
+ *                          and s likewise with sin.  Computed in double through libm: a property, not bits -- but whole
+ *                          quarter turns are exact, so the tables of N = 1, 2, 4 are.  `cap` (in pairs) below `period`:
+ *                          ADSB_ERR_CAPACITY.
+ *   adsb_mix_for_shift     host only: the table terms for a stream at 2.4 MS/s x down / up (a decimator is (1, D); both
+ *                          terms 1..128) whose spectrum is to be moved by shift_hz, signed: a radio tuned 2.4 MHz BELOW
+ *                          1090 MHz sees the signal 2.4 MHz above its centre and passes -2 400 000.
+ *                          k / N = shift_hz up / (2 400 000 down), reduced, k taken mod N into 0..N-1.  ADSB_ERR_INVALID
+ *                          (with the terms still written) where N > 256.
+ * Keep |shift_hz| well inside the stopband of the filter behind the mixer: the spike ends up |shift_hz| from the centre. */
+#define ADSB_MIX_MAX_PERIOD 256u
+ADSB_MUST_CHECK int adsb_mix_set_decim(adsb_decim *d, const int16_t *cs_pairs, uint32_t period);
+ADSB_MUST_CHECK int adsb_mix_set_resamp(adsb_resamp *r, const int16_t *cs_pairs, uint32_t period);
+extern uint32_t adsb_mix_get_decim(const adsb_decim *d);
+extern uint32_t adsb_mix_get_resamp(const adsb_resamp *r);
+ADSB_MUST_CHECK int adsb_mix_table(uint32_t k, uint32_t period, int16_t *cs_pairs, size_t cap);
+ADSB_MUST_CHECK int adsb_mix_for_shift(uint32_t up, uint32_t down, int32_t shift_hz, uint32_t *k, uint32_t *period);
+
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167
  * is one stream with one process-global filter, src/icao_filter.rs:8-9).  Shards run

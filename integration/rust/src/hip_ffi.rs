@@ -292,3 +292,14 @@ unsafe extern "C" {
     pub fn adsb_resamp_ratio_for_rate(rate_hz: u32, up: *mut u32, down: *mut u32) -> c_int;
     pub fn adsb_resamp_plan(up: u32, down: u32, consumed: u64, n_in: u64, first_n: *mut u64, n_out: *mut u64) -> c_int;
 }
+
+// The mixer of a decimator or resampler, for offset-tuned IQ (include/adsb_hip.h, "Frequency shift").
+#[link(name = "adsb_hip")]
+unsafe extern "C" {
+    pub fn adsb_mix_set_decim(d: *mut AdsbDecim, cs_pairs: *const i16, period: u32) -> c_int;
+    pub fn adsb_mix_set_resamp(r: *mut AdsbResamp, cs_pairs: *const i16, period: u32) -> c_int;
+    pub fn adsb_mix_get_decim(d: *const AdsbDecim) -> u32;
+    pub fn adsb_mix_get_resamp(r: *const AdsbResamp) -> u32;
+    pub fn adsb_mix_table(k: u32, period: u32, cs_pairs: *mut i16, cap: usize) -> c_int;
+    pub fn adsb_mix_for_shift(up: u32, down: u32, shift_hz: i32, k: *mut u32, period: *mut u32) -> c_int;
+}
