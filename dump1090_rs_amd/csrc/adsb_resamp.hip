@@ -25,8 +25,11 @@
 // beside one 64-bit tile base.  R (resamp_rows) depends on the ratio alone: the largest of 1024 .. 64 with L R <= 2048
 // whose LDS, counted with K = 512, leaves room for eight workgroups per CU (20 KB) and whose L R / 64 units divide evenly
 // among the four waves; failing that (a large M, whose inputs alone are more) the largest of 256, 128, 64 with
-// L R <= 2048 that fits 64 KB; else the largest of 64, 32, 16, 8 that does (a wave
-// is then partly idle: ratios with both terms near 128).  No scratch, no spills.
+// L R <= 2048 that fits 64 KB; else the largest of 64, 32, 16, 8 that does, L R unbounded.  Over the ratios
+// adsb_resamp_create accepts that third rule takes 5144 of 7223 (every L above 32) and only ever chooses 64 or 32 rows:
+// a tile is then 2112 .. 8192 outputs, up to 32 KB of staged outputs and eight passes of the final store loop, and at 32
+// rows (48 ratios, both terms near 128) half of every wave has no member.  Rows of 16 and 8 are listed and never chosen;
+// tests/test_resamp_cpu.py enumerates this.  No scratch, no spills.
 #include "../../include/adsb_hip.h"
 #include "adsb_dev_common.h"
 #include "adsb_mix_dev.h"

@@ -18,6 +18,34 @@ RADIO_RATES = {2_500_000: (24, 25), 10_000_000: (6, 25), 3_000_000: (4, 5), 6_00
 TABLE_RATIOS = sorted(set(RADIO_RATES.values()))   # ten, each once
 
 
+# tests/test_gpu_resamp_edges.py: the ratios whose tile geometry (resamp_rows) the radios' ratios do not reach
+EDGE_RATIOS = [(16, 15),                                # 128 rows with L a multiple of four
+               (2, 1),                                  # L = 2 M: every input feeds two outputs
+               (4, 3), (31, 128),                       # 512 rows with L = 4; 64 rows, a tile below 2048, uneven units
+               (5, 56), (7, 54),                        # the largest LDS requests (65 440 and 65 360 bytes at K = 512)
+               (33, 17), (33, 128), (48, 49),           # 64 rows, tiles of 2112 and 3072 outputs
+               (96, 95), (64, 127), (128, 65),          # 64 rows, tiles of 6144, 4096 and 8192
+               (128, 127), (127, 128), (117, 128)]      # 32 rows: half of every wave has no member
+# ... and the ratios tests/test_gpu_resamp.py and tests/test_gpu_mix.py launch on the device
+FIRST_FILES_RATIOS = [(1, 1), (1, 2), (1, 5), (1, 16), (2, 5), (3, 4), (3, 10), (3, 25), (4, 5), (6, 5), (6, 25), (15, 16),
+                      (24, 25), (24, 125)]
+MAX_RATIO = 128
+
+
+def accepted_ratios():
+    """Every (L, M) adsb_resamp_create accepts (include/adsb_hip.h): coprime, both 1..128, L <= 2 M, M <= 16 L."""
+    from math import gcd
+    return [(L, M) for L in range(1, MAX_RATIO + 1) for M in range(1, MAX_RATIO + 1)
+            if gcd(L, M) == 1 and L <= 2 * M and M <= 16 * L]
+
+
+def tile_class(L: int, tile: int):
+    """What decides the paths k_resamp takes at a ratio: the rows of a class (below 64: a wave is partly idle), whether
+    the staged tile is larger than 2048 outputs, and whether L is no multiple of four (at 64 rows and fewer the tile has
+    L units, which then do not divide evenly among the four waves)."""
+    return tile // L, tile > 2048, L % 4 != 0
+
+
 def ceil_div(a: int, b: int) -> int:
     return -(-a // b)
 
@@ -126,3 +154,55 @@ def hold_input(y, L: int, M: int, rng) -> np.ndarray:
     x = rng.integers(-32768, 32768, size=(int(q[-1]) + 1, 2), dtype=np.int64).astype(np.int16)
     x[q] = y
     return x
+
+
+def inputs_for(L: int, M: int, P: int, count: int) -> int:
+    """The fewest inputs behind P consumed ones that give at least `count` outputs: up to the newest input of the last."""
+    if count == 0:
+        return 0
+    last = ceil_div(P * L, M) + count - 1
+    return (last * M) // L - P + 1
+
+
+def window_inputs(first_output: int, count: int, T: int, L: int, M: int):
+    """[lo, hi): the inputs resample_window needs for outputs first_output .. first_output + count - 1."""
+    K = phase_taps(L, T)
+    return max((first_output * M) // L - (K - 1), 0), ((first_output + count - 1) * M) // L + 1
+
+
+def resample_window(x_window, first_output: int, count: int, h, L: int, M: int, s: int) -> np.ndarray:
+    """Outputs first_output .. first_output + count - 1 of a stream from a window of its inputs: x_window[0] is input
+    window_inputs(...)[0] of the stream and the window reaches the newest input of the last output."""
+    x = np.asarray(x_window, dtype=np.int64).reshape(-1, 2)
+    h = np.asarray(h, dtype=np.int64)
+    K = phase_taps(L, len(h))
+    lo, hi = window_inputs(first_output, count, len(h), L, M)
+    assert count == 0 or len(x) >= hi - lo
+    n = np.arange(first_output, first_output + count)
+    full = np.concatenate([np.zeros((K - 1, 2), np.int64), x])   # full[m - lo + K - 1] = x[m]
+    # (behind a window that starts inside the stream no output reaches the padding: lo is the oldest input of the first)
+    assert count == 0 or lo == 0 or (first_output * M) // L - (K - 1) == lo
+    return _outputs(n, full, K - 1 - lo, h, L, M, s)
+
+
+def tile_base(blk: int, q0: int, L: int, M: int, K: int, tile: int) -> int:
+    """The input index (0 = the call's first input) k_resamp's tile `blk` puts its buffer resource at: the 8-sample
+    boundary below (the first input the tile needs) - 8, or 0.  The first input the tile needs is its first output's
+    newest input, q0 + blk R M, less the K - 1 in front of it (R = tile / L; q0: the call's first output's newest input)."""
+    i0 = q0 + blk * (tile // L) * M - (K - 1)
+    return max((i0 - 8) & ~7, 0)
+
+
+def rail_window(x, h, L: int, M: int, n0: int, polarity: int):
+    """Puts the rail of each tap's sign (times the polarity) behind output n0 in x, on both components, and returns
+    (the accumulator these inputs give output n0, sum |h| of its phase).  Python integers."""
+    h = [int(v) for v in np.asarray(h)]
+    p, q = (n0 * M) % L, (n0 * M) // L
+    taps = h[p::L]
+    assert q >= len(taps) - 1
+    from tests.decim_support import rail_for
+    acc = 0
+    for j, hj in enumerate(taps):
+        x[q - j] = rail_for(hj, polarity)
+        acc += hj * int(x[q - j, 0])
+    return acc, sum(abs(v) for v in taps)

@@ -115,6 +115,119 @@ def test_selftest_tile(hip_lib):
         assert hip_lib.adsb_resamp_selftest_tile(L, M) == 0
 
 
+def test_every_tile_class_is_run_on_the_device(hip_lib):
+    """resamp_rows over every ratio adsb_resamp_create accepts: 32 to 1024 rows, never the 16 and 8 it lists, and every
+    class of (rows, tile above 2048 outputs, L no multiple of four) is met by a ratio the GPU files launch
+    (tests/test_gpu_resamp_edges.py: rs.EDGE_RATIOS; tests/test_gpu_resamp.py and tests/test_gpu_mix.py:
+    rs.FIRST_FILES_RATIOS).  A change of resamp_rows that opens another class fails here."""
+    def tile(L, M):
+        return int(hip_lib.adsb_resamp_selftest_tile(L, M))
+
+    ratios = rs.accepted_ratios()
+    assert len(ratios) == 7223 and set(rs.EDGE_RATIOS + rs.FIRST_FILES_RATIOS) <= set(ratios)
+    assert not set(rs.EDGE_RATIOS) & set(rs.FIRST_FILES_RATIOS)
+    classes = {}
+    for L, M in ratios:
+        t = tile(L, M)
+        assert t > 0 and t % L == 0 and t % 4 == 0 and t <= 8192, (L, M, t)
+        assert t // L in (32, 64, 128, 256, 512, 1024), (L, M, t)
+        classes.setdefault(rs.tile_class(L, t), []).append((L, M))
+    assert max(rows for rows, _, _ in classes) == 1024 and min(rows for rows, _, _ in classes) == 32
+    assert sum(len(v) for k, v in classes.items() if k[1]) == 5144   # tiles above 2048 outputs: 71 % of the ratios
+    run_on_the_gpu = {rs.tile_class(L, tile(L, M)) for L, M in rs.EDGE_RATIOS + rs.FIRST_FILES_RATIOS}
+    assert run_on_the_gpu == set(classes), sorted(set(classes) - run_on_the_gpu)
+    # the first files alone leave out every tile above 2048 outputs (four classes) and three more
+    first = {rs.tile_class(L, tile(L, M)) for L, M in rs.FIRST_FILES_RATIOS}
+    assert not any(big for _, big, _ in first) and len(set(classes) - first) == 7
+    # the ratios of three ordinary rates lie in the classes the first files leave out
+    from dump1090_rs_amd import ratio_for_rate
+    assert [ratio_for_rate(hz) for hz in (2_450_000, 2_375_000, 2_304_000)] == [(48, 49), (96, 95), (25, 24)]
+    assert [tile(L, M) for L, M in [(48, 49), (96, 95), (25, 24)]] == [3072, 6144, 1600]
+    assert rs.tile_class(25, 1600) == rs.tile_class(31, 31 * 64) and rs.tile_class(25, 1600) not in first
+    # the tiles the edge file's docstrings name
+    tiles = {r: tile(*r) for r in rs.EDGE_RATIOS}
+    assert [tiles[r] for r in [(33, 17), (33, 128), (48, 49), (96, 95), (64, 127), (128, 65)]] == [2112, 2112, 3072, 6144, 4096, 8192]
+    rows = [tiles[r] // r[0] for r in [(128, 127), (127, 128), (117, 128), (16, 15), (2, 1), (4, 3), (31, 128)]]
+    assert rows == [32, 32, 32, 128, 1024, 512, 64]
+
+
+def lds_bytes(L, M, rows, K):
+    """resamp_lds_words restated from DESIGN.md ("LDS layout"): the polyphase store in rows of an odd length, rounded up
+    to 16 bytes, the staged outputs, the 8-bit table."""
+    row_len = ((rows * M + K + 15 + M - 1) // M) | 1
+    return 4 * (((M * row_len + 3) & ~3) + L * rows + 128)
+
+
+def test_the_largest_lds_requests_are_among_the_edge_ratios(hip_lib):
+    def at_k_512(L, M):
+        return lds_bytes(L, M, int(hip_lib.adsb_resamp_selftest_tile(L, M)) // L, 512)
+
+    # (K = 512 needs 512 L <= 4096 taps)
+    sizes = sorted(((at_k_512(L, M), (L, M)) for L, M in rs.accepted_ratios() if 512 * L <= 4096), reverse=True)
+    assert sizes[0] == (65440, (5, 56)) and (65360, (7, 54)) in sizes[:3] and sizes[0][0] <= 65536
+    assert {(5, 56), (7, 54)} <= set(rs.EDGE_RATIOS)
+    assert max(at_k_512(L, M) for L, M in rs.FIRST_FILES_RATIOS) < 41 * 1024
+
+
+@pytest.mark.parametrize("L, M, T, s", [(3, 25, 201, 14), (6, 5, 49, 14), (33, 17, 4096, 16), (2, 1, 3, 0), (127, 128, 1, 0)])
+def test_restatement_by_windows_is_a_slice_of_the_whole(L, M, T, s):
+    rng = np.random.default_rng(300 + L)
+    h = rs.random_phase_taps(rng, T, L)
+    K = rs.phase_taps(L, T)
+    x = rs.random_iq(rng, 4000, run=K)
+    want = rs.resample(x, h, L, M, s)
+    assert len(want) >= 480
+    for first, count in [(0, 1), (0, 50), (1, 7), (K * L // M + 3, 100), (len(want) // 2, 233), (len(want) - 9, 9), (5, 0)]:
+        lo, hi = rs.window_inputs(first, count, T, L, M)
+        assert 0 <= lo < hi <= len(x) or count == 0
+        if count:
+            # the window is exactly what these outputs read: the oldest input of the first, the newest of the last
+            assert lo == max((first * M) // L - (K - 1), 0) and hi - 1 == ((first + count - 1) * M) // L
+        got = rs.resample_window(x[lo:hi], first, count, h, L, M, s)
+        assert np.array_equal(got, want[first:first + count]), (first, count)
+        # ... and no more: with a sample less the window is refused
+        if count:
+            with pytest.raises(AssertionError):
+                rs.resample_window(x[lo:hi - 1], first, count, h, L, M, s)
+
+
+def test_tile_base_is_the_boundary_below_the_first_input_needed():
+    for L, M, K, t, q0 in [(3, 25, 67, 768, 0), (3, 25, 67, 768, 7), (128, 127, 9, 4096, 0), (5, 56, 512, 1280, 3), (1, 1, 1, 1024, 0)]:
+        for blk in (0, 1, 2, 3, 1000, 41_000):
+            need = q0 + blk * (t // L) * M - (K - 1)   # the oldest input of the tile's first output
+            assert need == q0 + ((blk * t) * M) // L - (K - 1)
+            b = rs.tile_base(blk, q0, L, M, K, t)
+            assert b % 8 == 0 and (b == 0 or 8 <= need - b <= 15) and (b > 0 or need < 16)
+
+
+@pytest.mark.parametrize("L, M, K", [(33, 17, 125), (128, 65, 32), (6, 5, 512)])
+def test_rails_behind_an_output_reach_the_bound(L, M, K):
+    """rs.rail_window: the accumulator it returns is the one the restatement computes, and it lies where the taps' weight
+    and the rails put it."""
+    rng = np.random.default_rng(400 + L)
+    h = rs.random_phase_taps(rng, rs.max_taps(L), L)
+    assert rs.phase_taps(L, len(h)) == K
+    for n0 in (K * L, 2111, 2113):
+        for pol in (1, -1):
+            x = rs.random_iq(rng, (n0 * M) // L + 5, run=0)
+            acc, weight = rs.rail_window(x, h, L, M, n0, pol)
+            assert weight == 65534 and acc * pol > 0 and 65534 * 32767 <= abs(acc) <= 65534 * 32768 < 2 ** 31 - 32768
+            assert x[(n0 * M) // L].tolist() in ([32767, 32767], [-32768, -32768])
+            for s in (0, 16):
+                r = (1 << (s - 1)) if s else 0
+                assert rs.resample(x, h, L, M, s)[n0].tolist() == [min(max((acc + r) >> s, -32768), 32767)] * 2
+
+
+def test_the_stretched_stream_shares_the_boundaries_the_edge_file_says():
+    """(b M) mod L >= M exactly for b = 1 mod 96 at 96/95, and 131 072 = 32 mod 96: behind P = 64 a blocking call's first
+    output is 65 and its buffer boundaries 1 and 4 of every three fall between two outputs that share their newest input."""
+    L, M, P = 96, 95, 64
+    assert rs.out_range(L, M, P, 1)[0] == 65 and rs.CHUNK % L == 32
+    for b in range(1, 4 * L):
+        assert (((b - 1) * M) // L == (b * M) // L) == ((b * M) % L >= M) == (b % L == 1)
+    assert [k for k in range(1, 8) if (65 + k * rs.CHUNK) % L == 1] == [1, 4, 7]
+
+
 def plan(hip_lib, L, M, P, n_in):
     first, n = C.c_uint64(), C.c_uint64()
     st = hip_lib.adsb_resamp_plan(L, M, P, n_in, C.byref(first), C.byref(n))
