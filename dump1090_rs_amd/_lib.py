@@ -24,6 +24,7 @@ ADSB_SCORE_FIXED_2BIT = 1100
 ADSB_FAULT_PHASE1, ADSB_FAULT_PHASE2, ADSB_FAULT_HANG, ADSB_FAULT_RECORDS = 1, 2, 3, 4
 ADSB_MAX_RECEIVERS = 16384
 ADSB_DECIM_CS16, ADSB_DECIM_8BIT = 0, 1
+ADSB_DECIM_CF32, ADSB_DECIM_REAL16 = 2, 3
 
 
 class AdsbMsg(C.Structure):
@@ -335,6 +336,13 @@ def lib() -> C.CDLL:
         getattr(L, name).restype = u32
     for name in ("adsb_mix_set_decim", "adsb_mix_set_resamp", "adsb_mix_table", "adsb_mix_for_shift"):
         getattr(L, name).restype = C.c_int
+    # sample formats (include/adsb_hip.h)
+    for name in ("adsb_fmt_set_scale_decim", "adsb_fmt_set_scale_resamp"):
+        getattr(L, name).argtypes = [vp, C.c_float]
+        getattr(L, name).restype = C.c_int
+    for name in ("adsb_fmt_get_scale_decim", "adsb_fmt_get_scale_resamp"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = C.c_float
     L.adsb_host_replays.argtypes = [vp]
     L.adsb_host_replays.restype = C.c_uint64
     L.adsb_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]

@@ -86,6 +86,52 @@ def _as_cu8(iq) -> np.ndarray:
     return a
 
 
+def _as_cf32(iq) -> np.ndarray:
+    """CF32 input: a 1-D complex64 array, (N, 2) float32 rows of [re, im] or flat interleaved float32."""
+    a = np.asarray(iq)
+    if a.dtype == np.complex64:
+        if a.ndim != 1:
+            raise ValueError("complex64 IQ must be 1-D")
+        return np.ascontiguousarray(a).view(np.float32).reshape(-1, 2)
+    if a.dtype != np.float32:
+        raise TypeError("CF32 IQ must be a float32 or complex64 array")
+    a = np.ascontiguousarray(a)
+    if a.ndim == 1:
+        if a.size % 2:
+            raise ValueError("interleaved CF32 IQ needs an even number of float32")
+        a = a.reshape(-1, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("CF32 IQ must be (N, 2) float32 rows of [re, im]")
+    return a
+
+
+def _as_real16(samples) -> np.ndarray:
+    """REAL16 input: a 1-D int16 array, one real sample each."""
+    a = np.asarray(samples)
+    if a.dtype != np.int16:
+        raise TypeError("real samples must be an int16 array")
+    if a.ndim != 1:
+        raise ValueError("real samples must be 1-D: one int16 per sample")
+    return np.ascontiguousarray(a)
+
+
+def _as_format(iq, format: int) -> np.ndarray:
+    """The host array of a decimator's or resampler's input in `format`; shape[0] is its sample count."""
+    if format == _lib.ADSB_DECIM_CS16:
+        return _as_iq(iq)
+    if format == _lib.ADSB_DECIM_8BIT:
+        return _as_cu8(iq)
+    if format == _lib.ADSB_DECIM_CF32:
+        return _as_cf32(iq)
+    if format == _lib.ADSB_DECIM_REAL16:
+        return _as_real16(iq)
+    raise ValueError(f"no such sample format: {format}")
+
+
+def _set_scale(handle, call, what: str, scale) -> None:
+    handle._check(call(handle._h, C.c_float(float(scale))), what)
+
+
 # adsb_trial as a numpy record (32 bytes)
 TRIAL_DTYPE = np.dtype([("power", "<u8"), ("chunk", "<u4"), ("j_tp", "<u4"), ("msg", "u1", (14,)), ("pad", "<u2")])
 
@@ -352,6 +398,15 @@ class Context:
         r = Resampler(self, up, down, taps, shift)
         if shift_hz is not None:
             r.set_mixer(mixer_table(*mixer_for_shift(up, down, shift_hz)))
+        return r
+
+    def converter(self, scale: Optional[float] = None) -> "Resampler":
+        """The 1/1 resampler with the single tap 1 and shift 0 -- the identity on CS16 -- for CF32 (or REAL16, 8-bit)
+        input that is already at 2.4 MS/s (include/adsb_hip.h, "Sample formats"): converter().demod_iq(x,
+        format=ADSB_DECIM_CF32) is demod_iq on q(x).  scale: g of q, 32768 by default."""
+        r = Resampler(self, 1, 1, np.array([1], dtype=np.int16), 0)
+        if scale is not None:
+            r.set_scale(scale)
         return r
 
     def collect_raw(self, out_buf, cap: int) -> int:
@@ -723,6 +778,14 @@ class Decimator:
     def mixer_period(self) -> int:
         return int(self._L.adsb_mix_get_decim(self._h))
 
+    def set_scale(self, scale: float) -> None:
+        """adsb_fmt_set_scale_decim: g of CF32 input, q(x) = clamp(rint(x g)); finite, 0 < g <= 2^31 (32768 by default)."""
+        _set_scale(self, self._L.adsb_fmt_set_scale_decim, "adsb_fmt_set_scale_decim", scale)
+
+    @property
+    def scale(self) -> float:
+        return float(self._L.adsb_fmt_get_scale_decim(self._h))
+
     def out_count(self, n_in: int) -> int:
         n = C.c_size_t()
         self._check(self._L.adsb_decim_out_count(self._h, int(n_in), C.byref(n)), "adsb_decim_out_count")
@@ -742,8 +805,9 @@ class Decimator:
         return n.value
 
     def demod_iq(self, iq, format: int = _lib.ADSB_DECIM_CS16, cap: Optional[int] = None) -> List[ModeSMessage]:
-        """Host IQ at factor x 2.4 MS/s of any length -> the messages of the decimated stream (blocking)."""
-        a = _as_cu8(iq) if format == _lib.ADSB_DECIM_8BIT else _as_iq(iq)
+        """Host samples at factor x 2.4 MS/s of any length, in `format` (CS16, 8-bit, CF32: float32 or complex64, REAL16:
+        1-D int16) -> the messages of the decimated stream (blocking)."""
+        a = _as_format(iq, format)
         cap = cap or max(4096, a.shape[0] // (256 * self.factor))
         ptr = a.ctypes.data
         return self._ctx._collect(
@@ -831,6 +895,14 @@ class Resampler:
     def mixer_period(self) -> int:
         return int(self._L.adsb_mix_get_resamp(self._h))
 
+    def set_scale(self, scale: float) -> None:
+        """adsb_fmt_set_scale_resamp: g of CF32 input, q(x) = clamp(rint(x g)); finite, 0 < g <= 2^31 (32768 by default)."""
+        _set_scale(self, self._L.adsb_fmt_set_scale_resamp, "adsb_fmt_set_scale_resamp", scale)
+
+    @property
+    def scale(self) -> float:
+        return float(self._L.adsb_fmt_get_scale_resamp(self._h))
+
     def out_count(self, n_in: int) -> int:
         n = C.c_size_t()
         self._check(self._L.adsb_resamp_out_count(self._h, int(n_in), C.byref(n)), "adsb_resamp_out_count")
@@ -850,8 +922,9 @@ class Resampler:
         return n.value
 
     def demod_iq(self, iq, format: int = _lib.ADSB_DECIM_CS16, cap: Optional[int] = None) -> List[ModeSMessage]:
-        """Host IQ at 2.4 MS/s x down / up of any length -> the messages of the resampled stream (blocking)."""
-        a = _as_cu8(iq) if format == _lib.ADSB_DECIM_8BIT else _as_iq(iq)
+        """Host samples at 2.4 MS/s x down / up of any length, in `format` (CS16, 8-bit, CF32: float32 or complex64,
+        REAL16: 1-D int16) -> the messages of the resampled stream (blocking)."""
+        a = _as_format(iq, format)
         cap = cap or max(4096, a.shape[0] * self.up // (256 * self.down))
         ptr = a.ctypes.data
         return self._ctx._collect(

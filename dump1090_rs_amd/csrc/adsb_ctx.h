@@ -557,6 +557,11 @@ inline MixParams mixer_params(const Mixer &m, uint64_t consumed)
     p.recip = (uint32_t)(((1ull << 32) + m.period - 1u) / m.period);
     return p;
 }
+// A decimator's or resampler's CF32 scale (include/adsb_hip.h, "Sample formats"; adsb_fmt.cpp): host state, handed to
+// every launch in its parameters.  scale_of is how adsb_fmt.cpp reaches a handle's (each handle's unit defines its own).
+float *scale_of(adsb_decim *d);
+float *scale_of(adsb_resamp *r);
+inline bool format_ok(int format) { return format >= 0 && format < (int)kInFormats; }
 // T_soapy: the table SoapyRTLSDR widens an RTL-SDR's bytes with, (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f)
 void soapy_u8_table(int16_t *out256);
 // IQ staging for host-pointer calls, in device memory / pinned and mapped, grown on demand (adsb_context.cpp)

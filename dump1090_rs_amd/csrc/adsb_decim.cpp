@@ -24,12 +24,14 @@ struct adsb_decim {
     void *d_out = nullptr;
     size_t out_bytes = 0;
     Mixer mix;
+    float scale = kInDefaultScale;   // CF32: g of q(x) (adsb_fmt.cpp)
     Registry mem;   // owns the five buffers above and the mixer's table
 };
 
 namespace adsb {
 namespace host {
 MixerOwner mixer_of(adsb_decim *d) { return {d->ctx, &d->mem, &d->mix}; }
+float *scale_of(adsb_decim *d) { return &d->scale; }
 }  // namespace host
 }  // namespace adsb
 
@@ -47,8 +49,6 @@ inline uint32_t first_output_at(const adsb_decim *d)
     return (uint32_t)((d->factor - d->consumed % d->factor) % d->factor);
 }
 
-inline bool format_ok(int format) { return format == ADSB_DECIM_CS16 || format == ADSB_DECIM_8BIT; }
-
 // One call on the context's input stream: the kernels, the history's turn and P.  No wait.
 int run_on_stream(adsb_decim *d, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t n_out)
 {
@@ -61,6 +61,8 @@ int run_on_stream(adsb_decim *d, int format, const void *d_in, uint64_t n_in, vo
     p.hist_next = d->d_hist[d->cur ^ 1];
     p.taps = d->d_taps;
     p.u8_table = format == ADSB_DECIM_8BIT ? c->d_u8_table : nullptr;
+    p.format = (uint32_t)format;
+    p.scale = d->scale;
     p.out = static_cast<uint32_t *>(d_out);
     p.n_out = n_out;
     p.factor = d->factor, p.n_taps = d->n_taps, p.shift = d->shift;
@@ -91,7 +93,7 @@ int demod_host(adsb_decim *d, int format, const void *host_iq, size_t n_in, adsb
     adsb_ctx *c = d->ctx;
     ADSB_ON_DEVICE(c);
     if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
-    const size_t bps = format == ADSB_DECIM_8BIT ? 2 : 4;
+    const size_t bps = in_bytes_per_sample((uint32_t)format);
     const char *in = static_cast<const char *>(host_iq);
     const uint64_t D = d->factor, total_out = out_count(d, n_in);
     // pieces of whole output buffers, at most what one pass of a small call takes
@@ -187,6 +189,7 @@ try {
 } ADSB_ABI_CATCH
 
 uint32_t adsb_mix_get_decim(const adsb_decim *d) { return d ? d->mix.period : 0; }
+float adsb_fmt_get_scale_decim(const adsb_decim *d) { return d ? d->scale : 0.0f; }
 
 int adsb_decim_out_count(const adsb_decim *d, size_t n_in, size_t *n_out)
 {

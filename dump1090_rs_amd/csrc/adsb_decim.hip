@@ -3,7 +3,7 @@
 //
 //   y[n] = clamp((sum_k h[k] x[nD - k] + r) >> s), re and im separately, every step an exact integer.
 //
-// A memory-bound pass: (4 or 2) D bytes read and 4 written per output.  A workgroup of 256 lanes takes a tile of
+// A memory-bound pass: (8, 4 or 2) D bytes read and 4 written per output.  A workgroup of 256 lanes takes a tile of
 // kDecimTile = 256 outputs:
 //   * it needs the tile D + T - 1 inputs from `i0` on; they are fetched with back-to-back 16-byte buffer loads
 //     from the 32-byte boundary below i0 - 8, through a resource that spans [max(that, 0), n_in) of the call's input:
@@ -19,6 +19,11 @@
 //   * re and im stay packed in their dword: one v_dot2_i32_i16 per half, against {h, 0} and {0, h};
 //   * CU8 input is widened as it is stored to LDS, through a copy of the context's table in LDS, and masked by
 //     position: a sample in front of the stream is zero, not T[0];
+//   * FMT (include/adsb_hip.h, "Sample formats"; adsb_fmt_dev.h): the format fixes the bytes of a sample -- hence the
+//     samples of a 16-byte load: 4 for CS16, 8 for 8-bit, 2 for CF32, 8 for REAL16 -- and the conversion to CS16 between
+//     the load and the mixer: CF32 is q(x) = clamp(rint(x g)) per component, no table and nothing to mask (out of range
+//     the load gives +0.0, and q(0) = 0); REAL16 is the halfword in the low half of the dword, masked by position as
+//     8-bit is -- the load of an odd number of samples is rounded up to a dword;
 //   * MIX (include/adsb_hip.h, "Frequency shift"): a sample is mixed with its table entry between the widening and the
 //     store to LDS -- the samples of the call, not the history's, which holds mixed ones.  The workgroup reduces its
 //     tile's origin mod N once, a load its first sample's phase by a multiplication, and the phase then steps with a wrap
@@ -28,6 +33,7 @@
 // fit a CU's LDS in every case.
 #include "../../include/adsb_hip.h"
 #include "adsb_dev_common.h"
+#include "adsb_fmt_dev.h"
 #include "adsb_mix_dev.h"
 
 namespace adsb {
@@ -57,13 +63,15 @@ __device__ __forceinline__ int round_clamp(int acc, uint32_t shift, int round)
     return min(max((acc + round) >> shift, -32768), 32767);
 }
 
-template <bool U8, bool MIX>
+template <uint32_t FMT, bool MIX>
 __global__ __launch_bounds__(kThreadsDecim) void k_decim(DecimParams p)
 {
     extern __shared__ uint32_t lds[];
-    constexpr int kPerLoad = U8 ? 8 : 4;                                                   // samples per 16-byte load
-    constexpr int kLoads = (kDecimMaxLocal + kPerLoad * kThreadsDecim - 1) / (kPerLoad * kThreadsDecim);   // 5 / 3
-    constexpr int kBps = U8 ? 2 : 4;
+    constexpr bool U8 = FMT == kIn8Bit;
+    constexpr int kBps = (int)in_bytes_per_sample(FMT);
+    constexpr int kPerLoad = 16 / kBps;                                                    // samples per 16-byte load
+    // loads per lane: CS16 5, 8-bit and REAL16 3, CF32 10
+    constexpr int kLoads = (kDecimMaxLocal + kPerLoad * kThreadsDecim - 1) / (kPerLoad * kThreadsDecim);
     const int tid = threadIdx.x;
     const uint32_t D = p.factor, H = p.n_taps - 1, RL = p.row_len, M = p.recip;
     // input index (0 = the call's first sample) of the first input the tile needs, the origin of its local samples,
@@ -109,6 +117,10 @@ __global__ __launch_bounds__(kThreadsDecim) void k_decim(DecimParams p)
             if constexpr (U8) {
                 const uint32_t b2 = (w[c >> 1] >> (16 * (c & 1))) & 0xFFFFu;
                 v[c] = (ii >= 0 && ii < (long long)p.n_in) ? widen_u8_pair(tab, b2) : 0u;
+            } else if constexpr (FMT == kInReal16) {   // (the load is rounded up to a dword: the int16 behind an odd end)
+                v[c] = (ii >= 0 && ii < (long long)p.n_in) ? fmt_halfword(w, c) : 0u;
+            } else if constexpr (FMT == kInCf32) {     // (out of range the load gave +0.0, and q(0) = 0)
+                v[c] = fmt_cf32(w[2 * c], w[2 * c + 1], p.scale);
             } else {
                 v[c] = w[c];
             }
@@ -177,9 +189,10 @@ __global__ __launch_bounds__(kThreadsDecim) void k_decim(DecimParams p)
 // the last H inputs of the stream so far, widened: from the call's input, or from the previous history where the
 // call was shorter than the history (k_update_carry's rule).  MIX: what comes from the call's input is mixed, what
 // comes from the previous history is mixed already.
-template <bool U8, bool MIX>
+template <uint32_t FMT, bool MIX>
 __global__ __launch_bounds__(512) void k_decim_history(DecimParams p)
 {
+    constexpr bool U8 = FMT == kIn8Bit;
     const long long H = (long long)p.n_taps - 1, i = threadIdx.x, n = (long long)p.n_in;
     if (i >= H) return;
     const long long idx = n - H + i;
@@ -190,6 +203,11 @@ __global__ __launch_bounds__(512) void k_decim_history(DecimParams p)
         if constexpr (U8) {
             const uint8_t *s = (const uint8_t *)p.src;
             v = widen_u8_pair(p.u8_table, (uint32_t)s[2 * idx] | (uint32_t)s[2 * idx + 1] << 8);
+        } else if constexpr (FMT == kInReal16) {
+            v = ((const uint16_t *)p.src)[idx];
+        } else if constexpr (FMT == kInCf32) {
+            const uint2 f = ((const uint2 *)p.src)[idx];
+            v = fmt_cf32(f.x, f.y, p.scale);
         } else {
             v = ((const uint32_t *)p.src)[idx];
         }
@@ -220,25 +238,37 @@ int launch_decim(const DecimParams &p, void *stream)
         p.first >= p.factor || p.row_len != decim_row_len(p.factor, p.n_taps) ||
         p.recip != ((1u << 20) + p.factor - 1u) / p.factor || !p.src || !p.n_in || !p.hist_prev || !p.hist_next || !p.taps)
         return (int)hipErrorInvalidValue;
+    if (!in_format_ok(p.format, p.u8_table, p.scale)) return (int)hipErrorInvalidValue;
     if (!mix_params_ok(p.mix)) return (int)hipErrorInvalidValue;
     // every output of the call has its input inside it
     if (p.n_out && (!p.out || (unsigned long long)p.first + (p.n_out - 1) * (unsigned long long)p.factor >= p.n_in))
         return (int)hipErrorInvalidValue;
     const unsigned long long blocks = (p.n_out + kDecimTile - 1) / kDecimTile;
     if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-    const bool u8 = p.u8_table != nullptr, mix = p.mix.period != 0;
+    const bool u8 = p.format == kIn8Bit, mix = p.mix.period != 0;
     if (blocks) {
         const size_t lds_bytes = ((size_t)p.factor * p.row_len + (u8 ? 128u : 0u)) * 4u;
-        const auto kernel = u8 ? (mix ? k_decim<true, true> : k_decim<true, false>) : (mix ? k_decim<false, true> : k_decim<false, false>);
+        const auto kernel = p.format == kInCf32    ? (mix ? k_decim<kInCf32, true> : k_decim<kInCf32, false>)
+                            : p.format == kInReal16 ? (mix ? k_decim<kInReal16, true> : k_decim<kInReal16, false>)
+                            : u8                    ? (mix ? k_decim<kIn8Bit, true> : k_decim<kIn8Bit, false>)
+                                                    : (mix ? k_decim<kInCs16, true> : k_decim<kInCs16, false>);
         hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kThreadsDecim), lds_bytes, (hipStream_t)stream, p);
         if (hipError_t e = hipGetLastError()) return (int)e;
     }
     if (p.n_taps > 1) {
-        const auto kernel = u8 ? (mix ? k_decim_history<true, true> : k_decim_history<true, false>)
-                               : (mix ? k_decim_history<false, true> : k_decim_history<false, false>);
+        const auto kernel = p.format == kInCf32    ? (mix ? k_decim_history<kInCf32, true> : k_decim_history<kInCf32, false>)
+                            : p.format == kInReal16 ? (mix ? k_decim_history<kInReal16, true> : k_decim_history<kInReal16, false>)
+                            : u8                    ? (mix ? k_decim_history<kIn8Bit, true> : k_decim_history<kIn8Bit, false>)
+                                                    : (mix ? k_decim_history<kInCs16, true> : k_decim_history<kInCs16, false>);
         hipLaunchKernelGGL(kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
     }
     return (int)hipGetLastError();
+}
+
+bool in_format_ok(uint32_t format, const uint16_t *u8_table, float scale)
+{
+    if (format >= kInFormats || (format == kIn8Bit) != (u8_table != nullptr)) return false;
+    return format != kInCf32 || (scale > 0.0f && scale <= kInMaxScale);   // (a NaN fails both)
 }
 
 bool mix_params_ok(const MixParams &m)

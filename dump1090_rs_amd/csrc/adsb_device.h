@@ -422,13 +422,21 @@ struct MixParams {
 struct MixTable { uint32_t cs[kMixMaxPeriod]; };   // {c, s} as int16 pairs, c in the low half
 bool mix_params_ok(const MixParams &m);
 int launch_mix_store(const MixTable &t, uint32_t period, uint2 *d_table, void *stream);
+// Sample formats (adsb_fmt_*; include/adsb_hip.h, "Sample formats"): what a decimator's or resampler's `src` holds, the
+// values of ADSB_DECIM_CS16, _8BIT, _CF32 and _REAL16.  Each is its own instantiation of the four kernels; the format
+// fixes the bytes of a sample -- hence the samples of a 16-byte load -- and the conversion to CS16 in front of the mixer.
+enum InFormat : uint32_t { kInCs16 = 0, kIn8Bit = 1, kInCf32 = 2, kInReal16 = 3, kInFormats = 4 };
+__host__ __device__ constexpr uint32_t in_bytes_per_sample(uint32_t f) { return f == kInCf32 ? 8u : f == kInCs16 ? 4u : 2u; }
+constexpr float kInDefaultScale = 32768.0f, kInMaxScale = 2147483648.0f;   // CF32: 0 < g <= 2^31
+// what a launch checks: a format there is, the 8-bit table exactly where the format reads it, CF32's scale in range
+bool in_format_ok(uint32_t format, const uint16_t *u8_table, float scale);
 // Decimation (adsb_decim_*; adsb_decim.hip: k_decim, k_decim_history): one call's inputs -> its outputs and the
 // history the next call starts from.  A kernel of its own in front of the scan, with parameters of its own.
 constexpr uint32_t kDecimTile = 256;        // outputs per workgroup
 constexpr uint32_t kDecimMinFactor = 2, kDecimMaxFactor = 16, kDecimMaxTaps = 512, kDecimMaxShift = 16;
 constexpr uint32_t kDecimHistWords = 512;   // a history buffer: the last n_taps - 1 inputs, widened, at [0, n_taps - 1)
 struct DecimParams {
-    const void *src;            // the call's inputs: CS16 dwords or byte pairs, 16-byte aligned
+    const void *src;            // the call's inputs in `format`, 16-byte aligned
     uint64_t n_in;              // ... how many (> 0)
     const uint32_t *hist_prev;  // the n_taps - 1 inputs in front of the call (zero where the stream had not begun)
     uint32_t *hist_next;        // ... and in front of the next one (the other buffer)
@@ -441,6 +449,9 @@ struct DecimParams {
     uint32_t row_len;           // decim_row_len(factor, n_taps): dwords per polyphase row in LDS
     uint32_t recip;             // ceil(2^20 / factor)
     MixParams mix;              // the mixer (period 0: none)
+    // after everything else, so that the CS16 and 8-bit instantiations see the layout they always had
+    uint32_t format;            // InFormat (kIn8Bit exactly when u8_table is set)
+    float scale;                // CF32: g of q(x) = clamp(rint(x g)); means nothing to the other formats
 };
 uint32_t decim_row_len(uint32_t factor, uint32_t n_taps);
 int launch_decim(const DecimParams &p, void *stream);
@@ -450,7 +461,7 @@ constexpr uint32_t kResampMaxRatio = 128, kResampMaxTaps = 4096, kResampMaxPhase
 constexpr uint32_t kResampHistWords = 512;     // a history buffer: the last K - 1 inputs, widened, at [0, K - 1)
 constexpr uint32_t kResampLdsWords = 16384;    // 64 KB per workgroup at most
 struct ResampParams {
-    const void *src;            // the call's inputs: CS16 dwords or byte pairs, 16-byte aligned
+    const void *src;            // the call's inputs in `format`, 16-byte aligned
     uint64_t n_in;              // ... how many (> 0)
     const uint32_t *hist_prev;  // the K - 1 inputs in front of the call (zero where the stream had not begun)
     uint32_t *hist_next;        // ... and in front of the next one (the other buffer)
@@ -466,6 +477,9 @@ struct ResampParams {
     uint32_t row_len;           // resamp_row_len(down, rows, k_taps): dwords per polyphase row in LDS
     uint32_t recip_up, recip_down;   // ceil(2^32 / L), ceil(2^32 / M) (unused where the divisor is 1)
     MixParams mix;              // the mixer (period 0: none)
+    // after everything else, so that the CS16 and 8-bit instantiations see the layout they always had
+    uint32_t format;            // InFormat (kIn8Bit exactly when u8_table is set)
+    float scale;                // CF32: g of q(x) = clamp(rint(x g)); means nothing to the other formats
 };
 uint32_t resamp_rows(uint32_t up, uint32_t down);
 uint32_t resamp_row_len(uint32_t down, uint32_t rows, uint32_t k_taps);

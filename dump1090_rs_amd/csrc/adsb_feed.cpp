@@ -4,8 +4,8 @@
 // reference, main.rs:46) so that downstream tools (adsb_deku's radar, anything that speaks
 // the dump1090 raw format) can consume it.
 //
-//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K]
-//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] <capture.iq | ->
+//   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8|cf32|s16real] [--fix none|1bit|2bit] [--buffers K]
+//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] [--scale G] <capture.iq | ->
 //
 // --decimate D (2..16): the input is sampled at D x 2.4 MS/s, in the format --format names, and goes through the
 // library's decimator with its default taps (adsb_decim_default_taps) in front of the demodulation: the output lines are
@@ -21,6 +21,16 @@
 // --shift HZ (signed; only with --decimate or --resample): the radio was offset-tuned, and the spectrum is moved by HZ on
 // its way into the filter (include/adsb_hip.h, "Frequency shift": adsb_mix_for_shift, adsb_mix_table, adsb_mix_set_*).  A
 // radio tuned 2.4 MHz below 1090 MHz: --shift -2400000.  A shift whose table would be longer than 256 is a usage error.
+//
+// --format cf32 | s16real (only with --decimate or --resample; include/adsb_hip.h, "Sample formats"): cf32 is complex
+// float32, re then im, 8 bytes per sample -- what SoapySDR applications, GNU Radio file sinks, gqrx and `airspy_rx -t 0`
+// write -- converted on the device as clamp(rint(x G)); --scale G (only with --format cf32; finite, 0 < G <= 2^31) sets G,
+// 32768 by default.  s16real is one real int16 per sample, what `airspy_rx -t 3` writes; its band sits at a quarter of the
+// sample rate, and --shift brings it down with the exact quarter-turn table:
+//   Airspy R2 raw, 20 MS/s:    adsb_feed --format s16real --resample 3/25 --shift -5000000
+//   Airspy Mini raw, 12 MS/s:  adsb_feed --format s16real --decimate 5 --shift -3000000
+// cf32 that is already at 2.4 MS/s: --format cf32 --resample 1/1 (the default taps of 1/1 are a plain delay of four
+// samples).  --mem-order means nothing to either format.
 //
 // --stats turns the signal statistics on (adsb_set_signal_stats) and prints what a receiver's gain is tuned by to
 // STDERR, every SECONDS (default 1) over the buffers since the last line and once more, as the last line, over the
@@ -326,8 +336,10 @@ int main(int argc, char **argv)
     double stats_seconds = 1.0;
     int fix = ADSB_FIX_NONE, decimate = 0;
     unsigned res_up = 0, res_down = 0;
-    bool shifted = false;
+    bool shifted = false, scaled = false;
     long shift_hz = 0;
+    float scale = 0;
+    int in_format = ADSB_DECIM_CS16;   // (cu8 says ADSB_DECIM_8BIT: the ring path knows only that flag)
     uint32_t mix_k = 0, mix_period = 0;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
@@ -354,6 +366,12 @@ int main(int argc, char **argv)
             shifted = true;
             if (end == argv[i] || *end != 0 || shift_hz < -2147483647L || shift_hz > 2147483647L) path = nullptr, i = argc;
         }
+        else if (a == "--scale" && i + 1 < argc) {
+            char *end = nullptr;
+            scale = std::strtof(argv[++i], &end);
+            scaled = true;
+            if (end == argv[i] || *end != 0 || !(scale > 0.0f) || !(scale <= 2147483648.0f)) path = nullptr, i = argc;
+        }
         else if (a == "--out-cap" && i + 1 < argc) out_cap = std::atoi(argv[++i]);  // frames the output array starts with (it grows)
         else if (a == "--stats") {
             stats = true;
@@ -365,8 +383,11 @@ int main(int argc, char **argv)
         else if (a == "--mem-order") mem_order = true;
         else if (a == "--format" && i + 1 < argc) {
             const std::string f = argv[++i];
-            if (f == "cu8") cu8 = true;
-            else if (f == "cs16") cu8 = false;
+            cu8 = f == "cu8";
+            if (f == "cu8") in_format = ADSB_DECIM_8BIT;
+            else if (f == "cs16") in_format = ADSB_DECIM_CS16;
+            else if (f == "cf32") in_format = ADSB_DECIM_CF32;
+            else if (f == "s16real") in_format = ADSB_DECIM_REAL16;
             else path = nullptr, i = argc;
         }
         else if (a == "--fix" && i + 1 < argc) {
@@ -383,8 +404,11 @@ int main(int argc, char **argv)
     const bool shift_ok = !shifted || ((decimate != 0) != (res_up != 0) &&
                                        adsb_mix_for_shift(decimate ? 1u : res_up, decimate ? (uint32_t)decimate : res_down, (int32_t)shift_hz,
                                                           &mix_k, &mix_period) == ADSB_OK);
-    if (!path || buffers < 1 || (decimate && res_up) || !shift_ok) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] <capture.iq | ->\n");
+    // --format cf32 | s16real: only in front of a filter (the scan's own entry points take neither); --scale: only with cf32
+    const bool new_format = in_format == ADSB_DECIM_CF32 || in_format == ADSB_DECIM_REAL16;
+    const bool format_ok = (!new_format || decimate || res_up) && (!scaled || in_format == ADSB_DECIM_CF32);
+    if (!path || buffers < 1 || (decimate && res_up) || !shift_ok || !format_ok) {
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8|cf32|s16real] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] [--scale G] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -408,7 +432,7 @@ int main(int argc, char **argv)
     const bool blocking = decimate || res_up;   // through the decimator or the resampler: the blocking call, not the ring
     if (!blocking && (st = cu8 ? adsb_ring_create_u8(ctx, slot_samples) : adsb_ring_create(ctx, slot_samples)) != ADSB_OK)
         return die(ctx, "adsb_ring_create", st);
-    const size_t bps = cu8 ? 2 : 4;   // bytes per sample
+    const size_t bps = in_format == ADSB_DECIM_CF32 ? 8 : in_format == ADSB_DECIM_CS16 ? 4 : 2;   // bytes per sample
 
     // a 112 us frame every 120 us would be ~450 per 55 ms buffer; neighbouring preamble
     // positions can each emit one, so leave an order of magnitude of room
@@ -491,6 +515,10 @@ int main(int argc, char **argv)
                 return die(ctx, "adsb_mix_table / adsb_mix_set", st);
             }
         }
+        if (scaled && (st = dec ? adsb_fmt_set_scale_decim(dec, scale) : adsb_fmt_set_scale_resamp(res, scale)) != ADSB_OK) {
+            destroy();
+            return die(ctx, "adsb_fmt_set_scale", st);
+        }
         std::vector<char> in_buf(call_samples * bps);
         const auto t0 = std::chrono::steady_clock::now();
         for (bool eof = false; !eof;) {
@@ -501,9 +529,9 @@ int main(int argc, char **argv)
             }
             const size_t n_in = fill / bps;
             if (n_in == 0) break;
-            if (!mem_order && !cu8) swap_pairs(in_buf.data(), n_in);
+            if (!mem_order && in_format == ADSB_DECIM_CS16) swap_pairs(in_buf.data(), n_in);
             size_t n = 0;
-            const int fmt = cu8 ? ADSB_DECIM_8BIT : ADSB_DECIM_CS16;
+            const int fmt = in_format;
             st = dec ? adsb_decim_demod_iq(dec, fmt, in_buf.data(), n_in, out.data(), out.size(), &n)
                      : adsb_resamp_demod_iq(res, fmt, in_buf.data(), n_in, out.data(), out.size(), &n);
             if (st == ADSB_ERR_CAPACITY) {

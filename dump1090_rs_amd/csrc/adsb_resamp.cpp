@@ -24,12 +24,14 @@ struct adsb_resamp {
     void *d_out = nullptr;
     size_t out_bytes = 0;
     Mixer mix;
+    float scale = kInDefaultScale;   // CF32: g of q(x) (adsb_fmt.cpp)
     Registry mem;   // owns the five buffers above and the mixer's table
 };
 
 namespace adsb {
 namespace host {
 MixerOwner mixer_of(adsb_resamp *r) { return {r->ctx, &r->mem, &r->mix}; }
+float *scale_of(adsb_resamp *r) { return &r->scale; }
 }  // namespace host
 }  // namespace adsb
 
@@ -66,8 +68,6 @@ inline uint64_t inputs_for(const adsb_resamp *r, uint64_t need)
     return (uint64_t)((u128)last * r->down / r->up) - r->consumed + 1;
 }
 
-inline bool format_ok(int format) { return format == ADSB_DECIM_CS16 || format == ADSB_DECIM_8BIT; }
-
 // One call on the context's input stream: the kernels, the history's turn and P.  No wait.
 int run_on_stream(adsb_resamp *r, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t n_out)
 {
@@ -81,6 +81,8 @@ int run_on_stream(adsb_resamp *r, int format, const void *d_in, uint64_t n_in, v
     p.hist_next = r->d_hist[r->cur ^ 1];
     p.taps = r->d_taps;
     p.u8_table = format == ADSB_DECIM_8BIT ? c->d_u8_table : nullptr;
+    p.format = (uint32_t)format;
+    p.scale = r->scale;
     p.out = static_cast<uint32_t *>(d_out);
     p.n_out = n_out;
     p.up = L, p.down = M, p.k_taps = r->k_taps, p.k_pad = r->k_pad, p.shift = r->shift;
@@ -126,7 +128,7 @@ int demod_host(adsb_resamp *r, int format, const void *host_iq, size_t n_in, ads
     adsb_ctx *c = r->ctx;
     ADSB_ON_DEVICE(c);
     if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
-    const size_t bps = format == ADSB_DECIM_8BIT ? 2 : 4;
+    const size_t bps = in_bytes_per_sample((uint32_t)format);
     const char *in = static_cast<const char *>(host_iq);
     const uint64_t total_out = out_count(r, n_in);
     // pieces of whole output buffers, at most what one pass of a small call takes
@@ -245,6 +247,7 @@ try {
 } ADSB_ABI_CATCH
 
 uint32_t adsb_mix_get_resamp(const adsb_resamp *r) { return r ? r->mix.period : 0; }
+float adsb_fmt_get_scale_resamp(const adsb_resamp *r) { return r ? r->scale : 0.0f; }
 
 int adsb_resamp_out_count(const adsb_resamp *r, size_t n_in, size_t *n_out)
 {

@@ -3,7 +3,7 @@
 //
 //   p = (n M) mod L,  q = floor(n M / L),  y[n] = clamp((sum_j h[p + j L] x[q - j] + r) >> s), re and im separately.
 //
-// A memory-bound pass: (4 or 2) M / L bytes read and 4 written per output.  The phase p differs from output to output,
+// A memory-bound pass: (8, 4 or 2) M / L bytes read and 4 written per output.  The phase p differs from output to output,
 // but outputs n and n + L share it and their inputs lie exactly M apart.  A workgroup of 256 lanes takes a tile of L R
 // consecutive outputs as L CLASSES of R outputs each (output i of the tile: class i mod L, member i div L), and a wave
 // works on 64 members of one class at a time:
@@ -19,6 +19,8 @@
 //     zero for whatever lies in front of the call or past its end.  Inputs in front of the call come from the history
 //     buffer instead (the first K - 1 inputs of the first tiles); 8-bit input is widened as it is stored to LDS, through
 //     a copy of the context's table in LDS, and masked by position: a sample in front of the stream is zero, not T8[0];
+//   * FMT (include/adsb_hip.h, "Sample formats"; adsb_fmt_dev.h): as in k_decim, the format fixes the samples of a
+//     16-byte load (4, 8, 2, 8 for CS16, 8-bit, CF32, REAL16) and the conversion to CS16 in front of the mixer;
 //   * MIX (include/adsb_hip.h, "Frequency shift"): as in k_decim, a sample of the call is mixed with its table entry
 //     between the widening and the store to LDS; the table comes through cached global loads (adsb_mix_dev.h), no LDS.
 // The host hands over the call's first output already reduced (p0, q0): the kernel works in offsets that fit 32 bits
@@ -32,6 +34,7 @@
 // tests/test_resamp_cpu.py enumerates this.  No scratch, no spills.
 #include "../../include/adsb_hip.h"
 #include "adsb_dev_common.h"
+#include "adsb_fmt_dev.h"
 #include "adsb_mix_dev.h"
 
 namespace adsb {
@@ -59,13 +62,14 @@ __device__ __forceinline__ int round_clamp_r(int acc, uint32_t shift, int round)
     return min(max((acc + round) >> shift, -32768), 32767);
 }
 
-template <bool U8, bool MIX>
+template <uint32_t FMT, bool MIX>
 __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
 {
     extern __shared__ uint32_t lds[];
-    constexpr int kPerLoad = U8 ? 8 : 4;   // samples per 16-byte load
+    constexpr bool U8 = FMT == kIn8Bit;
+    constexpr int kBps = (int)in_bytes_per_sample(FMT);
+    constexpr int kPerLoad = 16 / kBps;    // samples per 16-byte load
     constexpr int kBatch = 4;              // loads in flight per lane
-    constexpr int kBps = U8 ? 2 : 4;
     const int tid = threadIdx.x;
     const uint32_t L = p.up, M = p.down, H = p.k_taps - 1, RL = p.row_len, R = p.rows;
     const uint32_t tile = L * R;
@@ -114,6 +118,10 @@ __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
                 if constexpr (U8) {
                     const uint32_t b2 = (w[c >> 1] >> (16 * (c & 1))) & 0xFFFFu;
                     v[c] = (ii >= 0 && ii < (long long)p.n_in) ? widen_u8_pair(tab, b2) : 0u;
+                } else if constexpr (FMT == kInReal16) {   // (the load is rounded up to a dword: the int16 behind an odd end)
+                    v[c] = (ii >= 0 && ii < (long long)p.n_in) ? fmt_halfword(w, c) : 0u;
+                } else if constexpr (FMT == kInCf32) {     // (out of range the load gave +0.0, and q(0) = 0)
+                    v[c] = fmt_cf32(w[2 * c], w[2 * c + 1], p.scale);
                 } else {
                     v[c] = w[c];
                 }
@@ -206,9 +214,10 @@ __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
 // the last H = K - 1 inputs of the stream so far, widened: from the call's input, or from the previous history where
 // the call was shorter than the history (k_decim_history's rule).  MIX: what comes from the call's input is mixed, what
 // comes from the previous history is mixed already.
-template <bool U8, bool MIX>
+template <uint32_t FMT, bool MIX>
 __global__ __launch_bounds__(512) void k_resamp_history(ResampParams p)
 {
+    constexpr bool U8 = FMT == kIn8Bit;
     const long long H = (long long)p.k_taps - 1, i = threadIdx.x, n = (long long)p.n_in;
     if (i >= H) return;
     const long long idx = n - H + i;
@@ -219,6 +228,11 @@ __global__ __launch_bounds__(512) void k_resamp_history(ResampParams p)
         if constexpr (U8) {
             const uint8_t *s = (const uint8_t *)p.src;
             v = widen_u8_pair(p.u8_table, (uint32_t)s[2 * idx] | (uint32_t)s[2 * idx + 1] << 8);
+        } else if constexpr (FMT == kInReal16) {
+            v = ((const uint16_t *)p.src)[idx];
+        } else if constexpr (FMT == kInCf32) {
+            const uint2 f = ((const uint2 *)p.src)[idx];
+            v = fmt_cf32(f.x, f.y, p.scale);
         } else {
             v = ((const uint32_t *)p.src)[idx];
         }
@@ -265,7 +279,7 @@ int launch_resamp(const ResampParams &p, void *stream)
         p.recip_up != (uint32_t)(((1ull << 32) + p.up - 1u) / p.up) || p.recip_down != (uint32_t)(((1ull << 32) + p.down - 1u) / p.down) ||
         !p.src || !p.n_in || !p.hist_prev || !p.hist_next || !p.taps)
         return (int)hipErrorInvalidValue;
-    if (!mix_params_ok(p.mix)) return (int)hipErrorInvalidValue;
+    if (!mix_params_ok(p.mix) || !in_format_ok(p.format, p.u8_table, p.scale)) return (int)hipErrorInvalidValue;
     const uint32_t lds_words = resamp_lds_words(p.up, p.down, p.rows, p.k_taps);
     if (lds_words > kResampLdsWords) return (int)hipErrorInvalidValue;
     // the call's first output has its newest input inside the call (then every tile's first output has)
@@ -275,16 +289,21 @@ int launch_resamp(const ResampParams &p, void *stream)
     if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     // ... and so has its last: floor((p0 + (n_out - 1) M) / L) + q0 < n_in  (n_out < 2^31 tiles of 2^13 at most: 64 bits do)
     if (p.n_out && ((p.n_out - 1) * p.down + p.p0) / p.up + p.q0 >= p.n_in) return (int)hipErrorInvalidValue;
-    const bool u8 = p.u8_table != nullptr, mix = p.mix.period != 0;
+    const bool u8 = p.format == kIn8Bit, mix = p.mix.period != 0;
     if (blocks) {
         const size_t lds_bytes = (size_t)lds_words * 4u;
-        const auto kernel = u8 ? (mix ? k_resamp<true, true> : k_resamp<true, false>) : (mix ? k_resamp<false, true> : k_resamp<false, false>);
+        const auto kernel = p.format == kInCf32    ? (mix ? k_resamp<kInCf32, true> : k_resamp<kInCf32, false>)
+                            : p.format == kInReal16 ? (mix ? k_resamp<kInReal16, true> : k_resamp<kInReal16, false>)
+                            : u8                    ? (mix ? k_resamp<kIn8Bit, true> : k_resamp<kIn8Bit, false>)
+                                                    : (mix ? k_resamp<kInCs16, true> : k_resamp<kInCs16, false>);
         hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kThreadsResamp), lds_bytes, (hipStream_t)stream, p);
         if (hipError_t e = hipGetLastError()) return (int)e;
     }
     if (p.k_taps > 1) {
-        const auto kernel = u8 ? (mix ? k_resamp_history<true, true> : k_resamp_history<true, false>)
-                               : (mix ? k_resamp_history<false, true> : k_resamp_history<false, false>);
+        const auto kernel = p.format == kInCf32    ? (mix ? k_resamp_history<kInCf32, true> : k_resamp_history<kInCf32, false>)
+                            : p.format == kInReal16 ? (mix ? k_resamp_history<kInReal16, true> : k_resamp_history<kInReal16, false>)
+                            : u8                    ? (mix ? k_resamp_history<kIn8Bit, true> : k_resamp_history<kIn8Bit, false>)
+                                                    : (mix ? k_resamp_history<kInCs16, true> : k_resamp_history<kInCs16, false>);
         hipLaunchKernelGGL(kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
     }
     return (int)hipGetLastError();

@@ -584,7 +584,8 @@ uint32_t adsb_rx_set_home(uint64_t key, uint32_t set_lg);
  *                            input decimates to -- buffers are cut every 131072 OUTPUT samples of the call, the last may
  *                            be short, `chunk` counts over the call; the filter persists.  Works in pieces of whole
  *                            output buffers, min(max_chunks, 16) of them at most, through staging the decimator allocates
- *                            on first use (at most (4 or 2) D + 4 bytes per output sample of a piece) and frees in
+ *                            on first use (at most b D + 4 bytes per output sample of a piece, b the bytes of an input
+ *                            sample: 8 for CF32, 4 for CS16, 2 for 8-bit and REAL16 -- "Sample formats") and frees in
  *                            adsb_decim_destroy.  ADSB_ERR_CAPACITY, adsb_fetch_messages, ADSB_ERR_BUSY and every context
  *                            mode (error correction, signal statistics, carry-over) are adsb_demod_iq's: the pass
  *                            underneath is the ordinary one.
@@ -731,6 +732,59 @@ extern uint32_t adsb_mix_get_decim(const adsb_decim *d);
 extern uint32_t adsb_mix_get_resamp(const adsb_resamp *r);
 ADSB_MUST_CHECK int adsb_mix_table(uint32_t k, uint32_t period, int16_t *cs_pairs, size_t cap);
 ADSB_MUST_CHECK int adsb_mix_for_shift(uint32_t up, uint32_t down, int32_t shift_hz, uint32_t *k, uint32_t *period);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Sample formats -- complex float32 and real int16 input.  CS16 and 8-bit pairs are two of the layouts the radios above
+ * produce.  Complex float32 (CF32) is the stream format of SoapySDR applications and GNU Radio file sinks, what gqrx and
+ * SigMF `cf32_le` record and what `airspy_rx -t 0` and UHD `fc32` deliver; an Airspy R2 or Mini samples REAL values
+ * (`airspy_rx -t 3`: int16 at 20 or 12 MS/s, the band at a quarter of the sample rate).  A decimator or a resampler reads
+ * both: adsb_decim_run_device, adsb_decim_demod_iq, adsb_resamp_run_device and adsb_resamp_demod_iq take the two formats
+ * below as they take CS16 and 8-bit, signatures and semantics unchanged.  The sample is converted to CS16 on the device
+ * between the load and the mixer: no kernel of its own, no second pass over the input.
+ *
+ * Definition.  The converted sample replaces x[m] in the decimator's and the resampler's definitions; the mixer, taps,
+ * shift, counts and "the cut is invisible" follow unchanged.
+ *   ADSB_DECIM_CF32    8 bytes per sample: float32 re, float32 im, little-endian.  Each component x means q(x), with the
+ *                      handle's scale g (32768.0f by default):
+ *                          t    = x * g        one IEEE binary32 multiply, round to nearest even, contracted with nothing
+ *                          q(x) = 0                                        where t is a NaN
+ *                          q(x) = clamp(rint(t), -32768, 32767)            otherwise: ties to even, +-inf to the rails
+ *                      A subnormal x gives 0 whether or not the device flushes it: 2^-126 * 2^31 rounds to 0.  So numpy's
+ *                          np.rint(x.astype(np.float32) * np.float32(g)), NaN mapped to 0, clipped to -32768 .. 32767
+ *                      is q bit for bit, with no tolerance.
+ *   ADSB_DECIM_REAL16  2 bytes per sample: one int16 r; x[m] = (r[m], 0).
+ * As for 8-bit, a sample outside the call is zero by position: x[m < 0] is zero and so is whatever lies behind the end of
+ * the call's input -- the int16 behind an odd number of REAL16 samples, which the rounded-up load does fetch, never
+ * reaches the filter.  The history holds converted (and mixed) CS16, so one stream may alternate all four formats from
+ * call to call.
+ * Sizes.  Device input is 16-byte aligned, as for the other formats.  adsb_*_demod_iq stages 8, 4, 2 or 2 bytes per input
+ * sample for CF32, CS16, 8-bit and REAL16: at most that times D (or M / L) plus 4 bytes per output sample of a piece.
+ *
+ *   adsb_fmt_set_scale_decim   }  g, finite with 0 < g <= 2^31; anything else is ADSB_ERR_INVALID and changes nothing.
+ *   adsb_fmt_set_scale_resamp  }  Host state that travels in each launch's parameters: it applies to the calls made after
+ *                                 the setter, is never ADSB_ERR_BUSY and means nothing to the other three formats.
+ *   adsb_fmt_get_scale_decim   }  g; 0 for NULL
+ *   adsb_fmt_get_scale_resamp  }
+ *                                 (The four calls carry the adsb_fmt_ prefix: the adsb_decim_* and adsb_resamp_* families
+ *                                 gain no function.)
+ * Recipes.
+ *   CF32 already at 2.4 MS/s   a 1/1 resampler with the single tap 1 and shift 0 -- "L = M = 1 is a plain FIR" with
+ *                              K = 1: adsb_resamp_create(ctx, 1, 1, &one, 1, 0, &r), then adsb_resamp_demod_iq(r,
+ *                              ADSB_RESAMP_CF32, ...) is adsb_demod_iq on q of the input.
+ *   Airspy R2 raw, 20 MS/s     REAL16 through a 3/25 resampler with the mixer adsb_mix_table(3, 4), the exact rotation that
+ *                              brings the band at +fs/4 to 0:  adsb_feed --format s16real --resample 3/25 --shift -5000000
+ *   Airspy Mini raw, 12 MS/s   REAL16 through a decimator with D = 5 and the same table:
+ *                                                              adsb_feed --format s16real --decimate 5 --shift -3000000
+ * Not here: exploiting the zero imaginary part, Airspy's unsigned and packed 12-bit real formats, real float32, and float
+ * input to the scan's own entry points. */
+#define ADSB_DECIM_CF32   2   /* 8 bytes per sample: f32 re, f32 im, little-endian */
+#define ADSB_DECIM_REAL16 3   /* 2 bytes per sample: one int16 r; x[m] = (r[m], 0) */
+#define ADSB_RESAMP_CF32   ADSB_DECIM_CF32
+#define ADSB_RESAMP_REAL16 ADSB_DECIM_REAL16
+ADSB_MUST_CHECK int adsb_fmt_set_scale_decim(adsb_decim *d, float scale);
+ADSB_MUST_CHECK int adsb_fmt_set_scale_resamp(adsb_resamp *r, float scale);
+extern float adsb_fmt_get_scale_decim(const adsb_decim *d);
+extern float adsb_fmt_get_scale_resamp(const adsb_resamp *r);
 
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167

@@ -128,6 +128,8 @@ pub struct AdsbDecim {
 
 pub const ADSB_DECIM_CS16: i32 = 0;
 pub const ADSB_DECIM_8BIT: i32 = 1;
+pub const ADSB_DECIM_CF32: i32 = 2;
+pub const ADSB_DECIM_REAL16: i32 = 3;
 
 /// An exact-integer L/M resampler in front of the scan, for IQ at 2.5, 3, 6, 8, 10, 20 MS/s and the like (`adsb_resamp_*`).
 #[repr(C)]
@@ -137,6 +139,8 @@ pub struct AdsbResamp {
 
 pub const ADSB_RESAMP_CS16: i32 = ADSB_DECIM_CS16;
 pub const ADSB_RESAMP_8BIT: i32 = ADSB_DECIM_8BIT;
+pub const ADSB_RESAMP_CF32: i32 = ADSB_DECIM_CF32;
+pub const ADSB_RESAMP_REAL16: i32 = ADSB_DECIM_REAL16;
 
 /// One capture over several GPUs from one process: one handle, one filter (`adsb_multi_*`).
 #[repr(C)]
@@ -302,4 +306,14 @@ unsafe extern "C" {
     pub fn adsb_mix_get_resamp(r: *const AdsbResamp) -> u32;
     pub fn adsb_mix_table(k: u32, period: u32, cs_pairs: *mut i16, cap: usize) -> c_int;
     pub fn adsb_mix_for_shift(up: u32, down: u32, shift_hz: i32, k: *mut u32, period: *mut u32) -> c_int;
+}
+
+// The CF32 scale of a decimator or resampler (include/adsb_hip.h, "Sample formats"); compared with the header by
+// tests/test_formats_in_cpu.py.
+#[link(name = "adsb_hip")]
+unsafe extern "C" {
+    pub fn adsb_fmt_set_scale_decim(d: *mut AdsbDecim, scale: f32) -> c_int;
+    pub fn adsb_fmt_set_scale_resamp(r: *mut AdsbResamp, scale: f32) -> c_int;
+    pub fn adsb_fmt_get_scale_decim(d: *const AdsbDecim) -> f32;
+    pub fn adsb_fmt_get_scale_resamp(r: *const AdsbResamp) -> f32;
 }
