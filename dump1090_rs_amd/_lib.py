@@ -343,6 +343,28 @@ def lib() -> C.CDLL:
     for name in ("adsb_fmt_get_scale_decim", "adsb_fmt_get_scale_resamp"):
         getattr(L, name).argtypes = [vp]
         getattr(L, name).restype = C.c_float
+    # resampler banks (include/adsb_hip.h)
+    szp = C.POINTER(sz)
+    L.adsb_bank_create.argtypes = [vp, u32, u32, u32, vp, u32, u32, C.POINTER(vp)]
+    L.adsb_bank_destroy.argtypes = [vp]
+    L.adsb_bank_destroy.restype = None
+    L.adsb_bank_streams.argtypes = [vp]
+    L.adsb_bank_reset.argtypes = [vp, u32]
+    L.adsb_bank_consumed.argtypes = [vp, u32, u64p]
+    L.adsb_bank_out_count.argtypes = [vp, u32, sz, szp]
+    L.adsb_bank_inputs_for.argtypes = [vp, u32, sz, szp, szp]
+    L.adsb_bank_run_device.argtypes = [vp, C.c_int, u32, vp, vp, vp, vp, vp, vp]
+    L.adsb_bank_set_mixer.argtypes = [vp, vp, u32]
+    L.adsb_bank_get_mixer.argtypes = [vp]
+    L.adsb_bank_set_scale.argtypes = [vp, C.c_float]
+    L.adsb_bank_get_scale.argtypes = [vp]
+    L.adsb_bank_get_scale.restype = C.c_float
+    L.adsb_bank_selftest_depth.argtypes = []
+    for name in ("adsb_bank_streams", "adsb_bank_get_mixer", "adsb_bank_selftest_depth"):
+        getattr(L, name).restype = u32
+    for name in ("adsb_bank_create", "adsb_bank_reset", "adsb_bank_consumed", "adsb_bank_out_count", "adsb_bank_inputs_for",
+                 "adsb_bank_run_device", "adsb_bank_set_mixer", "adsb_bank_set_scale"):
+        getattr(L, name).restype = C.c_int
     L.adsb_host_replays.argtypes = [vp]
     L.adsb_host_replays.restype = C.c_uint64
     L.adsb_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]

@@ -400,6 +400,16 @@ class Context:
             r.set_mixer(mixer_table(*mixer_for_shift(up, down, shift_hz)))
         return r
 
+    def resampler_bank(self, n_streams: int, up: int, down: int, taps=None, shift: Optional[int] = None,
+                       shift_hz: Optional[int] = None) -> "ResamplerBank":
+        """n_streams independent resampler streams of one ratio and one filter that one call advances in one launch
+        (include/adsb_hip.h, "Resampler banks"): each stream is a resampler() of the same arguments.  taps, shift and
+        shift_hz as for resampler()."""
+        b = ResamplerBank(self, n_streams, up, down, taps, shift)
+        if shift_hz is not None:
+            b.set_mixer(mixer_table(*mixer_for_shift(up, down, shift_hz)))
+        return b
+
     def converter(self, scale: Optional[float] = None) -> "Resampler":
         """The 1/1 resampler with the single tap 1 and shift 0 -- the identity on CS16 -- for CF32 (or REAL16, 8-bit)
         input that is already at 2.4 MS/s (include/adsb_hip.h, "Sample formats"): converter().demod_iq(x,
@@ -930,6 +940,113 @@ class Resampler:
         return self._ctx._collect(
             lambda out, c, n: self._L.adsb_resamp_demod_iq(self._h, int(format), ptr, a.shape[0], out, c, n),
             "adsb_resamp_demod_iq", cap)
+
+
+class ResamplerBank:
+    """One adsb_bank: n_streams stateful resampler streams of one ratio and one filter on the context's device, advanced
+    by one call (include/adsb_hip.h, "Resampler banks").  Close it before its context."""
+
+    ALL = 0xFFFFFFFF   # ADSB_BANK_ALL
+
+    def __init__(self, ctx: Context, n_streams: int, up: int, down: int, taps=None, shift: Optional[int] = None):
+        self._ctx, self._L = ctx, ctx._L
+        self._h = C.c_void_p()
+        if taps is None:
+            taps, default_shift = default_resampler_taps(up, down)
+            shift = default_shift if shift is None else shift
+        elif shift is None:
+            raise ValueError("taps of the caller's need a shift")
+        t = np.ascontiguousarray(taps, dtype=np.int16)
+        if t.ndim != 1:
+            raise ValueError("the taps are a flat int16 array")
+        self.up, self.down, self.taps, self.shift = int(up), int(down), t, int(shift)
+        self._check(self._L.adsb_bank_create(ctx._h, int(n_streams), int(up), int(down), t.ctypes.data, t.size, int(shift),
+                                             C.byref(self._h)), "adsb_bank_create")
+
+    def _check(self, st: int, what: str) -> None:
+        self._ctx._check(st, what)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            if self._ctx._h.value:   # (a context that is gone took the device state with it)
+                self._L.adsb_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def streams(self) -> int:
+        return int(self._L.adsb_bank_streams(self._h))
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """One stream, or every stream (None), starts over: P = 0 and a zero history, ordered on the stream like a run."""
+        self._check(self._L.adsb_bank_reset(self._h, self.ALL if stream is None else int(stream)), "adsb_bank_reset")
+
+    def consumed(self, stream: int) -> int:
+        p = C.c_uint64()
+        self._check(self._L.adsb_bank_consumed(self._h, int(stream), C.byref(p)), "adsb_bank_consumed")
+        return p.value
+
+    def out_count(self, stream: int, n_in: int) -> int:
+        n = C.c_size_t()
+        self._check(self._L.adsb_bank_out_count(self._h, int(stream), int(n_in), C.byref(n)), "adsb_bank_out_count")
+        return n.value
+
+    def inputs_for(self, stream: int, n_out: int):
+        """(n_in, n_out_made): the fewest inputs behind the stream's P that give at least n_out outputs, and how many they
+        give (n_out, or one more where up > down)."""
+        n_in, made = C.c_size_t(), C.c_size_t()
+        self._check(self._L.adsb_bank_inputs_for(self._h, int(stream), int(n_out), C.byref(n_in), C.byref(made)),
+                    "adsb_bank_inputs_for")
+        return n_in.value, made.value
+
+    def run_device(self, streams, ptrs_in, n_in, ptrs_out, out_caps, format: int = _lib.ADSB_DECIM_CS16) -> np.ndarray:
+        """Run r advances streams[r] by n_in[r] inputs at device address ptrs_in[r] and writes its outputs to ptrs_out[r]
+        (room for out_caps[r]); one launch for all of them, enqueued without waiting.  Returns the output counts.
+        AdsbError with status ADSB_ERR_CAPACITY (and the required counts in .required) when a run does not fit: nothing
+        was consumed."""
+        s = np.ascontiguousarray(streams, dtype=np.uint32)
+        pi, po = np.ascontiguousarray(ptrs_in, dtype=np.uintp), np.ascontiguousarray(ptrs_out, dtype=np.uintp)
+        ni, caps = np.ascontiguousarray(n_in, dtype=np.uintp), np.ascontiguousarray(out_caps, dtype=np.uintp)
+        if not (s.ndim == 1 and s.shape == pi.shape == po.shape == ni.shape == caps.shape):
+            raise ValueError("streams, pointers, counts and capacities are flat arrays of one length")
+        n = np.zeros(max(s.size, 1), dtype=np.uintp)
+        st = self._L.adsb_bank_run_device(self._h, int(format), s.size, s.ctypes.data, pi.ctypes.data, ni.ctypes.data,
+                                          po.ctypes.data, caps.ctypes.data, n.ctypes.data)
+        n = n[: s.size]
+        if st == _lib.ADSB_ERR_CAPACITY:
+            err = AdsbError(st, f"adsb_bank_run_device: {n.tolist()} outputs do not fit {caps.tolist()}")
+            err.required = n
+            raise err
+        self._check(st, "adsb_bank_run_device")
+        return n
+
+    def set_mixer(self, table) -> None:
+        """adsb_bank_set_mixer: the (period, 2) int16 table {c, s} every stream's inputs consumed from now on are mixed
+        with, each stream at its own phase (None: no mixer)."""
+        _set_mixer(self, self._L.adsb_bank_set_mixer, "adsb_bank_set_mixer", table)
+
+    @property
+    def mixer_period(self) -> int:
+        return int(self._L.adsb_bank_get_mixer(self._h))
+
+    def set_scale(self, scale: float) -> None:
+        """adsb_bank_set_scale: g of CF32 input, q(x) = clamp(rint(x g)); finite, 0 < g <= 2^31 (32768 by default)."""
+        _set_scale(self, self._L.adsb_bank_set_scale, "adsb_bank_set_scale", scale)
+
+    @property
+    def scale(self) -> float:
+        return float(self._L.adsb_bank_get_scale(self._h))
 
 
 _default: Optional[Context] = None

@@ -9,6 +9,7 @@
 //   adsb_ring.cpp      the pinned streaming ring
 //   adsb_decim.cpp     the decimator in front of the scan: its handle, counts, staging and default taps
 //   adsb_resamp.cpp    the L/M resampler in front of the scan: its handle, counts, staging, default taps and ratios
+//   adsb_bank.cpp      a bank of resampler streams advanced by one launch: its handle, per-stream state and descriptors
 //   adsb_mix.cpp       the mixer of a decimator or resampler: its table on the device, the table and shift helpers
 //   adsb_shard.cpp     the two-phase shard calls
 //   adsb_selftest.cpp  stage lists and digests for the tests
@@ -547,6 +548,7 @@ struct MixerOwner {
 };
 MixerOwner mixer_of(adsb_decim *d);
 MixerOwner mixer_of(adsb_resamp *r);
+MixerOwner mixer_of(adsb_bank *b);
 inline MixParams mixer_params(const Mixer &m, uint64_t consumed)
 {
     MixParams p{};
@@ -561,6 +563,7 @@ inline MixParams mixer_params(const Mixer &m, uint64_t consumed)
 // every launch in its parameters.  scale_of is how adsb_fmt.cpp reaches a handle's (each handle's unit defines its own).
 float *scale_of(adsb_decim *d);
 float *scale_of(adsb_resamp *r);
+float *scale_of(adsb_bank *b);
 inline bool format_ok(int format) { return format >= 0 && format < (int)kInFormats; }
 // T_soapy: the table SoapyRTLSDR widens an RTL-SDR's bytes with, (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f)
 void soapy_u8_table(int16_t *out256);

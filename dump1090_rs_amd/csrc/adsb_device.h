@@ -485,6 +485,26 @@ uint32_t resamp_rows(uint32_t up, uint32_t down);
 uint32_t resamp_row_len(uint32_t down, uint32_t rows, uint32_t k_taps);
 uint32_t resamp_lds_words(uint32_t up, uint32_t down, uint32_t rows, uint32_t k_taps);
 int launch_resamp(const ResampParams &p, void *stream);
+// Resampler banks (adsb_bank_*; adsb_resamp.hip: k_resamp_bank, k_resamp_bank_history): many calls of one ratio and one
+// filter in one launch.  What a call has of its own -- a ResampParams' src, n_in, out, n_out, hist_prev, hist_next, p0,
+// q0 and mix.phase -- comes from descriptor blockIdx.y in device memory; everything else stays in the launch's parameters.
+constexpr uint32_t kResampBankMaxRuns = 16384;   // ADSB_MAX_RECEIVERS (the grid's y extent: 65535 at most)
+struct ResampBankRun {
+    const void *src;
+    uint64_t n_in;              // (> 0: a run without input is not described)
+    uint32_t *out;
+    uint64_t n_out;
+    const uint32_t *hist_prev;
+    uint32_t *hist_next;
+    uint32_t p0, q0;
+    uint32_t mix_phase;         // P mod N of this run's stream (0 without a mixer)
+    uint32_t reserved;
+};
+// `common`: a ResampParams whose per-call fields mean nothing; `runs`: the descriptors as the host sees them (checked here,
+// each as launch_resamp checks a call), `d_runs`: the same in device memory, complete before the launch on `stream`.  The
+// grid is (tiles of the longest run) x n_runs: a workgroup past its run's last output returns at once.
+int launch_resamp_bank(const ResampParams &common, const ResampBankRun *runs, const ResampBankRun *d_runs, uint32_t n_runs,
+                       void *stream);
 // self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
 int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 

@@ -1,6 +1,7 @@
 // adsb_mix.cpp -- the host side of the mixer a decimator or a resampler may carry (include/adsb_hip.h, "Frequency
 // shift"): the table's checks and its way to the device (k_mix_store, adsb_decim.hip), and the two host-only helpers,
-// adsb_mix_table and adsb_mix_for_shift.  The handles are adsb_decim.cpp's and adsb_resamp.cpp's: mixer_of reaches into them.
+// adsb_mix_table and adsb_mix_for_shift.  The handles are adsb_decim.cpp's, adsb_resamp.cpp's and adsb_bank.cpp's: mixer_of
+// reaches into them.
 #include <cmath>
 #include <numeric>
 
@@ -50,6 +51,13 @@ int adsb_mix_set_resamp(adsb_resamp *r, const int16_t *cs_pairs, uint32_t period
 try {
     if (!r) return ADSB_ERR_INVALID;
     const MixerOwner o = mixer_of(r);
+    return mixer_set(o.ctx, *o.mem, *o.mix, cs_pairs, period);
+} ADSB_ABI_CATCH
+
+int adsb_bank_set_mixer(adsb_bank *b, const int16_t *cs_pairs, uint32_t period)
+try {
+    if (!b) return ADSB_ERR_INVALID;
+    const MixerOwner o = mixer_of(b);
     return mixer_set(o.ctx, *o.mem, *o.mix, cs_pairs, period);
 } ADSB_ABI_CATCH
 

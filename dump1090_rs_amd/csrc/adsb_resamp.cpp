@@ -5,7 +5,7 @@
 #include <cmath>
 #include <numeric>
 
-#include "adsb_ctx.h"
+#include "adsb_resamp_host.h"
 
 using namespace adsb::host;
 
@@ -37,36 +37,9 @@ float *scale_of(adsb_resamp *r) { return &r->scale; }
 
 namespace {
 
-typedef unsigned __int128 u128;
-
-inline bool ratio_ok(uint64_t up, uint64_t down)
-{
-    return up >= 1 && up <= kResampMaxRatio && down >= 1 && down <= kResampMaxRatio && std::gcd(up, down) == 1 &&
-           up <= 2 * down && down <= 16 * up;
-}
-
-// ceil(a L / M)
-inline uint64_t ceil_mul_div(uint64_t a, uint32_t L, uint32_t M) { return (uint64_t)(((u128)a * L + (M - 1)) / M); }
-// outputs of a call of n_in inputs behind P consumed ones: the n with P <= floor(n M / L) < P + n_in
-inline void plan(uint32_t L, uint32_t M, uint64_t P, uint64_t n_in, uint64_t *first_n, uint64_t *n_out)
-{
-    const uint64_t first = ceil_mul_div(P, L, M);
-    *first_n = first;
-    *n_out = (uint64_t)(((u128)P + n_in) * L / M + ((((u128)P + n_in) * L) % M != 0)) - first;
-}
-inline uint64_t out_count(const adsb_resamp *r, uint64_t n_in)
-{
-    uint64_t first, n;
-    plan(r->up, r->down, r->consumed, n_in, &first, &n);
-    return n;
-}
-// the fewest inputs behind P that produce at least `need` outputs (need >= 1): up to the newest input of output
-// first_n + need - 1
-inline uint64_t inputs_for(const adsb_resamp *r, uint64_t need)
-{
-    const uint64_t last = ceil_mul_div(r->consumed, r->up, r->down) + need - 1;
-    return (uint64_t)((u128)last * r->down / r->up) - r->consumed + 1;
-}
+// (the count arithmetic is adsb_resamp_host.h's, shared with the banks)
+inline uint64_t out_count(const adsb_resamp *r, uint64_t n_in) { return adsb::host::out_count(r->up, r->down, r->consumed, n_in); }
+inline uint64_t inputs_for(const adsb_resamp *r, uint64_t need) { return adsb::host::inputs_for(r->up, r->down, r->consumed, need); }
 
 // One call on the context's input stream: the kernels, the history's turn and P.  No wait.
 int run_on_stream(adsb_resamp *r, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t n_out)
@@ -79,21 +52,13 @@ int run_on_stream(adsb_resamp *r, int format, const void *d_in, uint64_t n_in, v
     p.n_in = n_in;
     p.hist_prev = r->d_hist[r->cur];
     p.hist_next = r->d_hist[r->cur ^ 1];
-    p.taps = r->d_taps;
     p.u8_table = format == ADSB_DECIM_8BIT ? c->d_u8_table : nullptr;
     p.format = (uint32_t)format;
     p.scale = r->scale;
     p.out = static_cast<uint32_t *>(d_out);
     p.n_out = n_out;
-    p.up = L, p.down = M, p.k_taps = r->k_taps, p.k_pad = r->k_pad, p.shift = r->shift;
-    // the first output n0 = ceil(P L / M): n0 M = P L + d with d = (-P L) mod M, so floor(n0 M / L) = P + d div L and
-    // (n0 M) mod L = d mod L
-    const uint32_t d = (uint32_t)((M - (r->consumed % M) * L % M) % M);
-    p.p0 = d % L, p.q0 = d / L;
-    p.rows = resamp_rows(L, M);
-    p.row_len = resamp_row_len(M, p.rows, r->k_taps);
-    p.recip_up = (uint32_t)(((1ull << 32) + L - 1u) / L);
-    p.recip_down = (uint32_t)(((1ull << 32) + M - 1u) / M);
+    filter_params(p, L, M, r->k_taps, r->k_pad, r->shift, r->d_taps);
+    first_output(L, M, r->consumed, &p.p0, &p.q0);
     p.mix = mixer_params(r->mix, r->consumed);
     if (int e = launch_resamp(p, c->stream)) return fail(c, (hipError_t)e, "launch_resamp");
     // (the next pass reads what this put on the context's own stream: order_behind_input)
@@ -180,14 +145,6 @@ int demod_host(adsb_resamp *r, int format, const void *host_iq, size_t n_in, ads
     return deliver(c, msgs, out, cap, n_out);
 }
 
-// the prototype's taps in polyphase order: [p][j] = h[p + j L]
-std::vector<int32_t> polyphase(const int16_t *taps, uint32_t n_taps, uint32_t L, uint32_t k_pad)
-{
-    std::vector<int32_t> out((size_t)L * k_pad, 0);
-    for (uint32_t k = 0; k < n_taps; k++) out[(size_t)(k % L) * k_pad + k / L] = taps[k];
-    return out;
-}
-
 }  // namespace
 
 extern "C" {
@@ -197,15 +154,8 @@ int adsb_resamp_create(adsb_ctx *c, uint32_t up, uint32_t down, const int16_t *t
 try {
     if (out) *out = nullptr;
     if (!c || !out || !taps) return ADSB_ERR_INVALID;
-    if (!ratio_ok(up, down) || n_taps < 1 || n_taps > kResampMaxTaps || shift > kResampMaxShift) return ADSB_ERR_INVALID;
-    const uint32_t k_taps = (n_taps + up - 1) / up;
-    if (k_taps > kResampMaxPhaseTaps) return ADSB_ERR_INVALID;
-    // (an int32 accumulator never wraps: 65534 * 32768 + 32768 < 2^31)
-    std::vector<uint32_t> abs_sum(up, 0);
-    for (uint32_t k = 0; k < n_taps; k++) abs_sum[k % up] += (uint32_t)std::abs((int)taps[k]);
-    for (uint32_t s : abs_sum)
-        if (s > 65534u) return ADSB_ERR_INVALID;
-    if (!resamp_rows(up, down)) return ADSB_ERR_INVALID;
+    uint32_t k_taps = 0;
+    if (!filter_ok(up, down, taps, n_taps, shift, &k_taps)) return ADSB_ERR_INVALID;
     ADSB_ON_DEVICE(c);
     adsb_resamp *r = new adsb_resamp;
     r->ctx = c;

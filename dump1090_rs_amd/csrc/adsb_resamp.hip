@@ -1,5 +1,7 @@
 // adsb_resamp.hip -- k_resamp: the exact-integer rational resampler in front of the scan (include/adsb_hip.h,
-// "Resampling"), and k_resamp_history, which hands the filter's history on to the next call.
+// "Resampling"), and k_resamp_history, which hands the filter's history on to the next call; k_resamp_bank and
+// k_resamp_bank_history, the same two bodies over the runs of a bank's call ("Resampler banks").  The tile's body is
+// adsb_resamp_body.inc.
 //
 //   p = (n M) mod L,  q = floor(n M / L),  y[n] = clamp((sum_j h[p + j L] x[q - j] + r) >> s), re and im separately.
 //
@@ -32,6 +34,8 @@
 // a tile is then 2112 .. 8192 outputs, up to 32 KB of staged outputs and eight passes of the final store loop, and at 32
 // rows (48 ratios, both terms near 128) half of every wave has no member.  Rows of 16 and 8 are listed and never chosen;
 // tests/test_resamp_cpu.py enumerates this.  No scratch, no spills.
+#include <algorithm>
+
 #include "../../include/adsb_hip.h"
 #include "adsb_dev_common.h"
 #include "adsb_fmt_dev.h"
@@ -65,157 +69,44 @@ __device__ __forceinline__ int round_clamp_r(int acc, uint32_t shift, int round)
 template <uint32_t FMT, bool MIX>
 __global__ __launch_bounds__(kThreadsResamp) void k_resamp(ResampParams p)
 {
-    extern __shared__ uint32_t lds[];
-    constexpr bool U8 = FMT == kIn8Bit;
-    constexpr int kBps = (int)in_bytes_per_sample(FMT);
-    constexpr int kPerLoad = 16 / kBps;    // samples per 16-byte load
-    constexpr int kBatch = 4;              // loads in flight per lane
-    const int tid = threadIdx.x;
-    const uint32_t L = p.up, M = p.down, H = p.k_taps - 1, RL = p.row_len, R = p.rows;
-    const uint32_t tile = L * R;
-    uint32_t *stage = lds + ((M * RL + 3u) & ~3u);   // the tile's outputs, then (8-bit input) the table
-    // input index (0 = the call's first sample) of the first input the tile needs, the origin of its local samples, and
-    // how many of those there are: the tile's outputs reach from its first output's newest input - H to that + R M
-    const long long i0 = (long long)p.q0 + (long long)blockIdx.x * (long long)(R * M) - (long long)H;
-    const long long a0 = (i0 - 8) & ~7ll;
-    const uint32_t e = (uint32_t)(i0 - a0);   // 8 .. 15
-    const uint32_t ltot = R * M + 1u + H + e;
-    const long long base = a0 > 0 ? a0 : 0;   // (< n_in: the tile has an output, whose newest input is i0 + H or behind)
-    const unsigned long long left = (p.n_in - (unsigned long long)base) * kBps;
-    const uint32_t bytes = (uint32_t)(left < (1ull << 30) ? ((left + 3) & ~3ull) : (1ull << 30));
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.src + base * kBps), 0, bytes, 0x00020000);
-    const int rel = (int)(a0 - base);   // <= 0: in front of the call the offsets wrap to huge unsigned ones, out of range
+#include "adsb_resamp_body.inc"
+}
 
-    uint16_t *tab = (uint16_t *)(stage + tile);
-    if constexpr (U8) {
-        tab[tid] = p.u8_table[tid];
-        __syncthreads();
-    }
-    // the table entry of local sample 0 (the tile's origin a0 = q0 + block R M - (H + e), reduced mod N)
-    uint32_t t0 = 0;
-    if constexpr (MIX) t0 = mix_tile_phase(p.mix.phase, p.q0, blockIdx.x, R * M, H + e, p.mix.period);
-    for (uint32_t lb = 0; lb < ltot; lb += (uint32_t)(kBatch * kPerLoad * kThreadsResamp)) {
-        u32x4r pre[kBatch];
-#pragma unroll
-        for (int i = 0; i < kBatch; i++) {
-            const uint32_t l = lb + (uint32_t)(kPerLoad * (tid + i * kThreadsResamp));
-            // (a load the tile does not need is sent out of range too: it returns zero and moves nothing.  Opaque: folded
-            // into the instruction's immediate, a constant would be added without wrapping)
-            int off = l < ltot ? (rel + (int)l) * kBps : -16;
-            asm volatile("" : "+v"(off));
-            pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < kBatch; i++) {
-            const uint32_t l = lb + (uint32_t)(kPerLoad * (tid + i * kThreadsResamp));
-            if (l >= ltot) continue;
-            const uint32_t w[4] = {pre[i].x, pre[i].y, pre[i].z, pre[i].w};
-            uint32_t v[kPerLoad];
-#pragma unroll
-            for (int c = 0; c < kPerLoad; c++) {
-                const long long ii = a0 + (long long)l + c;   // the sample's index in the call
-                if constexpr (U8) {
-                    const uint32_t b2 = (w[c >> 1] >> (16 * (c & 1))) & 0xFFFFu;
-                    v[c] = (ii >= 0 && ii < (long long)p.n_in) ? widen_u8_pair(tab, b2) : 0u;
-                } else if constexpr (FMT == kInReal16) {   // (the load is rounded up to a dword: the int16 behind an odd end)
-                    v[c] = (ii >= 0 && ii < (long long)p.n_in) ? fmt_halfword(w, c) : 0u;
-                } else if constexpr (FMT == kInCf32) {     // (out of range the load gave +0.0, and q(0) = 0)
-                    v[c] = fmt_cf32(w[2 * c], w[2 * c + 1], p.scale);
-                } else {
-                    v[c] = w[c];
-                }
-            }
-            if constexpr (MIX) {   // (in front of the call and behind its end the samples are zero, and stay zero)
-                uint32_t t = mix_mod(t0 + l, p.mix.period, p.mix.recip);
-#pragma unroll
-                for (int c = 0; c < kPerLoad; c++) {
-                    v[c] = mix_sample(v[c], p.mix.table[t]);
-                    if (++t == p.mix.period) t = 0;
-                }
-            }
-            if (a0 + (long long)l < 0) {   // in front of the call: the history (the first tiles only)
-#pragma unroll
-                for (int c = 0; c < kPerLoad; c++) {
-                    const long long ii = a0 + (long long)l + c;
-                    if (ii < 0 && ii >= -(long long)H) v[c] = p.hist_prev[(long long)H + ii];
-                }
-            }
-            uint32_t col = resamp_div(l, M, p.recip_down), row = l - col * M;
-#pragma unroll
-            for (int c = 0; c < kPerLoad; c++) {
-                if (l + c < ltot) lds[row * RL + col] = v[c];
-                if (++row == M) row = 0, col++;
-            }
-        }
-    }
-    __syncthreads();
+// A bank's launch (include/adsb_hip.h, "Resampler banks"): run blockIdx.y's fields replace the call's own in the launch's
+// parameters, which keep what the ratio and the filter fix.  The descriptor's index is wave-uniform and the descriptors
+// lie in the constant address space: four 16-byte scalar loads.
+static_assert(sizeof(ResampBankRun) == 64, "a descriptor is four 16-byte loads");
+__device__ __forceinline__ void bank_run_params(ResampParams &p, const ResampBankRun *runs, uint32_t run)
+{
+    typedef const u32x4r __attribute__((address_space(4))) *const_run_ptr;
+    const const_run_ptr d = (const_run_ptr)(uintptr_t)(runs + run);
+    const u32x4r a = d[0], b = d[1], c = d[2], e = d[3];
+    const auto wide = [](uint32_t lo, uint32_t hi) { return (unsigned long long)lo | (unsigned long long)hi << 32; };
+    p.src = (const void *)wide(a.x, a.y);
+    p.n_in = wide(a.z, a.w);
+    p.out = (uint32_t *)wide(b.x, b.y);
+    p.n_out = wide(b.z, b.w);
+    p.hist_prev = (const uint32_t *)wide(c.x, c.y);
+    p.hist_next = (uint32_t *)wide(c.z, c.w);
+    p.p0 = e.x, p.q0 = e.y;
+    p.mix.phase = e.z;
+}
 
-    // unit u of the tile: class u mod L, members 64 (u div L) .. + 63; the waves take the units in turn
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6), lane = (uint32_t)tid & 63u;
-    const uint32_t units = L * ((R + 63u) >> 6);
-    const int round = p.shift ? 1 << (p.shift - 1) : 0;
-    const uint32_t blocks = p.k_pad >> 3;
-    // (the constant address space: scalar loads)
-    typedef const i32x4r __attribute__((address_space(4))) *const_taps_ptr;
-    for (uint32_t u = wave; u < units; u += kWavesResamp) {
-        const uint32_t chunk = resamp_div(u, L, p.recip_up), c = u - chunk * L;
-        // the class's phase, and its first member's newest input counted from the tile's
-        const uint32_t x = p.p0 + c * M, qc = resamp_div(x, L, p.recip_up), phase = x - qc * L;
-        const uint32_t r = chunk * 64u + lane, rr = min(r, R - 1u);   // (a lane without a member reads the last one's)
-        // tap j of member r: local sample (e + H + qc - j) + r M
-        const uint32_t l0 = e + H + qc, col0 = resamp_div(l0, M, p.recip_down);
-        int ph = (int)(l0 - col0 * M);
-        uint32_t addr = (uint32_t)ph * RL + col0 + rr;
-        int acc_re = 0, acc_im = 0;
-        const const_taps_ptr taps8 = (const_taps_ptr)(uintptr_t)(p.taps + (size_t)phase * p.k_pad);
-        for (uint32_t kb = 0; kb < blocks; kb++) {
-            const i32x4r ta = taps8[2 * kb], tb = taps8[2 * kb + 1];
-            const int h[8] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w};
-#pragma unroll
-            for (int t = 0; t < 8; t++) {
-                const uint32_t s = lds[addr];
-                const uint32_t hp = (uint32_t)h[t] & 0xFFFFu;
-                acc_re = dot_half_r(s, hp, acc_re);
-                acc_im = dot_half_r(s, hp << 16, acc_im);
-                // one sample back: the row above, or from row 0 to the last row one column to the left
-                if (--ph < 0) {
-                    ph = (int)M - 1;
-                    addr += (M - 1) * RL - 1;
-                } else {
-                    addr -= RL;
-                }
-            }
-        }
-        if (r < R) {
-            const int re = round_clamp_r(acc_re, p.shift, round), im = round_clamp_r(acc_im, p.shift, round);
-            stage[c + L * r] = ((uint32_t)re & 0xFFFFu) | ((uint32_t)im << 16);
-        }
-    }
-    __syncthreads();
-
-    const unsigned long long nb = (unsigned long long)blockIdx.x * tile;
-    const unsigned long long rest = p.n_out - nb;   // (> 0: the grid has no tile without an output)
-    const uint32_t cnt = rest < tile ? (uint32_t)rest : tile;
-    uint32_t *out = p.out + nb;
-    if (((uintptr_t)p.out & 15u) == 0) {   // (tile is a multiple of four: every tile's outputs start on 16 bytes)
-        for (uint32_t i = 4u * (uint32_t)tid; i < cnt; i += 4u * kThreadsResamp) {
-            if (i + 4u <= cnt) {
-                *(u32x4r *)(out + i) = *(const u32x4r *)(stage + i);
-            } else {
-                for (uint32_t k = i; k < cnt; k++) out[k] = stage[k];
-            }
-        }
-    } else {
-        for (uint32_t i = (uint32_t)tid; i < cnt; i += kThreadsResamp) out[i] = stage[i];
-    }
+template <uint32_t FMT, bool MIX>
+__global__ __launch_bounds__(kThreadsResamp) void k_resamp_bank(ResampParams common, const ResampBankRun *runs)
+{
+    ResampParams p = common;
+    bank_run_params(p, runs, blockIdx.y);
+    // the grid is as wide as the call's longest run: a tile past this run's last output has nothing to do
+    if ((unsigned long long)blockIdx.x * (p.up * p.rows) >= p.n_out) return;
+#include "adsb_resamp_body.inc"
 }
 
 // the last H = K - 1 inputs of the stream so far, widened: from the call's input, or from the previous history where
 // the call was shorter than the history (k_decim_history's rule).  MIX: what comes from the call's input is mixed, what
 // comes from the previous history is mixed already.
 template <uint32_t FMT, bool MIX>
-__global__ __launch_bounds__(512) void k_resamp_history(ResampParams p)
+__device__ __forceinline__ void resamp_history(const ResampParams &p)
 {
     constexpr bool U8 = FMT == kIn8Bit;
     const long long H = (long long)p.k_taps - 1, i = threadIdx.x, n = (long long)p.n_in;
@@ -239,6 +130,47 @@ __global__ __launch_bounds__(512) void k_resamp_history(ResampParams p)
         if constexpr (MIX) v = mix_sample(v, p.mix.table[((unsigned long long)idx + p.mix.phase) % p.mix.period]);
     }
     p.hist_next[i] = v;
+}
+
+template <uint32_t FMT, bool MIX>
+__global__ __launch_bounds__(512) void k_resamp_history(ResampParams p)
+{
+    resamp_history<FMT, MIX>(p);
+}
+
+// ... and of every run of a bank's call: workgroup r follows the same rule for run r
+template <uint32_t FMT, bool MIX>
+__global__ __launch_bounds__(512) void k_resamp_bank_history(ResampParams common, const ResampBankRun *runs)
+{
+    ResampParams p = common;
+    bank_run_params(p, runs, blockIdx.x);
+    resamp_history<FMT, MIX>(p);
+}
+
+// what the ratio and the filter fix, a call's own fields aside
+bool resamp_common_ok(const ResampParams &p)
+{
+    if (p.up < 1 || p.up > kResampMaxRatio || p.down < 1 || p.down > kResampMaxRatio || p.k_taps < 1 ||
+        p.k_taps > kResampMaxPhaseTaps || p.k_pad != ((p.k_taps + 7u) & ~7u) || p.shift > kResampMaxShift || !p.rows ||
+        p.rows != resamp_rows(p.up, p.down) || p.row_len != resamp_row_len(p.down, p.rows, p.k_taps) ||
+        p.recip_up != (uint32_t)(((1ull << 32) + p.up - 1u) / p.up) || p.recip_down != (uint32_t)(((1ull << 32) + p.down - 1u) / p.down) ||
+        !p.taps)
+        return false;
+    if (!mix_params_ok(p.mix) || !in_format_ok(p.format, p.u8_table, p.scale)) return false;
+    return resamp_lds_words(p.up, p.down, p.rows, p.k_taps) <= kResampLdsWords;
+}
+
+// ... and a call's own (p.up, p.down and p.rows checked): its tile count in *blocks
+bool resamp_call_ok(const ResampParams &p, unsigned long long *blocks)
+{
+    if (p.p0 >= p.up || p.q0 >= p.down || !p.src || !p.n_in || !p.hist_prev || !p.hist_next) return false;
+    // the call's first output has its newest input inside the call (then every tile's first output has)
+    if (p.n_out && (!p.out || ((uintptr_t)p.out & 3u) || p.q0 >= p.n_in)) return false;
+    const uint64_t tile = (uint64_t)p.up * p.rows;
+    *blocks = (p.n_out + tile - 1) / tile;
+    if (*blocks > 0x7FFFFFFFull) return false;
+    // ... and so has its last: floor((p0 + (n_out - 1) M) / L) + q0 < n_in  (n_out < 2^31 tiles of 2^13 at most: 64 bits do)
+    return !(p.n_out && ((p.n_out - 1) * p.down + p.p0) / p.up + p.q0 >= p.n_in);
 }
 
 }  // namespace
@@ -271,40 +203,56 @@ uint32_t resamp_rows(uint32_t up, uint32_t down)
     return 0;
 }
 
+// the instantiation of a kernel family for a format and a mixer
+#define RESAMP_PICK(K, format, mix)                                                                  \
+    ((format) == kInCf32     ? ((mix) ? K<kInCf32, true> : K<kInCf32, false>)                         \
+     : (format) == kInReal16 ? ((mix) ? K<kInReal16, true> : K<kInReal16, false>)                     \
+     : (format) == kIn8Bit   ? ((mix) ? K<kIn8Bit, true> : K<kIn8Bit, false>)                         \
+                             : ((mix) ? K<kInCs16, true> : K<kInCs16, false>))
+
 int launch_resamp(const ResampParams &p, void *stream)
 {
-    if (p.up < 1 || p.up > kResampMaxRatio || p.down < 1 || p.down > kResampMaxRatio || p.k_taps < 1 ||
-        p.k_taps > kResampMaxPhaseTaps || p.k_pad != ((p.k_taps + 7u) & ~7u) || p.shift > kResampMaxShift || p.p0 >= p.up ||
-        p.q0 >= p.down || !p.rows || p.rows != resamp_rows(p.up, p.down) || p.row_len != resamp_row_len(p.down, p.rows, p.k_taps) ||
-        p.recip_up != (uint32_t)(((1ull << 32) + p.up - 1u) / p.up) || p.recip_down != (uint32_t)(((1ull << 32) + p.down - 1u) / p.down) ||
-        !p.src || !p.n_in || !p.hist_prev || !p.hist_next || !p.taps)
-        return (int)hipErrorInvalidValue;
-    if (!mix_params_ok(p.mix) || !in_format_ok(p.format, p.u8_table, p.scale)) return (int)hipErrorInvalidValue;
-    const uint32_t lds_words = resamp_lds_words(p.up, p.down, p.rows, p.k_taps);
-    if (lds_words > kResampLdsWords) return (int)hipErrorInvalidValue;
-    // the call's first output has its newest input inside the call (then every tile's first output has)
-    if (p.n_out && (!p.out || ((uintptr_t)p.out & 3u) || p.q0 >= p.n_in)) return (int)hipErrorInvalidValue;
-    const uint64_t tile = (uint64_t)p.up * p.rows;
-    const unsigned long long blocks = (p.n_out + tile - 1) / tile;
-    if (blocks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-    // ... and so has its last: floor((p0 + (n_out - 1) M) / L) + q0 < n_in  (n_out < 2^31 tiles of 2^13 at most: 64 bits do)
-    if (p.n_out && ((p.n_out - 1) * p.down + p.p0) / p.up + p.q0 >= p.n_in) return (int)hipErrorInvalidValue;
-    const bool u8 = p.format == kIn8Bit, mix = p.mix.period != 0;
+    unsigned long long blocks = 0;
+    if (!resamp_common_ok(p) || !resamp_call_ok(p, &blocks)) return (int)hipErrorInvalidValue;
+    const bool mix = p.mix.period != 0;
     if (blocks) {
-        const size_t lds_bytes = (size_t)lds_words * 4u;
-        const auto kernel = p.format == kInCf32    ? (mix ? k_resamp<kInCf32, true> : k_resamp<kInCf32, false>)
-                            : p.format == kInReal16 ? (mix ? k_resamp<kInReal16, true> : k_resamp<kInReal16, false>)
-                            : u8                    ? (mix ? k_resamp<kIn8Bit, true> : k_resamp<kIn8Bit, false>)
-                                                    : (mix ? k_resamp<kInCs16, true> : k_resamp<kInCs16, false>);
+        const size_t lds_bytes = (size_t)resamp_lds_words(p.up, p.down, p.rows, p.k_taps) * 4u;
+        const auto kernel = RESAMP_PICK(k_resamp, p.format, mix);
         hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kThreadsResamp), lds_bytes, (hipStream_t)stream, p);
         if (hipError_t e = hipGetLastError()) return (int)e;
     }
     if (p.k_taps > 1) {
-        const auto kernel = p.format == kInCf32    ? (mix ? k_resamp_history<kInCf32, true> : k_resamp_history<kInCf32, false>)
-                            : p.format == kInReal16 ? (mix ? k_resamp_history<kInReal16, true> : k_resamp_history<kInReal16, false>)
-                            : u8                    ? (mix ? k_resamp_history<kIn8Bit, true> : k_resamp_history<kIn8Bit, false>)
-                                                    : (mix ? k_resamp_history<kInCs16, true> : k_resamp_history<kInCs16, false>);
+        const auto kernel = RESAMP_PICK(k_resamp_history, p.format, mix);
         hipLaunchKernelGGL(kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, p);
+    }
+    return (int)hipGetLastError();
+}
+
+int launch_resamp_bank(const ResampParams &common, const ResampBankRun *runs, const ResampBankRun *d_runs, uint32_t n_runs,
+                       void *stream)
+{
+    if (!resamp_common_ok(common) || !runs || !d_runs || n_runs < 1 || n_runs > kResampBankMaxRuns) return (int)hipErrorInvalidValue;
+    // every run as the launch_resamp of a handle would check it, and the widest of them
+    unsigned long long widest = 0;
+    for (uint32_t r = 0; r < n_runs; r++) {
+        ResampParams p = common;
+        const ResampBankRun &d = runs[r];
+        p.src = d.src, p.n_in = d.n_in, p.out = d.out, p.n_out = d.n_out, p.hist_prev = d.hist_prev, p.hist_next = d.hist_next;
+        p.p0 = d.p0, p.q0 = d.q0, p.mix.phase = d.mix_phase;
+        unsigned long long blocks = 0;
+        if (!resamp_call_ok(p, &blocks) || (common.mix.period && d.mix_phase >= common.mix.period)) return (int)hipErrorInvalidValue;
+        widest = std::max(widest, blocks);
+    }
+    const bool mix = common.mix.period != 0;
+    if (widest) {
+        const size_t lds_bytes = (size_t)resamp_lds_words(common.up, common.down, common.rows, common.k_taps) * 4u;
+        const auto kernel = RESAMP_PICK(k_resamp_bank, common.format, mix);
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)widest, n_runs), dim3(kThreadsResamp), lds_bytes, (hipStream_t)stream, common, d_runs);
+        if (hipError_t e = hipGetLastError()) return (int)e;
+    }
+    if (common.k_taps > 1) {
+        const auto kernel = RESAMP_PICK(k_resamp_bank_history, common.format, mix);
+        hipLaunchKernelGGL(kernel, dim3(n_runs), dim3(512), 0, (hipStream_t)stream, common, d_runs);
     }
     return (int)hipGetLastError();
 }

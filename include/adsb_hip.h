@@ -786,6 +786,81 @@ ADSB_MUST_CHECK int adsb_fmt_set_scale_resamp(adsb_resamp *r, float scale);
 extern float adsb_fmt_get_scale_decim(const adsb_decim *d);
 extern float adsb_fmt_get_scale_resamp(const adsb_resamp *r);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Resampler banks -- many resampler streams in one launch.  A pass of many receivers ("Many receivers, one pass") takes
+ * one full 2.4 MS/s buffer per receiver, all in one device allocation.  Where the receivers' radios run at another rate
+ * each needs a resampler, and R adsb_resamp handles are R calls of two launches each, one behind the other, every grid a
+ * fraction of the device.  An adsb_bank is N independent streams of one ratio and one filter that ONE call advances by
+ * one launch of the resampling kernel (and one of the history kernel), whatever N.
+ *
+ * Definition.  A bank is N streams, 1 <= N <= ADSB_MAX_RECEIVERS, that share (up, down, taps, n_taps, shift) -- with
+ * exactly the limits of adsb_resamp_create -- one mixer table (off by default) and one CF32 scale (32768 by default).
+ * Stream i of a bank is, bit for bit and count for count, an adsb_resamp that was created with those arguments, was
+ * given that mixer table and scale, and was fed the calls that named stream i, in order.  Each stream has its own P
+ * (inputs consumed) and its own K - 1 inputs of history; the mixer is applied by the stream's own P; the output phase is
+ * the stream's own.  A call that does not name a stream leaves it untouched.  Nothing else is new: "Resampling",
+ * "Frequency shift" and "Sample formats" are the specification.
+ *
+ *   adsb_bank_create      a bank on the context's device.  Destroy it before the context.  Device memory: two histories
+ *                         of 2 KB per stream, and four blocks of 64 bytes per stream for the calls' descriptors.
+ *   adsb_bank_destroy     waits for what the bank put on the stream, then frees it
+ *   adsb_bank_streams     N; 0 for NULL
+ *   adsb_bank_reset       stream i, or every stream with ADSB_BANK_ALL, starts over (P = 0, zero history); ordered on
+ *                         the stream like a run
+ *   adsb_bank_consumed    host only: the stream's P
+ *   adsb_bank_out_count   host only: how many outputs the stream's next run of n_in inputs would produce
+ *   adsb_bank_inputs_for  host only: the fewest inputs behind the stream's P that give at least n_out_wanted outputs, in
+ *                         *n_in, and how many they give, in *n_out_made: n_out_wanted, or one more where L > M (two
+ *                         consecutive outputs can share their newest input).  0 wanted: 0 and 0.  This is how a caller
+ *                         cuts each receiver's input so that its run fills exactly one 131072-sample buffer.
+ *   adsb_bank_run_device  one `format` for the call (ADSB_DECIM_CS16, _8BIT, _CF32 or _REAL16; 8-bit through the
+ *                         context's table); run r advances streams[r] by n_in[r] inputs from device_in[r] and writes
+ *                         n_out[r] CS16 samples to device_out_cs16[r] -- normally the 131072-sample slots of the one
+ *                         allocation the _rx pass then takes.  Device memory to device memory, every pointer 16-byte
+ *                         aligned, nothing overlapping.  Enqueues on the stream the context orders its input behind, as
+ *                         adsb_resamp_run_device does, and returns without waiting; every n_out[r] is known at once; the
+ *                         next pass submitted on the context waits for it.  The arrays are read during the call.
+ *                         ADSB_ERR_INVALID -- nothing is enqueued and no stream changes -- for a NULL handle or array, a
+ *                         bad format, n_runs > N, streams[r] >= N, a stream named twice in one call, a pointer that is
+ *                         not 16-byte aligned, a NULL input with n_in[r] > 0 and a NULL output with n_out[r] > 0.
+ *                         ADSB_ERR_CAPACITY if any n_out[r] > out_cap[r]: every n_out[r] is still written and no stream
+ *                         of the call consumes anything.  A run of no input does nothing, and so does a call of no
+ *                         runs.  Never ADSB_ERR_BUSY.  A call's descriptors travel through one of
+ *                         adsb_bank_selftest_depth() blocks used in rotation, each guarded by an event behind the launch
+ *                         that reads it: a call that finds its block still in flight waits for that launch; it does not
+ *                         fail.
+ *   adsb_bank_set_mixer   adsb_mix_set_resamp's rules, for the one table every stream shares (each at its own phase)
+ *   adsb_bank_get_mixer   the period; 0 when the mixer is off
+ *   adsb_bank_set_scale   adsb_fmt_set_scale_resamp's rules
+ *   adsb_bank_get_scale   g; 0 for NULL
+ * Cost of uneven runs.  The launch's grid is (tiles of the call's LONGEST run) x (runs with input): a workgroup whose
+ * tile lies past its own run's last output returns at once, but it is still scheduled.  A call whose runs are about
+ * equal -- one buffer per receiver, the expected use -- wastes nothing; a call of one long and many short runs launches
+ * mostly empty workgroups and is better split in two.  A bank with L = 1 covers integer decimation.
+ * Not here: a blocking host-pointer *_demod_iq form for banks; per-stream ratios, taps or mixer tables (use one bank per
+ * ratio); banks in adsb_feed or adsb_multi; a bank form of adsb_decim.
+ * After a HIP failure the bank's state is undefined until adsb_bank_reset(bank, ADSB_BANK_ALL). */
+typedef struct adsb_bank adsb_bank;
+#define ADSB_BANK_ALL 0xFFFFFFFFu
+ADSB_MUST_CHECK int adsb_bank_create(adsb_ctx *ctx, uint32_t n_streams, uint32_t up, uint32_t down, const int16_t *taps,
+                                     uint32_t n_taps, uint32_t shift, adsb_bank **out);
+extern void adsb_bank_destroy(adsb_bank *b);
+extern uint32_t adsb_bank_streams(const adsb_bank *b);
+ADSB_MUST_CHECK int adsb_bank_reset(adsb_bank *b, uint32_t stream);
+ADSB_MUST_CHECK int adsb_bank_consumed(const adsb_bank *b, uint32_t stream, uint64_t *consumed);
+ADSB_MUST_CHECK int adsb_bank_out_count(const adsb_bank *b, uint32_t stream, size_t n_in, size_t *n_out);
+ADSB_MUST_CHECK int adsb_bank_inputs_for(const adsb_bank *b, uint32_t stream, size_t n_out_wanted, size_t *n_in,
+                                         size_t *n_out_made);
+ADSB_MUST_CHECK int adsb_bank_run_device(adsb_bank *b, int format, uint32_t n_runs, const uint32_t *streams,
+                                         const void *const *device_in, const size_t *n_in, void *const *device_out_cs16,
+                                         const size_t *out_cap, size_t *n_out);
+ADSB_MUST_CHECK int adsb_bank_set_mixer(adsb_bank *b, const int16_t *cs_pairs, uint32_t period);
+extern uint32_t adsb_bank_get_mixer(const adsb_bank *b);
+ADSB_MUST_CHECK int adsb_bank_set_scale(adsb_bank *b, float scale);
+extern float adsb_bank_get_scale(const adsb_bank *b);
+/* Host only, for the tests: the number of descriptor blocks a bank rotates through. */
+extern uint32_t adsb_bank_selftest_depth(void);
+
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167
  * is one stream with one process-global filter, src/icao_filter.rs:8-9).  Shards run

@@ -142,6 +142,14 @@ pub const ADSB_RESAMP_8BIT: i32 = ADSB_DECIM_8BIT;
 pub const ADSB_RESAMP_CF32: i32 = ADSB_DECIM_CF32;
 pub const ADSB_RESAMP_REAL16: i32 = ADSB_DECIM_REAL16;
 
+/// Many resampler streams of one ratio and one filter, advanced by one launch (`adsb_bank_*`).
+#[repr(C)]
+pub struct AdsbBank {
+    _private: [u8; 0],
+}
+
+pub const ADSB_BANK_ALL: u32 = 0xFFFF_FFFF;
+
 /// One capture over several GPUs from one process: one handle, one filter (`adsb_multi_*`).
 #[repr(C)]
 pub struct AdsbMulti {
@@ -295,6 +303,25 @@ unsafe extern "C" {
     pub fn adsb_resamp_default_taps(up: u32, down: u32, taps: *mut i16, cap: usize, n_taps: *mut u32, shift: *mut u32) -> c_int;
     pub fn adsb_resamp_ratio_for_rate(rate_hz: u32, up: *mut u32, down: *mut u32) -> c_int;
     pub fn adsb_resamp_plan(up: u32, down: u32, consumed: u64, n_in: u64, first_n: *mut u64, n_out: *mut u64) -> c_int;
+}
+
+// A bank of resampler streams advanced by one launch (include/adsb_hip.h, "Resampler banks"; the header marks the calls
+// ADSB_MUST_CHECK or `extern`); compared with the header by tests/test_bank_cpu.py.
+#[link(name = "adsb_hip")]
+unsafe extern "C" {
+    pub fn adsb_bank_create(ctx: *mut AdsbCtx, n_streams: u32, up: u32, down: u32, taps: *const i16, n_taps: u32, shift: u32, out: *mut *mut AdsbBank) -> c_int;
+    pub fn adsb_bank_destroy(b: *mut AdsbBank);
+    pub fn adsb_bank_streams(b: *const AdsbBank) -> u32;
+    pub fn adsb_bank_reset(b: *mut AdsbBank, stream: u32) -> c_int;
+    pub fn adsb_bank_consumed(b: *const AdsbBank, stream: u32, consumed: *mut u64) -> c_int;
+    pub fn adsb_bank_out_count(b: *const AdsbBank, stream: u32, n_in: usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_bank_inputs_for(b: *const AdsbBank, stream: u32, n_out_wanted: usize, n_in: *mut usize, n_out_made: *mut usize) -> c_int;
+    pub fn adsb_bank_run_device(b: *mut AdsbBank, format: c_int, n_runs: u32, streams: *const u32, device_in: *const *const c_void, n_in: *const usize, device_out_cs16: *const *mut c_void, out_cap: *const usize, n_out: *mut usize) -> c_int;
+    pub fn adsb_bank_set_mixer(b: *mut AdsbBank, cs_pairs: *const i16, period: u32) -> c_int;
+    pub fn adsb_bank_get_mixer(b: *const AdsbBank) -> u32;
+    pub fn adsb_bank_set_scale(b: *mut AdsbBank, scale: f32) -> c_int;
+    pub fn adsb_bank_get_scale(b: *const AdsbBank) -> f32;
+    pub fn adsb_bank_selftest_depth() -> u32;
 }
 
 // The mixer of a decimator or resampler, for offset-tuned IQ (include/adsb_hip.h, "Frequency shift").
