@@ -24,6 +24,7 @@ from .context import (  # noqa: F401
     ratio_for_rate,
     mixer_table,
     mixer_for_shift,
+    input_summary,
     MagnitudeBuffer,
     ModeSMessage,
     replay_records_rx,
@@ -35,7 +36,7 @@ from . import demod_2400, icao_filter, utils  # noqa: F401
 __all__ = [
     "MODES_MAG_BUF_SAMPLES", "MODES_LONG_MSG_BYTES", "MODES_SHORT_MSG_BYTES", "TRAILING_SAMPLES",
     "MagnitudeBuffer", "ModeSMessage", "Context", "default_context", "Decimator", "default_taps",
-    "Resampler", "ResamplerBank", "default_resampler_taps", "ratio_for_rate", "mixer_table", "mixer_for_shift",
+    "Resampler", "ResamplerBank", "default_resampler_taps", "ratio_for_rate", "mixer_table", "mixer_for_shift", "input_summary",
     "ADSB_DECIM_CS16", "ADSB_DECIM_8BIT", "ADSB_DECIM_CF32", "ADSB_DECIM_REAL16",
     "utils", "demod_2400", "icao_filter",
 ]

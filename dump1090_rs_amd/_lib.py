@@ -117,6 +117,44 @@ class AdsbSignalSummary(C.Structure):
     ]
 
 
+ADSB_INPUT_BINS = 17
+
+
+class AdsbInputStats(C.Structure):
+    """adsb_input_stats (include/adsb_hip.h, "Input statistics"): the integer record of a set of raw input samples of a
+    decimator, a resampler or one stream of a bank.  208 bytes."""
+    _fields_ = [
+        ("n_samples", C.c_uint64),
+        ("sum_re", C.c_int64),
+        ("sum_im", C.c_int64),
+        ("sum_re2", C.c_uint64),
+        ("sum_im2", C.c_uint64),
+        ("sum_re_im", C.c_int64),
+        ("n_clipped", C.c_uint64),
+        ("n_nan", C.c_uint64),
+        ("hist", C.c_uint64 * ADSB_INPUT_BINS),
+        ("peak", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class AdsbInputSummary(C.Structure):
+    """adsb_input_summary_t: what adsb_input_summary makes of any number of records."""
+    _fields_ = [
+        ("n_records", C.c_uint64),
+        ("n_samples", C.c_uint64),
+        ("mean_power_dbfs", C.c_double),
+        ("peak_dbfs", C.c_double),
+        ("dc_re", C.c_double),
+        ("dc_im", C.c_double),
+        ("clipped_fraction", C.c_double),
+        ("nan_fraction", C.c_double),
+        ("iq_gain_db", C.c_double),
+        ("bits_used", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class AdsbError(RuntimeError):
     def __init__(self, status: int, what: str, detail: str = ""):
         self.status = status
@@ -365,6 +403,22 @@ def lib() -> C.CDLL:
     for name in ("adsb_bank_create", "adsb_bank_reset", "adsb_bank_consumed", "adsb_bank_out_count", "adsb_bank_inputs_for",
                  "adsb_bank_run_device", "adsb_bank_set_mixer", "adsb_bank_set_scale"):
         getattr(L, name).restype = C.c_int
+    # input statistics (include/adsb_hip.h)
+    stp = C.POINTER(AdsbInputStats)
+    for kind in ("decim", "resamp", "bank"):
+        getattr(L, f"adsb_instat_set_{kind}").argtypes = [vp, C.c_int]
+        getattr(L, f"adsb_instat_get_{kind}").argtypes = [vp]
+        getattr(L, f"adsb_instat_fetch_{kind}").argtypes = [vp, u32, u32, stp] if kind == "bank" else [vp, stp]
+        getattr(L, f"adsb_instat_selftest_launches_{kind}").argtypes = [vp]
+        getattr(L, f"adsb_instat_selftest_launches_{kind}").restype = u64
+        for call in ("set", "get", "fetch"):
+            getattr(L, f"adsb_instat_{call}_{kind}").restype = C.c_int
+    L.adsb_input_bin.argtypes = [C.c_int16]
+    L.adsb_input_bin.restype = C.c_int
+    L.adsb_input_summary.argtypes = [stp, sz, C.POINTER(AdsbInputSummary)]
+    L.adsb_input_summary.restype = C.c_int
+    L.adsb_instat_selftest_geometry.argtypes = [C.c_int, u32p, u32p]
+    L.adsb_instat_selftest_geometry.restype = C.c_int
     L.adsb_host_replays.argtypes = [vp]
     L.adsb_host_replays.restype = C.c_uint64
     L.adsb_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]

@@ -153,6 +153,39 @@ def signal_summary(records: np.ndarray) -> dict:
     return {name: getattr(out, name) for name, _ in _lib.AdsbSignalSummary._fields_}
 
 
+# adsb_input_stats as a numpy record (208 bytes)
+INPUT_STATS_DTYPE = np.dtype([("n_samples", "<u8"), ("sum_re", "<i8"), ("sum_im", "<i8"), ("sum_re2", "<u8"), ("sum_im2", "<u8"),
+                              ("sum_re_im", "<i8"), ("n_clipped", "<u8"), ("n_nan", "<u8"), ("hist", "<u8", (_lib.ADSB_INPUT_BINS,)),
+                              ("peak", "<u4"), ("reserved", "<u4")])
+assert INPUT_STATS_DTYPE.itemsize == C.sizeof(_lib.AdsbInputStats) == 208
+
+
+def input_summary(records: np.ndarray) -> dict:
+    """adsb_input_summary over any number of input records (host only): mean power and peak in dBFS, the DC offset in
+    LSB, the clipped and NaN fractions, the I/Q gain balance in dB and the bits in use."""
+    rec = np.ascontiguousarray(records, dtype=INPUT_STATS_DTYPE).reshape(-1)
+    out = _lib.AdsbInputSummary()
+    ptr = rec.ctypes.data_as(C.POINTER(_lib.AdsbInputStats)) if rec.size else None
+    st = _lib.lib().adsb_input_summary(ptr, rec.size, C.byref(out))
+    if st != _lib.ADSB_OK:
+        raise AdsbError(st, "adsb_input_summary")
+    return {name: getattr(out, name) for name, _ in _lib.AdsbInputSummary._fields_ if name != "reserved"}
+
+
+def _set_input_stats(handle, kind: str, enabled: bool) -> None:
+    call = getattr(handle._L, f"adsb_instat_set_{kind}")
+    handle._check(call(handle._h, 1 if enabled else 0), f"adsb_instat_set_{kind}")
+
+
+def _input_stats(handle, kind: str, first: Optional[int] = None, n: Optional[int] = None) -> np.ndarray:
+    out = np.zeros(1 if n is None else int(n), dtype=INPUT_STATS_DTYPE)
+    ptr = out.ctypes.data_as(C.POINTER(_lib.AdsbInputStats))
+    call = getattr(handle._L, f"adsb_instat_fetch_{kind}")
+    st = call(handle._h, ptr) if first is None else call(handle._h, int(first), int(n), ptr)
+    handle._check(st, f"adsb_instat_fetch_{kind}")
+    return out
+
+
 def replay_records(records: np.ndarray, filter_table: Optional[np.ndarray] = None, cap: Optional[int] = None,
                    mode: int = 0) -> List["ModeSMessage"]:
     """adsb_replay_records: the ordered host replay (scoring + best-of-5 + ICAO filter) over raw
@@ -796,6 +829,20 @@ class Decimator:
     def scale(self) -> float:
         return float(self._L.adsb_fmt_get_scale_decim(self._h))
 
+    def set_input_stats(self, enabled: bool) -> None:
+        """adsb_instat_set_decim: opt-in; every input sample the decimator consumes from now on is counted on the device, raw,
+        in front of the filter (input_stats()).  Disabling discards what was counted."""
+        _set_input_stats(self, "decim", enabled)
+
+    @property
+    def input_stats_enabled(self) -> bool:
+        return int(self._L.adsb_instat_get_decim(self._h)) == 1
+
+    def input_stats(self) -> np.ndarray:
+        """adsb_instat_fetch_decim: waits for the handle's calls, then returns the record of the inputs consumed since the
+        previous fetch (or the enable) as a 0-d structured array with the layout of adsb_input_stats, and zeroes it."""
+        return _input_stats(self, "decim")[0]
+
     def out_count(self, n_in: int) -> int:
         n = C.c_size_t()
         self._check(self._L.adsb_decim_out_count(self._h, int(n_in), C.byref(n)), "adsb_decim_out_count")
@@ -912,6 +959,20 @@ class Resampler:
     @property
     def scale(self) -> float:
         return float(self._L.adsb_fmt_get_scale_resamp(self._h))
+
+    def set_input_stats(self, enabled: bool) -> None:
+        """adsb_instat_set_resamp: opt-in; every input sample the resampler consumes from now on is counted on the device, raw,
+        in front of the filter (input_stats()).  Disabling discards what was counted."""
+        _set_input_stats(self, "resamp", enabled)
+
+    @property
+    def input_stats_enabled(self) -> bool:
+        return int(self._L.adsb_instat_get_resamp(self._h)) == 1
+
+    def input_stats(self) -> np.ndarray:
+        """adsb_instat_fetch_resamp: waits for the handle's calls, then returns the record of the inputs consumed since the
+        previous fetch (or the enable) as a 0-d structured array with the layout of adsb_input_stats, and zeroes it."""
+        return _input_stats(self, "resamp")[0]
 
     def out_count(self, n_in: int) -> int:
         n = C.c_size_t()
@@ -1047,6 +1108,21 @@ class ResamplerBank:
     @property
     def scale(self) -> float:
         return float(self._L.adsb_bank_get_scale(self._h))
+
+    def set_input_stats(self, enabled: bool) -> None:
+        """adsb_instat_set_bank: opt-in; every input sample any stream of the bank consumes from now on is counted on the device, raw,
+        in front of the filter (input_stats()).  Disabling discards what was counted."""
+        _set_input_stats(self, "bank", enabled)
+
+    @property
+    def input_stats_enabled(self) -> bool:
+        return int(self._L.adsb_instat_get_bank(self._h)) == 1
+
+    def input_stats(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """adsb_instat_fetch_bank: waits for the bank's calls, then returns the records of streams first .. first + n - 1
+        (n = None: up to the last) over the inputs each consumed since its previous fetch (or the enable), as a structured
+        array with the layout of adsb_input_stats, and zeroes exactly those."""
+        return _input_stats(self, "bank", first, self.streams - int(first) if n is None else n)
 
 
 _default: Optional[Context] = None

@@ -29,6 +29,7 @@ struct adsb_bank {
     uint32_t next_block = 0;
     Mixer mix;
     float scale = kInDefaultScale;
+    InStat instat;   // input statistics (adsb_instat.cpp), a record per stream: off unless asked for
     Registry mem;   // owns all of the above that the runtime reserved
 };
 
@@ -36,6 +37,7 @@ namespace adsb {
 namespace host {
 MixerOwner mixer_of(adsb_bank *b) { return {b->ctx, &b->mem, &b->mix}; }
 float *scale_of(adsb_bank *b) { return &b->scale; }
+InStatOwner instat_of(adsb_bank *b) { return {b->ctx, &b->mem, &b->instat, b->n_streams}; }
 }  // namespace host
 }  // namespace adsb
 
@@ -77,10 +79,14 @@ int run_on_stream(adsb_bank *b, int format, uint32_t n_runs, const uint32_t *str
         d.hist_next = hist_of(b, s, b->cur[s] ^ 1);
         first_output(L, M, b->consumed[s], &d.p0, &d.q0);
         d.mix_phase = b->mix.period ? (uint32_t)(b->consumed[s] % b->mix.period) : 0u;
+        d.reserved = s;   // (k_instat_bank's: the stream whose record the run counts into; k_resamp_bank does not read it)
     }
     if (!n) return ADSB_OK;
     HIP_TRY(c, hipMemcpyAsync(blk.d, blk.h, (size_t)n * sizeof(ResampBankRun), hipMemcpyHostToDevice, c->stream));
     if (c->stream == c->own_stream) c->own_stream_dirty = true;
+    // (the raw inputs counted first, from the same descriptors: the block's event below stays behind both launches)
+    if (b->instat.on)
+        if (int rc = b->instat.count_bank(c, b->instat, b->n_streams, format, b->scale, blk.h, blk.d, n)) return rc;
     if (int e = launch_resamp_bank(p, blk.h, blk.d, n, c->stream)) return fail(c, (hipError_t)e, "launch_resamp_bank");
     HIP_TRY(c, hipEventRecord(blk.read, c->stream));
     blk.in_flight = true;

@@ -11,6 +11,7 @@
 //   adsb_resamp.cpp    the L/M resampler in front of the scan: its handle, counts, staging, default taps and ratios
 //   adsb_bank.cpp      a bank of resampler streams advanced by one launch: its handle, per-stream state and descriptors
 //   adsb_mix.cpp       the mixer of a decimator or resampler: its table on the device, the table and shift helpers
+//   adsb_instat.cpp    the input statistics of a decimator, resampler or bank: the mode, the launch, the fetch, the summary
 //   adsb_shard.cpp     the two-phase shard calls
 //   adsb_selftest.cpp  stage lists and digests for the tests
 #pragma once
@@ -565,6 +566,32 @@ float *scale_of(adsb_decim *d);
 float *scale_of(adsb_resamp *r);
 float *scale_of(adsb_bank *b);
 inline bool format_ok(int format) { return format >= 0 && format < (int)kInFormats; }
+// A decimator's, resampler's or bank's input statistics (include/adsb_hip.h, "Input statistics"; adsb_instat.cpp): the
+// mode, the accumulator -- one record per stream in device memory, with as much pinned memory for the fetch, both
+// reserved in the handle's registry by the first enable -- and the launches made so far.  instat_of is how adsb_instat.cpp
+// reaches a handle's (each handle's unit defines its own).  A handle whose mode is off pays one test of `on` per call.
+// What a handle's run path calls in front of its filter launch while the mode is on -- `count`: one call's input into the
+// record; `count_bank`: a bank's call, from its descriptors, filled (`reserved` = the stream) and already on their way to
+// the device -- is installed by the enable: a handle's unit refers to nothing of adsb_instat.cpp or adsb_instat.hip, and
+// links without them.
+struct InStat {
+    bool on = false;
+    unsigned long long *d_acc = nullptr;
+    adsb_input_stats *h_acc = nullptr;
+    uint64_t launches = 0;
+    int (*count)(adsb_ctx *c, InStat &st, int format, float scale, const void *d_in, uint64_t n_in) = nullptr;
+    int (*count_bank)(adsb_ctx *c, InStat &st, uint32_t n_streams, int format, float scale, const ResampBankRun *runs,
+                      const ResampBankRun *d_runs, uint32_t n_runs) = nullptr;
+};
+struct InStatOwner {
+    adsb_ctx *ctx;
+    Registry *mem;
+    InStat *st;
+    uint32_t n_streams;
+};
+InStatOwner instat_of(adsb_decim *d);
+InStatOwner instat_of(adsb_resamp *r);
+InStatOwner instat_of(adsb_bank *b);
 // T_soapy: the table SoapyRTLSDR widens an RTL-SDR's bytes with, (int16_t)(((float)x - 127.4f) * (1.0f / 128.0f) * 32767.0f)
 void soapy_u8_table(int16_t *out256);
 // IQ staging for host-pointer calls, in device memory / pinned and mapped, grown on demand (adsb_context.cpp)

@@ -25,13 +25,15 @@ struct adsb_decim {
     size_t out_bytes = 0;
     Mixer mix;
     float scale = kInDefaultScale;   // CF32: g of q(x) (adsb_fmt.cpp)
-    Registry mem;   // owns the five buffers above and the mixer's table
+    InStat instat;                   // input statistics (adsb_instat.cpp): off unless asked for
+    Registry mem;   // owns the five buffers above, the mixer's table and the statistics' accumulator
 };
 
 namespace adsb {
 namespace host {
 MixerOwner mixer_of(adsb_decim *d) { return {d->ctx, &d->mem, &d->mix}; }
 float *scale_of(adsb_decim *d) { return &d->scale; }
+InStatOwner instat_of(adsb_decim *d) { return {d->ctx, &d->mem, &d->instat, 1u}; }
 }  // namespace host
 }  // namespace adsb
 
@@ -70,6 +72,9 @@ int run_on_stream(adsb_decim *d, int format, const void *d_in, uint64_t n_in, vo
     p.row_len = decim_row_len(d->factor, d->n_taps);
     p.recip = ((1u << 20) + d->factor - 1u) / d->factor;
     p.mix = mixer_params(d->mix, d->consumed);
+    // (the raw input counted first, on the same stream: a small call's input is still in cache for the filter)
+    if (d->instat.on)
+        if (int rc = d->instat.count(c, d->instat, format, d->scale, d_in, n_in)) return rc;
     if (int e = launch_decim(p, c->stream)) return fail(c, (hipError_t)e, "launch_decim");
     // (the next pass reads what this put on the context's own stream: order_behind_input)
     if (c->stream == c->own_stream) c->own_stream_dirty = true;

@@ -505,6 +505,30 @@ struct ResampBankRun {
 // grid is (tiles of the longest run) x n_runs: a workgroup past its run's last output returns at once.
 int launch_resamp_bank(const ResampParams &common, const ResampBankRun *runs, const ResampBankRun *d_runs, uint32_t n_runs,
                        void *stream);
+// Input statistics (adsb_instat_*; adsb_instat.hip: k_instat, k_instat_bank): the raw input of a decimator's, resampler's
+// or bank's call counted into adsb_input_stats records in device memory.  A kernel of its own in front of the filter's,
+// with parameters of its own.  A tile is what a workgroup reads in one round: kInstatThreads x kInstatUnroll 16-byte
+// loads; a launch has kInstatMaxGroups workgroups per run at most, each taking every gridDim.x-th tile.
+constexpr int kInstatThreads = 256, kInstatUnroll = 4;
+constexpr uint32_t kInstatMaxGroups = 1024;
+constexpr uint32_t kInstatBankGroups = 4096;   // a bank's launch: about this many workgroups over all its runs
+__host__ __device__ constexpr uint32_t instat_tile_samples(uint32_t format)
+{
+    return (uint32_t)(kInstatThreads * kInstatUnroll) * (16u / in_bytes_per_sample(format));
+}
+struct InstatParams {
+    const void *src;            // the call's inputs in `format`, 16-byte aligned (a bank: from the descriptors)
+    uint64_t n_in;              // ... how many (> 0)
+    const uint16_t *u8_table;   // 8-bit input: the widening table (device memory), else null
+    unsigned long long *acc;    // device memory: n_streams records, each laid out as adsb_input_stats
+    uint32_t n_streams;         // 1; a bank: its N (a descriptor's `reserved` is the stream, below N)
+    uint32_t format;            // InFormat
+    float scale;                // CF32: g
+};
+int launch_instat(const InstatParams &p, void *stream);
+// `runs` / `d_runs`: the descriptors of launch_resamp_bank, on the host (checked here) and in device memory
+int launch_instat_bank(const InstatParams &common, const ResampBankRun *runs, const ResampBankRun *d_runs, uint32_t n_runs,
+                       void *stream);
 // self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
 int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 

@@ -5,7 +5,8 @@
 // the dump1090 raw format) can consume it.
 //
 //   adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8|cf32|s16real] [--fix none|1bit|2bit] [--buffers K]
-//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] [--scale G] <capture.iq | ->
+//             [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] [--scale G]
+//             [--input-stats [SECONDS]] <capture.iq | ->
 //
 // --decimate D (2..16): the input is sampled at D x 2.4 MS/s, in the format --format names, and goes through the
 // library's decimator with its default taps (adsb_decim_default_taps) in front of the demodulation: the output lines are
@@ -37,6 +38,16 @@
 // whole input: the number of buffers, the noise floor (the median magnitude), the mean power and the peak in dBFS, and
 // the shares of clipped and of strong (above -3 dBFS) samples.  stdout and the TCP stream are byte for byte what they
 // are without the flag.
+//
+// --input-stats (only with --decimate or --resample) turns the input statistics of the decimator or resampler on
+// (include/adsb_hip.h, "Input statistics": adsb_instat_set_*): the RAW input, at the radio's own rate and in its own
+// format, counted on the device in front of the filter -- the rail hits, the DC offset and the NaNs that --stats, which
+// looks at the filtered 2.4 MS/s stream, can no longer see.  Lines beginning "adsb_feed: input stats (" go to STDERR, every
+// SECONDS (default 1) over the input since the last line and once more, as the last line, over the whole input: samples,
+// mean power and peak in dBFS, the DC offset in LSB, the shares of clipped and of NaN samples, the I/Q gain balance in dB
+// and the bits in use.  stdout, the TCP stream and the lines of --stats are byte for byte what they are without the flag.
+//   Airspy R2 raw, 20 MS/s, gain set by the ADC's own rail hits:
+//                              adsb_feed --format s16real --resample 3/25 --shift -5000000 --input-stats
 //
 // --fix 1bit repairs DF17/18 frames with one flipped bit from aircraft already heard, --fix 2bit with one or two
 // (adsb_set_error_correction);
@@ -181,6 +192,30 @@ struct SignalFold {
         if (adsb_signal_summary(folded.data(), folded.size(), &s) != ADSB_OK) return;
         std::fprintf(stderr, "adsb_feed: stats (%s): buffers %llu, floor %.3f dBFS, mean %.3f dBFS, peak %.3f dBFS, clipped %.6f %%, strong %.6f %%\n",
                      scope, buffers, s.median_dbfs, s.mean_power_dbfs, s.peak_dbfs, 100.0 * s.clipped_fraction, 100.0 * s.strong_fraction);
+    }
+};
+
+// --input-stats: input records folded together.  The records' own sums are 64 bits wide, and adsb_input_summary takes
+// any number of records: a new one is begun every 2^32 samples.
+struct InputFold {
+    std::vector<adsb_input_stats> folded;
+    void add(const adsb_input_stats &r)
+    {
+        if (folded.empty() || folded.back().n_samples >> 32) folded.push_back(adsb_input_stats{});
+        adsb_input_stats &f = folded.back();
+        f.n_samples += r.n_samples, f.sum_re += r.sum_re, f.sum_im += r.sum_im, f.sum_re2 += r.sum_re2, f.sum_im2 += r.sum_im2;
+        f.sum_re_im += r.sum_re_im, f.n_clipped += r.n_clipped, f.n_nan += r.n_nan;
+        if (r.peak > f.peak) f.peak = r.peak;
+        for (int b = 0; b < ADSB_INPUT_BINS; b++) f.hist[b] += r.hist[b];
+    }
+    void clear() { folded.clear(); }
+    void print(const char *scope) const
+    {
+        adsb_input_summary_t s{};
+        if (adsb_input_summary(folded.data(), folded.size(), &s) != ADSB_OK) return;
+        std::fprintf(stderr, "adsb_feed: input stats (%s): samples %llu, mean %.3f dBFS, peak %.3f dBFS, dc re %.3f im %.3f LSB, clipped %.6f %%, nan %.6f %%, iq gain %.3f dB, bits %u\n",
+                     scope, (unsigned long long)s.n_samples, s.mean_power_dbfs, s.peak_dbfs, s.dc_re, s.dc_im, 100.0 * s.clipped_fraction,
+                     100.0 * s.nan_fraction, s.iq_gain_db, s.bits_used);
     }
 };
 
@@ -334,6 +369,8 @@ int main(int argc, char **argv)
     int device = 0, port = 0, buffers = 64, latency_ms = 100, out_cap = 0, readers = 4;
     bool quiet = false, mem_order = false, cu8 = false, stats = false;
     double stats_seconds = 1.0;
+    bool input_stats = false;
+    double input_stats_seconds = 1.0;
     int fix = ADSB_FIX_NONE, decimate = 0;
     unsigned res_up = 0, res_down = 0;
     bool shifted = false, scaled = false;
@@ -379,6 +416,12 @@ int main(int argc, char **argv)
             const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
             if (i + 1 < argc && end != argv[i + 1] && *end == 0 && v > 0) stats_seconds = v, i++;
         }
+        else if (a == "--input-stats") {
+            input_stats = true;
+            char *end = nullptr;   // SECONDS is optional, as --stats's
+            const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 < argc && end != argv[i + 1] && *end == 0 && v > 0) input_stats_seconds = v, i++;
+        }
         else if (a == "--quiet") quiet = true;
         else if (a == "--mem-order") mem_order = true;
         else if (a == "--format" && i + 1 < argc) {
@@ -407,8 +450,10 @@ int main(int argc, char **argv)
     // --format cf32 | s16real: only in front of a filter (the scan's own entry points take neither); --scale: only with cf32
     const bool new_format = in_format == ADSB_DECIM_CF32 || in_format == ADSB_DECIM_REAL16;
     const bool format_ok = (!new_format || decimate || res_up) && (!scaled || in_format == ADSB_DECIM_CF32);
-    if (!path || buffers < 1 || (decimate && res_up) || !shift_ok || !format_ok) {
-        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8|cf32|s16real] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] [--scale G] <capture.iq | ->\n");
+    // --input-stats: the statistics are a decimator's or a resampler's
+    const bool input_stats_ok = !input_stats || decimate || res_up;
+    if (!path || buffers < 1 || (decimate && res_up) || !shift_ok || !format_ok || !input_stats_ok) {
+        std::fprintf(stderr, "usage: adsb_feed [--device N] [--port P] [--quiet] [--mem-order] [--format cs16|cu8|cf32|s16real] [--fix none|1bit|2bit] [--buffers K] [--latency-ms T] [--readers R] [--stats [SECONDS]] [--decimate D | --resample L/M] [--shift HZ] [--scale G] [--input-stats [SECONDS]] <capture.iq | ->\n");
         return 2;
     }
     std::signal(SIGPIPE, SIG_IGN);
@@ -519,6 +564,12 @@ int main(int argc, char **argv)
             destroy();
             return die(ctx, "adsb_fmt_set_scale", st);
         }
+        if (input_stats && (st = dec ? adsb_instat_set_decim(dec, 1) : adsb_instat_set_resamp(res, 1)) != ADSB_OK) {
+            destroy();
+            return die(ctx, "adsb_instat_set", st);
+        }
+        InputFold in_interval, in_total;
+        auto t_input_stats = std::chrono::steady_clock::now();
         std::vector<char> in_buf(call_samples * bps);
         const auto t0 = std::chrono::steady_clock::now();
         for (bool eof = false; !eof;) {
@@ -550,6 +601,20 @@ int main(int argc, char **argv)
                 }
                 for (size_t i = 0; i < n_sig; i++) sig_total.add(sig[i]);
             }
+            if (input_stats) {   // the call's record: the blocking call has finished, the fetch waits for nothing
+                adsb_input_stats rec{};
+                if ((st = dec ? adsb_instat_fetch_decim(dec, &rec) : adsb_instat_fetch_resamp(res, &rec)) != ADSB_OK) {
+                    destroy();
+                    return die(ctx, "adsb_instat_fetch", st);
+                }
+                in_interval.add(rec), in_total.add(rec);
+                const auto now = std::chrono::steady_clock::now();
+                if (std::chrono::duration<double>(now - t_input_stats).count() >= input_stats_seconds) {
+                    in_interval.print("interval");
+                    in_interval.clear();
+                    t_input_stats = now;
+                }
+            }
             emit(n);
             total_samples += n_in;
         }
@@ -561,6 +626,7 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "adsb_feed: %llu samples resampled by %u/%u to 2.4 MS/s, %llu frames in %.3f s (%.1f Msamples/s); %llu clients dropped\n",
                          total_samples, res_up, res_down, total_frames, secs, secs > 0 ? total_samples / secs / 1e6 : 0.0, clients.dropped);
         if (stats) sig_total.print("whole input");
+        if (input_stats) in_total.print("whole input");
         if (in != 0) ::close(in);
         destroy();
         adsb_destroy(ctx);

@@ -25,13 +25,15 @@ struct adsb_resamp {
     size_t out_bytes = 0;
     Mixer mix;
     float scale = kInDefaultScale;   // CF32: g of q(x) (adsb_fmt.cpp)
-    Registry mem;   // owns the five buffers above and the mixer's table
+    InStat instat;                   // input statistics (adsb_instat.cpp): off unless asked for
+    Registry mem;   // owns the five buffers above, the mixer's table and the statistics' accumulator
 };
 
 namespace adsb {
 namespace host {
 MixerOwner mixer_of(adsb_resamp *r) { return {r->ctx, &r->mem, &r->mix}; }
 float *scale_of(adsb_resamp *r) { return &r->scale; }
+InStatOwner instat_of(adsb_resamp *r) { return {r->ctx, &r->mem, &r->instat, 1u}; }
 }  // namespace host
 }  // namespace adsb
 
@@ -60,6 +62,9 @@ int run_on_stream(adsb_resamp *r, int format, const void *d_in, uint64_t n_in, v
     filter_params(p, L, M, r->k_taps, r->k_pad, r->shift, r->d_taps);
     first_output(L, M, r->consumed, &p.p0, &p.q0);
     p.mix = mixer_params(r->mix, r->consumed);
+    // (the raw input counted first, on the same stream: a small call's input is still in cache for the filter)
+    if (r->instat.on)
+        if (int rc = r->instat.count(c, r->instat, format, r->scale, d_in, n_in)) return rc;
     if (int e = launch_resamp(p, c->stream)) return fail(c, (hipError_t)e, "launch_resamp");
     // (the next pass reads what this put on the context's own stream: order_behind_input)
     if (c->stream == c->own_stream) c->own_stream_dirty = true;

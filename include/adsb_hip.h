@@ -861,6 +861,102 @@ extern float adsb_bank_get_scale(const adsb_bank *b);
 /* Host only, for the tests: the number of descriptor blocks a bank rotates through. */
 extern uint32_t adsb_bank_selftest_depth(void);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Input statistics -- opt-in per handle, off by default; with the mode off nothing observable changes: the handle makes
+ * no launch and reserves no memory.  adsb_set_signal_stats counts on the 2.4 MS/s CS16 the scan reads.  Behind a
+ * decimator, a resampler or a bank that is the wrong place to set a radio's gain by: a sample that hit the ADC rail at
+ * 20 MS/s has been averaged with its neighbours, the DC spike and the LO leakage have been mixed and filtered away, a
+ * CF32 conversion that clamps does so silently, and every output of a bank looks like band-limited noise.  This mode
+ * counts where the ADC's samples still exist: on the RAW input of adsb_decim, adsb_resamp and adsb_bank, by a kernel of
+ * its own (k_instat) in front of the filter's, as exact integers.
+ *
+ * The record.  c[m] = (re, im) is the converted CS16 sample that "Sample formats" puts in the place of x[m], BEFORE the
+ * mixer: CS16 the sample itself; 8-bit T8[b], through the context's table at the time of the call; CF32 q(x) with the
+ * handle's scale; REAL16 (r, 0).  A record covers a set S of input samples of one stream.  Every field is an exact
+ * integer and independent of the order of addition: it equals the plain restatement with tolerance 0.
+ *   adsb_input_bin(v)  0 for v == 0, else 1 + floor(log2 |v|): 0 .. 16, and -32768 lands in bin 16.  Host only.
+ *   clipped            a sample with a component at a rail of the RAW format.  CS16 / REAL16: a component in {-32768,
+ *                      32767}.  8-bit: a byte in {0, 255}, tested on the bytes before widening, as adsb_signal_stats
+ *                      does -- the table does not enter.  CF32: a component that is not NaN and has q(x) in {-32768,
+ *                      32767}.
+ *   NaN                a NaN component counts its sample in n_nan, never in n_clipped; its converted value 0 enters the
+ *                      sums and bin 0.
+ * Samples outside the call's n_in are never counted: not the int16 behind an odd REAL16 end, not whatever the rounded-up
+ * 16-byte load fetches behind the last sample, not the zero history.  The mixer, the taps and the ratio do not enter: the
+ * record is the same with the mixer on, off or changed.  The sums are 64-bit and wrap beyond that: about 2^33 samples
+ * between two fetches are safe (2^33 x 2^30 = 2^63 for the squares).
+ *
+ * Accumulation.  While the mode is on, every input sample the handle consumes is added to the handle's accumulator in
+ * device memory -- in a bank, to the accumulator of the run's stream -- whichever call consumed it: *_run_device,
+ * *_demod_iq piece by piece, or adsb_bank_run_device.  A call that returns ADSB_ERR_CAPACITY or ADSB_ERR_INVALID consumes
+ * nothing and counts nothing; a run of no input counts nothing; *_reset leaves the accumulator alone.  "The cut is
+ * invisible" extends to the record: the record of a stream is the same for any cutting into calls, with formats
+ * alternating between calls.  The launch goes on the stream the filter launch uses, in front of it, in the same call.
+ *
+ *   adsb_instat_set_*    1: the first enable reserves the accumulator -- 208 B (208 B x N for a bank) of device memory
+ *                        and as much pinned memory for the fetch -- and zeroes it, ordered on the stream like a run;
+ *                        enabling a handle that is already on changes nothing.  0: later calls launch nothing, and what
+ *                        was accumulated is discarded.  Never ADSB_ERR_BUSY.  ADSB_ERR_INVALID for NULL.
+ *   adsb_instat_get_*    1 / 0; ADSB_ERR_INVALID for NULL
+ *   adsb_instat_fetch_*  waits for everything the handle has put on the stream, writes the records that cover exactly the
+ *                        inputs consumed since the previous fetch of that stream (or since the enable), and zeroes what
+ *                        it fetched.  A bank fetch writes n_streams records, stream first_stream first, and touches only
+ *                        that range.  ADSB_ERR_INVALID for NULL arguments, a range beyond N, or a handle whose mode is off.
+ *   adsb_input_summary   folds n records into what a gain display shows -- a property, not bits: the doubles come from
+ *                        libm.  A logarithm of zero comes back as -inf, never NaN, as in adsb_signal_summary.  Host
+ *                        only.  ADSB_ERR_INVALID for a null `out`, or a null `s` with n > 0.
+ * Recipe.  An Airspy R2 at 20 MS/s raw, its gain set by the rail hits the ADC itself saw:
+ *     adsb_feed --format s16real --resample 3/25 --shift -5000000 --input-stats 1
+ * and an Airspy Mini at 12 MS/s:
+ *     adsb_feed --format s16real --decimate 5 --shift -3000000 --input-stats 1
+ * Not here: input statistics on the scan's own entry points (adsb_set_signal_stats is that), per-call records, and
+ * statistics in adsb_multi. */
+#define ADSB_INPUT_BINS 17
+typedef struct adsb_input_stats {
+    uint64_t n_samples;              /* |S| */
+    int64_t  sum_re, sum_im;         /* sum of re, of im: the DC offset times n */
+    uint64_t sum_re2, sum_im2;       /* sum of re^2, of im^2: power, and the I/Q gain balance */
+    int64_t  sum_re_im;              /* sum of re im: the I/Q phase error */
+    uint64_t n_clipped;              /* samples with a component at a rail of the RAW format */
+    uint64_t n_nan;                  /* CF32: samples with a NaN component; 0 in the other formats */
+    uint64_t hist[ADSB_INPUT_BINS];  /* hist[adsb_input_bin(v)]++ for v = re and v = im (REAL16: re only) */
+    uint32_t peak;                   /* max over S of max(|re|, |im|); 0 .. 32768; 0 for empty S */
+    uint32_t reserved;               /* 0 */
+} adsb_input_stats;                  /* 208 bytes */
+
+/* What a gain display shows, over any number of records (adsb_input_summary). */
+typedef struct adsb_input_summary_t {
+    uint64_t n_records;
+    uint64_t n_samples;
+    double mean_power_dbfs;   /* 10 log10((sum re^2 + sum im^2) / n_samples / 32768^2) */
+    double peak_dbfs;         /* 20 log10(max peak / 32768) */
+    double dc_re, dc_im;      /* sum re / n_samples, sum im / n_samples, in LSB (0 when there are no samples) */
+    double clipped_fraction;  /* n_clipped / n_samples (0 when there are no samples) */
+    double nan_fraction;      /* n_nan / n_samples */
+    double iq_gain_db;        /* 10 log10(sum re^2 / sum im^2) */
+    uint32_t bits_used;       /* the highest non-empty bin (0 when there are no samples) */
+    uint32_t reserved;
+} adsb_input_summary_t;
+
+ADSB_MUST_CHECK int adsb_instat_set_decim(adsb_decim *d, int enabled);
+ADSB_MUST_CHECK int adsb_instat_set_resamp(adsb_resamp *r, int enabled);
+ADSB_MUST_CHECK int adsb_instat_set_bank(adsb_bank *b, int enabled);
+ADSB_MUST_CHECK int adsb_instat_get_decim(const adsb_decim *d);
+ADSB_MUST_CHECK int adsb_instat_get_resamp(const adsb_resamp *r);
+ADSB_MUST_CHECK int adsb_instat_get_bank(const adsb_bank *b);
+ADSB_MUST_CHECK int adsb_instat_fetch_decim(adsb_decim *d, adsb_input_stats *out);
+ADSB_MUST_CHECK int adsb_instat_fetch_resamp(adsb_resamp *r, adsb_input_stats *out);
+ADSB_MUST_CHECK int adsb_instat_fetch_bank(adsb_bank *b, uint32_t first_stream, uint32_t n_streams, adsb_input_stats *out);
+extern int adsb_input_bin(int16_t v);
+ADSB_MUST_CHECK int adsb_input_summary(const adsb_input_stats *s, size_t n, adsb_input_summary_t *out);
+/* Test hooks, host only.  _geometry: the samples of `format` a workgroup reads in one round, and the most workgroups a
+ * launch gives one run (a longer run gives each workgroup several tiles); ADSB_ERR_INVALID for a format there is not.
+ * _launches: how many k_instat / k_instat_bank launches the handle has made (none while the mode is off); 0 for NULL. */
+ADSB_MUST_CHECK int adsb_instat_selftest_geometry(int format, uint32_t *tile_samples, uint32_t *max_groups_per_run);
+extern uint64_t adsb_instat_selftest_launches_decim(const adsb_decim *d);
+extern uint64_t adsb_instat_selftest_launches_resamp(const adsb_resamp *r);
+extern uint64_t adsb_instat_selftest_launches_bank(const adsb_bank *b);
+
 /* Sharded capture: one capture cut into contiguous ranges of 131072-sample buffers, one
  * range per GPU (BASELINE config 4; the reference's loop dump1090_rs/src/main.rs:161-167
  * is one stream with one process-global filter, src/icao_filter.rs:8-9).  Shards run

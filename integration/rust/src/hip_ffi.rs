@@ -115,6 +115,43 @@ pub struct AdsbSignalSummary {
     pub strong_fraction: f64,
 }
 
+pub const ADSB_INPUT_BINS: usize = 17;
+
+/// `adsb_input_stats`: the integer record of a set of raw input samples of a decimator, a resampler or one stream of a
+/// bank (opt-in, `adsb_instat_set_*`).  208 bytes.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct AdsbInputStats {
+    pub n_samples: u64,
+    pub sum_re: i64,
+    pub sum_im: i64,
+    pub sum_re2: u64,
+    pub sum_im2: u64,
+    pub sum_re_im: i64,
+    pub n_clipped: u64,
+    pub n_nan: u64,
+    pub hist: [u64; 17],
+    pub peak: u32,
+    pub reserved: u32,
+}
+
+/// `adsb_input_summary_t`: what `adsb_input_summary` makes of any number of records.  80 bytes.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct AdsbInputSummary {
+    pub n_records: u64,
+    pub n_samples: u64,
+    pub mean_power_dbfs: f64,
+    pub peak_dbfs: f64,
+    pub dc_re: f64,
+    pub dc_im: f64,
+    pub clipped_fraction: f64,
+    pub nan_fraction: f64,
+    pub iq_gain_db: f64,
+    pub bits_used: u32,
+    pub reserved: u32,
+}
+
 #[repr(C)]
 pub struct AdsbCtx {
     _private: [u8; 0],
@@ -343,4 +380,25 @@ unsafe extern "C" {
     pub fn adsb_fmt_set_scale_resamp(r: *mut AdsbResamp, scale: f32) -> c_int;
     pub fn adsb_fmt_get_scale_decim(d: *const AdsbDecim) -> f32;
     pub fn adsb_fmt_get_scale_resamp(r: *const AdsbResamp) -> f32;
+}
+
+// The input statistics of a decimator, a resampler or a bank (include/adsb_hip.h, "Input statistics"; the header marks the
+// calls ADSB_MUST_CHECK or `extern`); compared with the header by tests/test_instat_cpu.py.
+#[link(name = "adsb_hip")]
+unsafe extern "C" {
+    pub fn adsb_instat_set_decim(d: *mut AdsbDecim, enabled: c_int) -> c_int;
+    pub fn adsb_instat_set_resamp(r: *mut AdsbResamp, enabled: c_int) -> c_int;
+    pub fn adsb_instat_set_bank(b: *mut AdsbBank, enabled: c_int) -> c_int;
+    pub fn adsb_instat_get_decim(d: *const AdsbDecim) -> c_int;
+    pub fn adsb_instat_get_resamp(r: *const AdsbResamp) -> c_int;
+    pub fn adsb_instat_get_bank(b: *const AdsbBank) -> c_int;
+    pub fn adsb_instat_fetch_decim(d: *mut AdsbDecim, out: *mut AdsbInputStats) -> c_int;
+    pub fn adsb_instat_fetch_resamp(r: *mut AdsbResamp, out: *mut AdsbInputStats) -> c_int;
+    pub fn adsb_instat_fetch_bank(b: *mut AdsbBank, first_stream: u32, n_streams: u32, out: *mut AdsbInputStats) -> c_int;
+    pub fn adsb_input_bin(v: i16) -> c_int;
+    pub fn adsb_input_summary(s: *const AdsbInputStats, n: usize, out: *mut AdsbInputSummary) -> c_int;
+    pub fn adsb_instat_selftest_geometry(format: c_int, tile_samples: *mut u32, max_groups_per_run: *mut u32) -> c_int;
+    pub fn adsb_instat_selftest_launches_decim(d: *const AdsbDecim) -> u64;
+    pub fn adsb_instat_selftest_launches_resamp(r: *const AdsbResamp) -> u64;
+    pub fn adsb_instat_selftest_launches_bank(b: *const AdsbBank) -> u64;
 }
