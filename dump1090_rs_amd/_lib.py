@@ -322,6 +322,14 @@ def lib() -> C.CDLL:
     L.adsb_selftest_rx_score_tune.argtypes = [vp, u32, u32]
     L.adsb_selftest_rx_set_lookup.argtypes = [vp, vp, sz, vp, sz, vp]
     L.adsb_rx_set_home.argtypes = [C.c_uint64, u32]
+    L.adsb_set_receiver_carry.argtypes = [vp, C.c_int]
+    L.adsb_get_receiver_carry.argtypes = [vp]
+    L.adsb_receiver_carry_reset.argtypes = [vp, u32]
+    L.adsb_selftest_rx_seam_tune.argtypes = [vp, u32]
+    L.adsb_selftest_rx_seam_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    for name in ("adsb_set_receiver_carry", "adsb_get_receiver_carry", "adsb_receiver_carry_reset", "adsb_selftest_rx_seam_tune",
+                 "adsb_selftest_rx_seam_counters"):
+        getattr(L, name).restype = C.c_int
     L.adsb_rx_set_home.restype = u32
     for name in ("adsb_set_receiver_scoring", "adsb_get_receiver_scoring", "adsb_selftest_rx_score_counters",
                  "adsb_selftest_rx_score_tune", "adsb_selftest_rx_set_lookup"):

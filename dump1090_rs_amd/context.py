@@ -18,6 +18,7 @@ TRAILING_SAMPLES = 326
 MODES_LONG_MSG_BYTES = 14
 MODES_SHORT_MSG_BYTES = 7
 MAG_DATA_LEN = TRAILING_SAMPLES + MODES_MAG_BUF_SAMPLES
+RX_ALL = 0xFFFFFFFF   # ADSB_RX_ALL: every receiver (Context.receiver_carry_reset)
 
 
 @dataclass
@@ -621,6 +622,28 @@ class Context:
     def ring_submit_rx(self, n_samples: int, receivers) -> None:
         m = _as_map(receivers, n_samples)
         self._check(self._L.adsb_ring_submit_rx(self._h, n_samples, m.ctypes.data), "adsb_ring_submit_rx")
+
+    def set_receiver_carry(self, enabled: bool) -> None:
+        """adsb_set_receiver_carry: carry-over with receivers on -- every buffer's lead-in is the end of its own receiver's
+        previous buffer (include/adsb_hip.h, "Receiver seams")."""
+        self._check(self._L.adsb_set_receiver_carry(self._h, 1 if enabled else 0), "adsb_set_receiver_carry")
+
+    def get_receiver_carry(self) -> bool:
+        return int(self._L.adsb_get_receiver_carry(self._h)) == 1
+
+    def receiver_carry_reset(self, receiver: int = RX_ALL) -> None:
+        """adsb_receiver_carry_reset: nothing precedes the next buffer of `receiver` (default: of every receiver)."""
+        self._check(self._L.adsb_receiver_carry_reset(self._h, receiver), "adsb_receiver_carry_reset")
+
+    def selftest_rx_seam_tune(self, list_cap: int = 0) -> None:
+        self._check(self._L.adsb_selftest_rx_seam_tune(self._h, list_cap), "adsb_selftest_rx_seam_tune")
+
+    def selftest_rx_seam_counters(self) -> dict:
+        """adsb_selftest_rx_seam_counters: passes with a seam step / seam records handed to the replay / records of the
+        pass itself dropped for j < 326 / seam steps redone after an overflow."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.adsb_selftest_rx_seam_counters(self._h, out), "adsb_selftest_rx_seam_counters")
+        return {"passes": int(out[0]), "records": int(out[1]), "dropped": int(out[2]), "redone": int(out[3])}
 
     def set_receiver_scoring(self, enabled: bool) -> None:
         """adsb_set_receiver_scoring: dense passes of a receivers context are scored on the device, a filter per receiver."""

@@ -107,7 +107,8 @@ bool take_device_result(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vecto
 // is at).  A pass of at least rx_parallel_min records with more than one receiver in it is dealt, receiver by receiver,
 // to the threads of a pool made when the first such pass comes along (adsb_replay_host.h: ReceiverReplay).
 // *gained: some receiver's filter took a new address.
-int replay_receivers(adsb_ctx *c, const Slot &sl, size_t n, uint64_t chunk_offset, std::vector<adsb_msg> &out, bool *gained)
+int replay_receivers(adsb_ctx *c, const Slot &sl, const TrialRecord *rec, size_t n, uint64_t chunk_offset, std::vector<adsb_msg> &out,
+                     bool *gained)
 {
     const size_t first = (size_t)chunk_offset, last = std::min(sl.rx_map.size(), first + sl.n_chunks);
     bool several = false;
@@ -122,7 +123,7 @@ int replay_receivers(adsb_ctx *c, const Slot &sl, size_t n, uint64_t chunk_offse
         pool = c->rx_pool.get();
     }
     bool pooled = false;
-    if (!c->rx_replay.run(c->rx_filter_of.data(), sl.rx_map.data(), sl.rx_map.size(), c->crc, sl.h_rec, n, chunk_offset, out, pool,
+    if (!c->rx_replay.run(c->rx_filter_of.data(), sl.rx_map.data(), sl.rx_map.size(), c->crc, rec, n, chunk_offset, out, pool,
                           &c->host_sorts, gained, &pooled)) {
         c->last_error = "a trial record names a buffer outside the pass that wrote it";
         return ADSB_ERR_HIP;
@@ -264,6 +265,10 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
     // pass's address/parity trials may have been matched before its bit was set: again, through the three
     // launches (every earlier pass is complete now, so nothing can be missed a second time).
     if (sl.fused && sl.unsynced_from && c->last_new_insert_seq >= sl.unsynced_from) return 2;
+    // Receiver seams: the seam step's records, once per pass (the overflow fallback's one-buffer passes find them taken;
+    // so does a pass whose seam collect_oldest redid).  Its k_seam_match ran behind the pass's last kernel.
+    if (sl.seam_on && !c->seam_taken)
+        if (int rc = take_seam(c, sl)) return rc;
     const size_t n = sl.h_sum->n_hits;
     // (k_records' own test: a pass that k_score took over has left its records in device memory)
     const bool rec_on_device = sl.device_scored && n <= c->score.cap;
@@ -343,7 +348,17 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
         if (c->n_receivers && !skip_replay) {
             // (conservative: the address ANY receiver's filter gained may be one the union already held -- never wrong)
             bool gained = false;
-            if (int rc = replay_receivers(c, sl, n, chunk_offset, out, &gained)) return rc;
+            const TrialRecord *rec = sl.h_rec;
+            size_t n_rec = n;
+            if (sl.seam_on) {
+                // the pass's own records at j < 326 tried a zero lead-in: the seam's records of these buffers take their
+                // place (the replay sorts)
+                merge_seam_records(sl.h_rec, n, c->seam_rec.data(), c->seam_rec.size(), chunk_offset, sl.n_chunks, (uint32_t)kLead,
+                                   c->seam_merged, &c->seam_dropped, &c->seam_records);
+                rec = c->seam_merged.data();
+                n_rec = c->seam_merged.size();
+            }
+            if (int rc = replay_receivers(c, sl, rec, n_rec, chunk_offset, out, &gained)) return rc;
             if (gained) c->last_new_insert_seq = sl.scan_seq;
         } else if (!skip_replay) {
             replay(c->filter, c->crc, sl.h_rec, n, chunk_offset, out, &c->host_sorts);
@@ -389,7 +404,14 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
     st.n_chunks = sl.n_chunks;
     if (sl.flush_before) flush_host_filters(c);  // icao_flush() took effect before this pass
     flush_receivers(c, sl.rx_flush);             // ... and so did the adsb_icao_flush_receiver calls recorded against it
+    c->seam_taken = false;
     int rc = finish_pass(c, sl, 0, st, out);
+    // whatever makes the library redo the pass's match redoes the seam's too, from scratch and independent of the
+    // superset (a seam step does not depend on the pass's lists, but its match read the same bitmap)
+    if (rc > 0 && sl.seam_on) {
+        if (int e = drain_streams(c)) return e;
+        if (int e = redo_seam(c, sl)) rc = e;
+    }
     if (rc == 2) {
         // a one-launch pass that a pass in flight beside it may have invalidated (finish_pass): once more
         // through the three launches.  Passes submitted after it may have rotated the bitmaps behind an
@@ -454,6 +476,7 @@ int collect_oldest(adsb_ctx *c, std::vector<adsb_msg> &out)
     c->sig_out.clear();
     if (rc == 0 && sl.sig_on) rc = take_signal_records(c, sl);
     sl.busy = false;
+    c->seam_taken = false;
     c->collected++;
     if (rc > 0) {
         c->last_error = "device lists overflowed on a single chunk";

@@ -870,6 +870,10 @@ try {
         ADSB_ON_DEVICE(c);
         if (int rc = ensure_rx_scoring(c)) return rc;
     }
+    if (c->rx_carry && c->seam_receivers_changed) {   // receiver seams: every stream restarts; n = 0 turns the mode off
+        ADSB_ON_DEVICE(c);
+        if (int rc = c->seam_receivers_changed(c)) return rc;
+    }
     return ADSB_OK;
 } ADSB_ABI_CATCH
 
@@ -924,6 +928,7 @@ int adsb_set_receiver_scoring(adsb_ctx *c, int enabled)
 try {
     if (!c) return ADSB_ERR_INVALID;
     if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    if (enabled && c->rx_carry) return ADSB_ERR_INVALID;   // (seam trials are scored by the host: adsb_set_receiver_carry)
     if (enabled && !c->rx_scoring) {
         ADSB_ON_DEVICE(c);
         c->rx_scoring = true;   // (remembered whatever comes of it: adsb_set_receivers reserves what is missing)

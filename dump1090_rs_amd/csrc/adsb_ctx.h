@@ -135,6 +135,18 @@ struct Slot {
     uint32_t *d_rx_slot = nullptr;
     uint32_t *h_add_rx = nullptr, *h_add_rx_dev = nullptr;
     RxScoreDev rx{};
+    // receiver seams (adsb_set_receiver_carry; all null until the mode is first enabled): whether this pass has a seam
+    // step, the parameters its launches went out with (the tail's k_seam_match and a redo take them from here), the
+    // slot's descriptors, summary and record block in mapped host memory, and its counters, lead-in rows (kept until the
+    // slot is reused: a redo reads them again) and seam list in device memory
+    bool seam_on = false;
+    SeamParams seam{};
+    SeamDesc *h_seam_desc = nullptr, *h_seam_desc_dev = nullptr;
+    SeamSummary *h_seam_sum = nullptr, *h_seam_sum_dev = nullptr;
+    TrialRecord *h_seam_rec = nullptr, *h_seam_rec_dev = nullptr;
+    SeamCounters *d_seam_ctr = nullptr;
+    uint32_t *d_seam_lead = nullptr;
+    TrialRecord *d_seam_list = nullptr;
 };
 
 // Passes in flight: 4 and the device never waits for the host between large passes (3 do for sparse
@@ -376,6 +388,26 @@ struct adsb_ctx {
     std::vector<uint32_t> rx_held, rx_pass_adds, rx_touched;
     bool rx_held_valid = false;
     uint64_t rx_scored_taken = 0, rx_scored_refused = 0, rx_set_rebuilds = 0, rx_no_room = 0;   // adsb_selftest_rx_score_counters
+    // Receiver seams (adsb_set_receiver_carry; include/adsb_hip.h, "Receiver seams"; adsb_seam.cpp): carry-over with
+    // receivers on.  The scan stays as it is; the first kLead positions of every buffer are tried by kernels of their own
+    // (adsb_seam.hip) against the end of the same receiver's previous buffer, and the host replay takes their records in
+    // place of the pass's own records with j < kLead.  One CS16 carry per receiver in device memory; per slot see Slot.
+    bool rx_carry = false;
+    uint32_t *d_rx_carry = nullptr;          // n_receivers rows of kCarrySamples dwords
+    char *h_seam_block = nullptr, *h_seam_block_dev = nullptr, *d_seam_block = nullptr;   // every slot's share: one allocation each
+    uint32_t seam_cap = 0, seam_tune = 0;    // entries of a slot's seam list and of its record block / adsb_selftest_rx_seam_tune
+    struct SeamFallback {                    // records of a redo's piece, sized for the worst case (lazy)
+        TrialRecord *h_rec = nullptr, *h_rec_dev = nullptr;
+    } seam_fb;
+    std::vector<TrialRecord> seam_rec, seam_merged;   // the seam records of the pass being collected / the pass's merged records
+    std::vector<int32_t> seam_latest, seam_prev;      // seam_prev_map's scratch (the latest buffer of every receiver) and results
+    std::vector<uint32_t> seam_last;
+    bool seam_taken = false;                 // seam_rec holds the seam records of the pass being collected
+    uint64_t seam_passes = 0, seam_records = 0, seam_dropped = 0, seam_redone = 0;   // adsb_selftest_rx_seam_counters
+    // what adsb_set_receivers calls when the number of receivers changes while the mode is, or has been, on: installed by
+    // the first enable, so that adsb_context.cpp refers to nothing of adsb_seam.cpp -- tests/test_context_lifetime_cpu.py
+    // links adsb_context.cpp against a fake runtime WITHOUT that unit, as InStat::count is installed for adsb_instat.cpp
+    int (*seam_receivers_changed)(adsb_ctx *c) = nullptr;
     uint32_t rx_set_lg() const { return rx_tune_lg ? std::min(rx_tune_lg, rx_set_alloc_lg) : rx_set_alloc_lg; }
     uint32_t rx_probe_max() const { return rx_tune_probe ? rx_tune_probe : kRxProbeMax; }
 };
@@ -615,6 +647,18 @@ struct RxCall {
     RxCall(const RxCall &) = delete;
     RxCall &operator=(const RxCall &) = delete;
 };
+
+// adsb_seam.cpp: receiver seams.  `ordered_passes`: consecutive passes are ordered by stream order on the first scan
+// stream and read their input with launches in front of the scan (either carry-over mode).  seam_front: the step in front
+// of a pass's scan launch on its scan stream `ss` (lead-ins, carries, k_seam_scan; clears a fresh folded bitmap first, so
+// that what the seam learns stays); seam_tail: the step behind the pass's last kernel on the stream that ran on.
+// take_seam: at collect, the pass's seam records into c->seam_rec (redone in pieces when a seam list overflowed);
+// redo_seam: the same from scratch, every trial a record (blocking; whenever the library redoes the pass's own match).
+inline bool ordered_passes(const adsb_ctx *c) { return c->carry_over || c->rx_carry; }
+int seam_front(adsb_ctx *c, Slot &sl, ScanParams &p, SrcFormat fmt, bool plain_iq, bool redo, hipStream_t ss);
+int seam_tail(adsb_ctx *c, Slot &sl, hipStream_t ts);
+int take_seam(adsb_ctx *c, Slot &sl);
+int redo_seam(adsb_ctx *c, Slot &sl);
 
 // adsb_collect.cpp
 int verify_records(adsb_ctx *c, const Summary *sum, const TrialRecord *rec, size_t n);

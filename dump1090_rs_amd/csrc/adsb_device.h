@@ -529,6 +529,60 @@ int launch_instat(const InstatParams &p, void *stream);
 // `runs` / `d_runs`: the descriptors of launch_resamp_bank, on the host (checked here) and in device memory
 int launch_instat_bank(const InstatParams &common, const ResampBankRun *runs, const ResampBankRun *d_runs, uint32_t n_runs,
                        void *stream);
+// Receiver seams (adsb_set_receiver_carry; adsb_seam.hip): the first kLead positions of every buffer of a receivers pass
+// tried against a lead-in that holds the end of the same receiver's previous buffer.  Kernels of their own beside the
+// scan, with parameters of their own -- ScanParams and the scan's instantiations stay as they are.
+constexpr uint32_t kSeamWorstPerChunk = 5u * (uint32_t)kLead;   // every seam position sliced, five trials each
+struct SeamDesc {            // per buffer of a pass, written by the host into mapped memory (host::seam_prev_map)
+    int32_t prev;            // the previous buffer of this buffer's receiver in the same pass, or -1: the receiver's carry
+    uint32_t rx;             // the buffer's receiver
+    uint32_t last;           // 1: no later buffer of the pass belongs to that receiver (its end becomes the carry)
+    uint32_t reserved;
+};
+struct SeamCounters {        // device memory, all zero between passes (k_seam_match leaves them so)
+    uint32_t n_list, n_rec, overflow, reserved;   // overflow: bit 0 the record block, bit 1 the seam list
+    unsigned long long rec_sum;                   // 64-bit sum of every u64 word of the records written
+};
+struct SeamSummary {         // mapped host memory, eight separate posted writes, `seq` issued last
+    uint32_t n_rec, overflow, rec_sum_lo, rec_sum_hi, n_list, reserved;
+    uint32_t check;          // seam_summary_check() of the six words above and seq
+    uint32_t seq;
+};
+__host__ __device__ inline uint32_t seam_summary_check(const uint32_t w[6], uint32_t seq)
+{
+    uint32_t x = 0x5EA3C0DEu ^ (seq * 2654435761u);
+    for (int k = 0; k < 6; k++) x ^= (w[k] << (k + 3)) | (w[k] >> (29 - k));
+    return x;
+}
+struct SeamParams {
+    const void *src;         // the pass's IQ: CS16 dwords or CU8 byte pairs
+    uint64_t n_samples;
+    uint32_t n_chunks;       // buffers of the pass
+    uint32_t first_chunk;    // k_seam_scan: the launch takes buffers [first_chunk, first_chunk + n_scan)
+    uint32_t n_scan;
+    const uint16_t *u8_table;   // CU8: the widening table (device memory), else null
+    const SeamDesc *desc;    // n_chunks, mapped host memory
+    uint32_t *carry;         // n_receivers rows of kCarrySamples CS16 dwords
+    uint32_t n_receivers;
+    uint32_t *lead;          // n_chunks rows of kCarrySamples CS16 dwords: the samples in front of each buffer
+    uint32_t *bitmap;        // the pass's address superset (ScanParams::bitmap)
+    uint32_t bitmap_lg;
+    const uint32_t *tables;  // ScanParams::tables
+    uint32_t fix;            // ScanParams::fix
+    uint32_t emit_all;       // the redo after an overflow: address/parity trials are records too (no list, no match);
+                             // what it learns goes into `bitmap` all the same -- the bitmap in use at the redo, which an
+                             // icao_flush behind the pass may have made another one than the first run's
+    TrialRecord *list;       // address/parity trials with their sliced bytes and power, device memory
+    uint32_t list_cap;
+    TrialRecord *rec;        // finished records, mapped host memory
+    uint32_t rec_cap;
+    SeamCounters *ctr;
+    SeamSummary *summary;    // mapped host memory
+    uint32_t seq;
+};
+int launch_seam_lead(const SeamParams &q, void *stream);    // k_rx_lead, then k_rx_carry_update
+int launch_seam_scan(const SeamParams &q, void *stream);    // k_seam_scan
+int launch_seam_match(const SeamParams &q, void *stream);   // k_seam_match: the list against the bitmap, then the summary
 // self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
 int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 

@@ -74,7 +74,7 @@ static int scan_stream_index(const adsb_ctx *c, bool plain_iq, bool carry, bool 
 // The scan stream the next plain IQ pass of n_chunks buffers will run on.
 hipStream_t next_scan_stream(const adsb_ctx *c, uint32_t n_chunks)
 {
-    return c->scan_stream[scan_stream_index(c, true, c->carry_over, one_launch_pass(c, n_chunks), false)];
+    return c->scan_stream[scan_stream_index(c, true, ordered_passes(c), one_launch_pass(c, n_chunks), false)];
 }
 
 void pass_params(adsb_ctx *c, const Slot &sl, ScanParams &p, uint32_t **retired, uint32_t *clear_next)
@@ -187,7 +187,7 @@ static int plan_pass(adsb_ctx *c, const Slot &sl, SrcFormat fmt, uint32_t n_chun
     // matches, builds the records and publishes the summary, with no event behind it.  (Level 2 wants the kernels apart.)
     pl.fused = !opt.force_simple && !opt.no_fuse && one_launch_pass(c, n_chunks);
     pl.classic = !pl.fused && (pl.prof > 1 || (pl.prof == 1 && (!pl.fast || !knob_ext_events())));
-    pl.si = scan_stream_index(c, pl.fast, c->carry_over && !pl.from_mag && sl.d_carry, pl.fused, opt.redo);
+    pl.si = scan_stream_index(c, pl.fast, (c->carry_over && !pl.from_mag && sl.d_carry) || c->rx_carry, pl.fused, opt.redo);
     pl.ss = c->scan_stream[pl.si];
     // A small pass is all launch overhead: its tail stays on its scan stream too (the scan streams still let
     // consecutive passes overlap), which saves the cross-stream hand-off.
@@ -522,14 +522,19 @@ int enqueue_pass(adsb_ctx *c, Slot &sl, const void *d_src, SrcFormat fmt, uint64
     if (int rc = order_behind_input(c, opt.input_done, pl.si, pl.ss)) return rc;   // edge in
     if (int rc = edges_before_scan(c, sl, p, pl)) return rc;             // edges 0, 1'', one launch: 1, 2, 3'
     if (int rc = enqueue_signal_stats(c, sl, p, fmt, opt, pl)) return rc;  // (no edge: stream order on the scan stream)
+    // receiver seams (adsb_set_receiver_carry), only when the mode is on: the seam step in front of the scan launch, on its
+    // stream and behind the same edges as the signal statistics (no edge of its own: every pass of the mode runs on the
+    // first scan stream), and k_seam_match behind the pass's last kernel on the stream that one ran on
+    if (int rc = seam_front(c, sl, p, fmt, pl.fast, opt.redo, pl.ss)) return rc;
     if (int rc = launch_scan_step(c, sl, p, fmt, opt, pl)) return rc;    // (row 6)
     if (pl.fused) {   // everything is out; what the next pass has to know about this one
         sl.tail_q = c->prev_scan_stream = pl.ss;
         c->prev_scanned = nullptr;
         c->prev_inline = c->prev_fused = true;
-        return ADSB_OK;
+        return seam_tail(c, sl, pl.ss);
     }
     if (int rc = enqueue_tail(c, sl, p, fmt, pl)) return rc;             // edges 1, 2, 2', 3
+    if (int rc = seam_tail(c, sl, sl.tail_q)) return rc;                 // (before `done`: edge 5 covers it)
     return enqueue_score(c, sl, p, pl);                                  // edges 4, 5
 }
 
@@ -784,7 +789,7 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
     // host copy into it instead of a copy command, its staging inside the runtime and an event.
     // Samples inside a buffer the caller registered (adsb_host_register) are pinned and mapped already: one launch
     // that reads them where they are, no host copy at all.
-    if (n_samples && n_samples <= std::min<size_t>(piece, (size_t)kInlineTailChunks * kChunkSamples) && !c->carry_over &&
+    if (n_samples && n_samples <= std::min<size_t>(piece, (size_t)kInlineTailChunks * kChunkSamples) && !ordered_passes(c) &&
         ((uintptr_t)iq & 15u) == 0) {
         const char *b = iqb;
         for (const auto &r : c->host_ranges)
@@ -796,7 +801,7 @@ int demod_host(adsb_ctx *c, const void *iq, size_t n_samples, adsb_msg *out, siz
                 return deliver(c, msgs, out, cap, n_out);
             }
     }
-    const bool in_place = n_samples <= (size_t)kInlineTailChunks * kChunkSamples && !c->carry_over;
+    const bool in_place = n_samples <= (size_t)kInlineTailChunks * kChunkSamples && !ordered_passes(c);
     int rc = in_place ? ensure_host_stage(c, std::max<size_t>(n_samples, 1) * bps + 512)   // (+ the progress word)
                       : ensure_stage(c, std::min(piece, std::max<size_t>(n_samples, 1)) * bps);
     if (rc) return rc;

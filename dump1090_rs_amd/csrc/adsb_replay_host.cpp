@@ -534,6 +534,53 @@ void learned_addresses(const Crc24 &crc, const TrialRecord *rec, size_t n, std::
     }
 }
 
+bool seam_prev_map(const uint32_t *map, size_t n_buffers, uint32_t n_receivers, std::vector<int32_t> &latest, int32_t *prev,
+                   uint32_t *last)
+{
+    for (size_t b = 0; b < n_buffers; b++)
+        if (map[b] >= n_receivers) return false;
+    if (latest.size() < n_receivers) latest.resize(n_receivers, -1);
+    for (size_t b = 0; b < n_buffers; b++) {
+        int32_t &at = latest[map[b]];
+        prev[b] = at;
+        last[b] = 1;
+        if (at >= 0) last[at] = 0;
+        at = (int32_t)b;
+    }
+    for (size_t b = 0; b < n_buffers; b++) latest[map[b]] = -1;   // (only the entries touched)
+    return true;
+}
+
+void merge_seam_records(const TrialRecord *pass, size_t n_pass, const TrialRecord *seam, size_t n_seam, uint64_t first,
+                        uint64_t n_buffers, uint32_t lead, std::vector<TrialRecord> &out, uint64_t *dropped, uint64_t *taken)
+{
+    out.clear();
+    out.reserve(n_pass + n_seam);
+    for (size_t i = 0; i < n_pass; i++) {
+        if ((pass[i].j_tp & 0xFFFFFFu) < lead) {
+            if (dropped) ++*dropped;
+            continue;
+        }
+        out.push_back(pass[i]);
+    }
+    const size_t n_kept = out.size();
+    for (size_t i = 0; i < n_seam; i++) {
+        if (seam[i].chunk < first || seam[i].chunk - first >= n_buffers) continue;
+        TrialRecord r = seam[i];
+        r.chunk = (uint32_t)(r.chunk - first);
+        out.push_back(r);
+        if (taken) ++*taken;
+    }
+    // a dense pass hands its records over in (chunk, j, try_phase) order: the few seam records are merged into their
+    // places, so that the replay finds the whole list in order and does not sort tens of thousands of records itself
+    const auto key = [](const TrialRecord &r) { return (uint64_t)r.chunk << 32 | (uint64_t)(r.j_tp & 0xFFFFFFu) << 8 | (r.j_tp >> 24); };
+    const auto before = [&](const TrialRecord &a, const TrialRecord &b) { return key(a) < key(b); };
+    if (out.size() > n_kept && std::is_sorted(out.begin(), out.begin() + (long)n_kept, before)) {
+        std::sort(out.begin() + (long)n_kept, out.end(), before);
+        std::inplace_merge(out.begin(), out.begin() + (long)n_kept, out.end(), before);
+    }
+}
+
 void union_sorted(const std::vector<const std::vector<uint32_t> *> &lists, const std::vector<uint32_t> &known,
                   std::vector<uint32_t> &out)
 {

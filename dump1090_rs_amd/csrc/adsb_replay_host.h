@@ -284,6 +284,20 @@ class ReceiverReplay {
     std::vector<uint32_t> part_of_;   // receiver -> part + 1 (0: none), only the entries of receivers present are touched
 };
 
+// Receiver seams (include/adsb_hip.h, "Receiver seams"), the host's two parts.
+// seam_prev_map: for every buffer b of a pass, prev[b] = the latest buffer before b that belongs to b's receiver (-1: none
+// in this pass -- its lead-in is the receiver's carry) and last[b] = 1 when no later buffer does (its end becomes the
+// carry).  `latest`: scratch of n_receivers entries, all -1 on entry and on return.  false: a map entry >= n_receivers
+// (nothing written).
+bool seam_prev_map(const uint32_t *map, size_t n_buffers, uint32_t n_receivers, std::vector<int32_t> &latest, int32_t *prev,
+                   uint32_t *last);
+// merge_seam_records: what the replay of buffers [first, first + n_buffers) of a pass gets -- the pass's own records
+// (chunk relative to `first` already) without those at j < lead, which tried a zero lead-in, and the seam's records of
+// those buffers (chunk as in the whole pass) with `first` taken off.  `out` is cleared first; *dropped / *taken count.  Where the pass's records come in (chunk, j, try_phase)
+// order the result is in that order too; otherwise the seam's records follow the pass's.
+void merge_seam_records(const TrialRecord *pass, size_t n_pass, const TrialRecord *seam, size_t n_seam, uint64_t first,
+                        uint64_t n_buffers, uint32_t lead, std::vector<TrialRecord> &out, uint64_t *dropped, uint64_t *taken);
+
 // The sorted union of several sorted, duplicate-free address lists (the shards' learned addresses), appended to
 // `out` (cleared first); what is already in `known` (sorted, duplicate-free) is left out.
 void union_sorted(const std::vector<const std::vector<uint32_t> *> &lists, const std::vector<uint32_t> &known,

@@ -103,11 +103,11 @@ static int ring_submit(adsb_ctx *c, size_t n_samples)
     //    three in flight: 10.9 / 11.0 / 13.1 Gsample/s against 9.1 / 9.5 / 10.2 in place; one in flight: 6.3 /
     //    8.1 / 9.7 against 7.6 / 9.4 / 10.1 -- profiles/r4_ring_copy_ab.txt), and the only way for slots of more
     //    than one launch.
-    bool in_place = one_launch_pass(c, n_chunks) && !c->carry_over &&
+    bool in_place = one_launch_pass(c, n_chunks) && !ordered_passes(c) &&
                     (n_chunks <= kRingInPlaceChunks || c->submitted == c->delivered);
     if (const char *e = tuning_env("ADSB_RING_COPY")) {   // measurement aid (tuning build only): 0 in place where possible, else copy
         const int mode = std::atoi(e);
-        const bool can = one_launch_pass(c, n_chunks) && !c->carry_over;
+        const bool can = one_launch_pass(c, n_chunks) && !ordered_passes(c);
         in_place = can && mode == 0;
     }
     if (in_place) {

@@ -547,6 +547,61 @@ int adsb_selftest_rx_set_lookup(adsb_ctx *ctx, const uint64_t *keys, size_t n_ke
 uint32_t adsb_rx_set_home(uint64_t key, uint32_t set_lg);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Receiver seams -- carry-over with receivers on.  Opt-in, off by default; with it off nothing changes: no launch, no
+ * allocation.  This mode is the way to get carry-over with many receivers: adsb_set_carry_over itself stays
+ * ADSB_ERR_INVALID while receivers are on, as the section above says.
+ *
+ * Without it every buffer of every receiver starts from a zero lead-in, and a preamble that begins in the last 326
+ * samples of a receiver's buffer is never tried (326 of every 131072 positions).  With it:
+ *
+ * Definition.  The sentence that defines the _rx calls, with one change: feed receiver r's buffers, one adsb_demod_iq
+ * call per buffer, to a plain context r of its own THAT HAS adsb_set_carry_over(ctx, 1); relabel every message's `chunk`
+ * with b; merge in ascending (chunk, j).  That merged list is what every _rx call, its _u8 twin, submit / collect,
+ * adsb_ring_submit_rx and the plain IQ calls ("every buffer is receiver 0") return, field for field and signal_level bit
+ * for bit, in every error-correction mode, and adsb_receiver_filter_table(r) equals context r's table slot for slot.
+ * `j` stays the index into MagnitudeBuffer.data: a frame that starts in the lead-in has j < 326, as under
+ * adsb_set_carry_over.  A receiver's stream is CS16 inside the library: CS16 and CU8 buffers may alternate.  A short
+ * last buffer of n < 326 samples leaves its receiver's carry as the last 326 samples of (old carry ++ buffer).
+ *
+ * How: a trial at position j reads data[j .. j+290] and nothing else, so a buffer's lead-in decides the trials at
+ * j < 326 and no others.  The pass's scan runs unchanged; kernels of their own gather a lead-in per buffer (the
+ * receiver's carry, or the end of the receiver's previous buffer in the same pass), try those 326 positions per buffer in
+ * front of the scan -- what they learn is in the address superset before the pass's match reads it -- and match their
+ * address/parity trials behind the pass's last kernel.  The host drops the pass's own records with j < 326 and replays
+ * the seam's records in their place, buffer by buffer against the receiver's filter as before.  All passes of a context
+ * in this mode run on one scan stream, ordered by it (as under adsb_set_carry_over).
+ *
+ *   adsb_set_receiver_carry(ctx, enabled)   ADSB_ERR_BUSY while passes are pending; ADSB_ERR_INVALID for a null context,
+ *                           with receivers off, and while adsb_set_receiver_scoring is on (and
+ *                           adsb_set_receiver_scoring(ctx, 1) is ADSB_ERR_INVALID while this mode is on: seam trials are
+ *                           scored by the host).  Enabling, disabling and any change of adsb_set_receivers restart every
+ *                           receiver's stream with nothing before its next buffer; adsb_set_receivers(ctx, 0) turns the
+ *                           mode off.  adsb_icao_flush and adsb_icao_flush_receiver touch filters only.
+ *   adsb_get_receiver_carry   1 / 0, or ADSB_ERR_INVALID for a null context.
+ *   adsb_receiver_carry_reset(ctx, r)   receiver r (or all, ADSB_RX_ALL) reconnected: nothing precedes its next buffer.
+ *                           Ordered between the submissions before and after it; never ADSB_ERR_BUSY;
+ *                           ADSB_ERR_INVALID for r >= n and with the mode off.
+ *   unchanged               adsb_demodulate2400 (the caller's magnitudes), the signal statistics (a lead-in is not
+ *                           counted), and everything with the mode off.
+ *   footprint               reserved by the enable.  Device: 1312 bytes per receiver; per pass in flight 1312 max_chunks
+ *                           bytes of lead-ins and a seam list of S x 32 bytes, S = min(max(2048, 64 max_chunks), 65536).
+ *                           Pinned host: per pass in flight 16 max_chunks + S x 32 bytes.  A full seam list or record
+ *                           block makes the library redo that pass's seam step in pieces sized for the worst case (326 x 5
+ *                           records a buffer; 417 KB more pinned memory, reserved then): nothing is lost.
+ * Not part of this mode: valid lengths per buffer, seam trials scored on the device, and seams in adsb_multi and
+ * adsb_feed.
+ * Test hooks (results never depend on them).  tune: the seam list and record block of the passes submitted from now on
+ * hold list_cap entries (0 = the default; never more than was reserved); ADSB_ERR_BUSY while passes are pending.
+ * counters, out4: [0] passes with a seam step, [1] seam records handed to the replay, [2] records of the pass itself
+ * dropped for j < 326, [3] seam steps redone after an overflow. */
+#define ADSB_RX_ALL 0xFFFFFFFFu
+int adsb_set_receiver_carry(adsb_ctx *ctx, int enabled);
+int adsb_get_receiver_carry(const adsb_ctx *ctx);
+int adsb_receiver_carry_reset(adsb_ctx *ctx, uint32_t receiver);
+int adsb_selftest_rx_seam_tune(adsb_ctx *ctx, uint32_t list_cap);
+int adsb_selftest_rx_seam_counters(const adsb_ctx *ctx, uint64_t *out4);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Decimation -- IQ sampled at an integer multiple of 2.4 MS/s.  Every entry point above takes IQ at exactly 2.4 MS/s;
  * a HackRF, bladeRF, USRP or Airspy runs at 4.8, 9.6, 12, 19.2 or 24 MS/s.  An adsb_decim is a stateful, exact-integer
  * FIR decimator by an integer factor D that runs on the device in front of the scan, in a kernel of its own: its output
