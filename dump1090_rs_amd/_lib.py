@@ -260,6 +260,11 @@ def lib() -> C.CDLL:
     L.adsb_selftest_gate_stages.restype = C.c_int
     L.adsb_selftest_set_order_polls.argtypes = [vp, C.c_uint32]
     L.adsb_selftest_set_order_polls.restype = C.c_int
+    # (hooks reached by name, not declared in include/adsb_hip.h: k_scan_sparse on / off for a context, and its launches)
+    L.adsb_selftest_set_sparse_scan.argtypes = [vp, C.c_int]
+    L.adsb_selftest_set_sparse_scan.restype = C.c_int
+    L.adsb_selftest_sparse_scans.argtypes = [vp]
+    L.adsb_selftest_sparse_scans.restype = C.c_uint64
     L.adsb_selftest_crc_table.argtypes = [vp]
     L.adsb_selftest_crc_table.restype = C.c_int
     L.adsb_selftest_learned_union.argtypes = [vp, sz, vp, sz, vp, sz, C.POINTER(sz)]

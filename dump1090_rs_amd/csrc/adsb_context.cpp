@@ -1006,6 +1006,6 @@ int adsb_get_stats(const adsb_ctx *c, adsb_stats *out)
 
 const char *adsb_last_error(const adsb_ctx *c) { return c ? c->last_error.c_str() : ""; }
 
-const char *adsb_version(void) { return "adsb_hip 0.22 gfx950 scan=v9-tile-buckets tail=v8-sparse-lean multi=v3-bounded-waits streams=v2-own-queues stats=v1 rxscore=v1"; }
+const char *adsb_version(void) { return "adsb_hip 0.23 gfx950 scan=v10-sparse-folded tail=v8-sparse-lean multi=v3-bounded-waits streams=v2-own-queues stats=v1 rxscore=v1"; }
 
 }  // extern "C"

@@ -223,6 +223,8 @@ struct adsb_ctx {
     int fresh_slot = -1;
     uint64_t rematches = 0;                 // one-launch passes redone because a pass in flight beside them did
     uint32_t order_polls = 200;             // ScanParams::order_polls (adsb_selftest_set_order_polls)
+    bool sparse_scan = true;                // eligible passes run k_scan_sparse (adsb_selftest_set_sparse_scan; off: k_scan_fast, the A/B)
+    uint64_t sparse_scans = 0;              // ... how many have (adsb_selftest_sparse_scans)
     const unsigned long long *next_src_ready = nullptr;  // ScanParams::src_ready of the next pass enqueued (adsb_demod_iq)
     // adsb_host_register: the caller's buffers, pinned and mapped (adsb_demod_iq reads samples inside them in place)
     struct HostRange {

@@ -364,7 +364,10 @@ int launch_widen_u8(const void *d_src, uint64_t first, uint32_t count, const uin
 // zero a counters block and, when `bitmap` is non-null, clear an address bitmap (bit 0 stays
 // set); only needed once per context: afterwards every pass cleans up for the next one
 int launch_reset(Counters *ctr, uint32_t *bitmap, uint32_t bitmap_lg, void *stream);
-int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream);   // fast (IQ) or simple (mag)
+// fast (IQ) or simple (mag).  sparse_ok: the caller lets a pass that uses none of the scan's optional features (the sparse
+// stream of a large context: adsb_scan_fast.hip, sparse_scan_eligible) run k_scan_sparse, the same scan with those
+// features folded out; *ran_sparse says whether this launch did
+int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream, bool sparse_ok = false, bool *ran_sparse = nullptr);
 // the whole pass in one launch (p.fused_rec set): one workgroup per tile, the last one to finish matches
 // what the pass learned late, builds the records and publishes the summary; for passes of a few buffers
 int launch_pass_fused(const ScanParams &p, SrcFormat fmt, void *stream);

@@ -374,9 +374,11 @@ static int launch_scan_step(adsb_ctx *c, Slot &sl, ScanParams &p, SrcFormat fmt,
                                   hipMemcpyDeviceToDevice, ss));
     {
         HT(c, HT_SCAN_LAUNCH);
+        bool ran_sparse = false;
         if (int e = pl.fused ? launch_pass_fused(p, fmt, ss)
-                             : (opt.force_simple ? launch_scan_simple(p, fmt, ss) : launch_scan(p, fmt, ss)))
+                             : (opt.force_simple ? launch_scan_simple(p, fmt, ss) : launch_scan(p, fmt, ss, c->sparse_scan, &ran_sparse)))
             return fail(c, (hipError_t)e, "launch_scan");
+        if (ran_sparse) c->sparse_scans++;
     }
     if (pl.classic) HIP_TRY(c, hipEventRecord(sl.ev[1], ss));
     if (hand_carry_on) {

@@ -916,6 +916,43 @@ __global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIG
 #include "adsb_scan_fast_body.inc"
 }
 
+// The sparse stream's scan in a large context (the headline pass), the same body once more: every feature such a pass
+// never uses is a run-time field of ScanParams that k_scan_fast has to test, and here a constant.  The kernel takes
+// the pass's parameters as they are, copies them and overwrites exactly the fields sparse_scan_eligible() below has
+// checked; the compiler carries the constants through the body -- the dense buckets, the shard's fresh-address list,
+// the folded bitmap's index, the carry-over loads and their scalar registers go (no SGPR spill is left).  The same
+// template header as k_scan_fast, so that the body's `if constexpr` blocks are discarded alike; only
+// <false, false, false, false, false> exists.  The LDS and launch bounds of k_scan_fast: the same occupancy.
+// Whoever adds a field here adds its test to sparse_scan_eligible(), and the other way round.
+template <bool FROM_MAG, bool SELFTEST = false, bool FUSED = false, bool FIELDS = false, bool U8 = false>
+__global__ __launch_bounds__(kThreads, FUSED ? 2 : kWavesPerSimd) ADSB_NO_UNALIGNED void k_scan_sparse(ScanParams q)
+{
+    static_assert(!FROM_MAG && !SELFTEST && !FUSED && !FIELDS && !U8, "the sparse CS16 scan of a large context only");
+    __shared__ FastLds s;
+    __shared__ FusedLds<FUSED> fs;
+    __shared__ HitFieldLds<FIELDS, FUSED> hf;
+    constexpr bool FIX = false, FIX2 = false;
+    uint32_t *const fixt = nullptr;
+    ScanParams p = q;
+    p.cand_out = nullptr;
+    p.hit_fields = nullptr;
+    p.fix = 0;
+    p.bitmap_lg = kFullBitmapLg;
+    p.bitmap_fresh = 0;
+    p.fresh = nullptr;
+    p.fresh_seen = nullptr;
+    p.order_cnt = nullptr;
+    p.carry = nullptr;
+    p.lead_from_src = 0;
+    p.fused_rec = nullptr;
+    p.src_ready = nullptr;
+    p.src_host = 0;
+    p.timeline = nullptr;
+    p.debug_stop = 0;
+    p.score.si = nullptr;
+#include "adsb_scan_fast_body.inc"
+}
+
 inline int hip_ok(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 // hipGetLastError is sticky across unrelated calls (the caller's too): start every launch clean
 inline void hip_clear() { (void)hipGetLastError(); }
@@ -996,9 +1033,30 @@ int launch_pass_fused(const ScanParams &p, SrcFormat fmt, void *stream)
     return hip_ok(hipGetLastError());
 }
 
-int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream)
+// The passes k_scan_sparse may run: every field that kernel replaces by a constant has that constant's value.  One
+// line per field, with the feature that sets it -- a new run-time feature of the scan gets its line here and its
+// constant in k_scan_sparse, or the sparse stream's kernel computes something else than k_scan_fast would.
+// (The ablation and timeline tools set debug_stop / timeline, in a tuning build: they go on measuring k_scan_fast.)
+static bool sparse_scan_eligible(const ScanParams &p, SrcFormat fmt)
+{
+    return fmt == SrcFormat::kCs16          // CU8 (adsb_demod_iq_u8 ...) and a caller's MagnitudeBuffer: instantiations of their own
+           && !p.cand_out                   // adsb_selftest_stage_lists / _gate_stages: the self-test instantiation
+           && !p.hit_fields                 // dense streams and one-launch passes: the FIELDS instantiations
+           && !p.fix                        // adsb_set_error_correction: k_scan_fix / k_scan_fix2
+           && p.bitmap_lg == kFullBitmapLg  // folded bitmaps: contexts for passes of a few buffers
+           && !p.bitmap_fresh               // ... whose one-launch pass clears the next bitmap itself
+           && !p.fresh && !p.fresh_seen     // first phase of a shard of an adsb_multi: the fresh-address list
+           && !p.order_cnt                  // dense streams: device-side ordering (tile buckets)
+           && !p.carry && !p.lead_from_src  // adsb_set_carry_over, receiver seams: the lead-in from the previous call
+           && !p.fused_rec && !p.src_ready && !p.src_host   // one-launch passes (launch_pass_fused)
+           && !p.timeline && !p.debug_stop  // ADSB_TIMELINE / ADSB_DEBUG_STOP (tuning builds)
+           && !p.score.si;                  // device-side scoring (dense streams, scored shards)
+}
+
+int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream, bool sparse_ok, bool *ran_sparse)
 {
     hip_clear();
+    if (ran_sparse) *ran_sparse = false;
     const uint32_t tiles = p.n_chunks * kTilesPerChunk;
     if (tiles == 0) return 0;
     const int resident = scan_resident_blocks();
@@ -1007,6 +1065,18 @@ int launch_scan(const ScanParams &p, SrcFormat fmt, void *stream)
     // With events, the launch itself carries them (hipExtLaunchKernelGGL): the dispatch
     // packet's own begin/end timestamps, no barrier packets in the stream around it.
     const bool ev = p.ev_start && p.ev_stop;
+    if (sparse_ok && sparse_scan_eligible(p, fmt)) {
+        // (the grid of k_scan_fast: the same LDS and launch bounds and fewer registers, so what scan_resident_blocks()
+        // found resident for that kernel is resident for this one)
+        if (ev)
+            hipExtLaunchKernelGGL((k_scan_sparse<false, false, false, false, false>), dim3(blocks), dim3(kThreads), 0, st,
+                                  (hipEvent_t)p.ev_start, (hipEvent_t)p.ev_stop, 0, p);
+        else
+            hipLaunchKernelGGL((k_scan_sparse<false, false, false, false, false>), dim3(blocks), dim3(kThreads), 0, st, p);
+        const int rc = hip_ok(hipGetLastError());
+        if (ran_sparse) *ran_sparse = rc == 0;
+        return rc;
+    }
     if (fmt == SrcFormat::kCu8) {   // CU8: the same choice of instantiation as for CS16 below, without the self-test's
         if (!p.u8_table || p.cand_out) return (int)hipErrorInvalidValue;
         if (p.hit_fields) launch_fast<false, false, true, true>(p, blocks, st, ev);

@@ -187,4 +187,16 @@ int adsb_selftest_set_order_polls(adsb_ctx *c, uint32_t polls)
     return ADSB_OK;
 }
 
+// Test and measurement hooks, reached by name (not in include/adsb_hip.h): whether the passes of this context that are
+// eligible for it run k_scan_sparse (on by default; off: k_scan_fast, for an A/B in one process), and how many have.
+int adsb_selftest_set_sparse_scan(adsb_ctx *c, int on)
+{
+    if (!c) return ADSB_ERR_INVALID;
+    if (c->submitted != c->delivered) return ADSB_ERR_BUSY;
+    c->sparse_scan = on != 0;
+    return ADSB_OK;
+}
+
+uint64_t adsb_selftest_sparse_scans(const adsb_ctx *c) { return c ? c->sparse_scans : 0; }
+
 }  // extern "C"

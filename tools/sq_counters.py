@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """SQ / GRBM counter passes over bench.py for k_scan_fast, raw rows kept.
 
-    python3 tools/sq_counters.py <tag> [--pipelined]      (on the GPU box, from the repo root)
+    python3 tools/sq_counters.py <tag> [--pipelined] [--counters A,B,...]      (on the GPU box, from the repo root)
 
 Runs rocprofv3 --pmc in separate passes (8 SQ slots per pass on gfx950, MI355X_MICROARCH.md
 "rocprofv3 PMC slots"), each with --kernel-trace only, over
@@ -12,6 +12,7 @@ Runs rocprofv3 --pmc in separate passes (8 SQ slots per pass on gfx950, MI355X_M
 gpurun_out/<tag>/sq_counters.json: per-launch averages of every counter over the k_scan_fast
 dispatches of the 256 MiB workload, the derived VALU roofline, and the raw per-dispatch rows of
 the first launches (so that the averages can be recomputed from the file).  Copy it to profiles/.
+--counters: ONE pass with the counters named (at most 8), instead of the three passes below.
 
 SQ_WAVE_CYCLES / SQ_BUSY_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles (4 shader
 clocks); SQ_INSTS_* count wave-instructions.  This process never touches the GPU itself: it only
@@ -24,6 +25,7 @@ import csv
 import glob
 import json
 import os
+import re
 import subprocess
 import sys
 from pathlib import Path
@@ -64,19 +66,26 @@ def main():
     bench_args = ["--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-also"]
     if not pipelined:
         bench_args.insert(0, "--sync")
+    passes = PASSES
+    if "--counters" in sys.argv:
+        passes = [sys.argv[sys.argv.index("--counters") + 1].split(",")]
+        assert 1 <= len(passes[0]) <= 8, "one pass holds 8 SQ counters"
+    kernels = set()
     per_dispatch = collections.defaultdict(dict)  # (pass, dispatch id) -> counter -> value
     grid, dur_ns = {}, {}
     library = None
     lines = []
-    for k, counters in enumerate(PASSES):
+    for k, counters in enumerate(passes):
         rows, line, rc = run_pass(tag, k, counters, bench_args)
         lines.append({"pass": k, "rc": rc, "ms_per_step": line and line.get("ms_per_step"),
                       "kernel_avg_ms": line and line["roofline"].get("kernel_avg_ms")})
         if line:
             library = line["config"]["library"]
         for r in rows:
-            if "k_scan_fast" not in r["Kernel_Name"]:
+            # (the headline pass runs k_scan_sparse, the folded form of k_scan_fast<false>, from library 0.23 on)
+            if "k_scan_fast" not in r["Kernel_Name"] and "k_scan_sparse" not in r["Kernel_Name"]:
                 continue
+            kernels.add(re.search(r"k_scan_\w+(<[^>]*>)?", r["Kernel_Name"]).group(0))
             did = (k, int(r["Dispatch_Id"]))
             per_dispatch[did][r["Counter_Name"]] = per_dispatch[did].get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
             grid[did] = int(r.get("Grid_Size", 0) or 0)
@@ -96,10 +105,11 @@ def main():
     n = {k: len(v) for k, v in agg.items()}
     out = {"library": library, "chunks": 512,
            "what": "rocprofv3 --pmc passes over `python3 bench.py " + " ".join(bench_args) + "`, per-launch averages for "
-                   "adsb::k_scan_fast<false> (full-grid launches of the 256 MiB workload only)",
+                   "the sparse scan kernel (full-grid launches of the 256 MiB workload only)",
+           "kernels": sorted(kernels),
            "units": "SQ_*_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* : quad-cycles summed over all waves (or SIMDs for BUSY); "
                     "SQ_INSTS_* : wave-instructions; GRBM_GUI_ACTIVE: shader clocks the GPU was busy",
-           "passes": PASSES, "bench_lines": lines, "launches_averaged": n, "per_launch_avg": {k: round(v, 1) for k, v in avg.items()},
+           "passes": passes, "bench_lines": lines, "launches_averaged": n, "per_launch_avg": {k: round(v, 1) for k, v in avg.items()},
            "grid_size": full}
     durs = [dur_ns[d] for d in per_dispatch if grid[d] == full]
     try:

@@ -14,6 +14,8 @@ Without --round-child this is a driver: R rounds, each a process of its own unde
   dense     the same on 5000 bursts per 512 buffers (`also.config5_dense`: device-ordered, device-scored passes);
   unordered blocking passes over the 5000-burst buffer in a context that is in sparse mode when they are submitted (a
             sparse pass between them switches it back): the host-ordered tail at 17 000 hits, ms per pass.
+  alone     blocking sparse passes (bench.py --sync's shape): a scan launch on its own, timed by the launch's own events
+            (adsb_stats.ms_scan); kernel_avg_ms = the mean over a block of 20, the libraries taking turns block by block.
 The summary: per library and leg the median over the rounds and their min-max; for every library but the parent the fall
 of its median against the parent's and whether that clears the parent's own min-max spread over its rounds
 (`clears_parent_spread`).  Lines go to stdout and, with --out, are appended to DIR/tail_rate.jsonl.
@@ -58,6 +60,7 @@ def load(path):
     L.adsb_destroy.argtypes = [C.c_void_p]
     L.adsb_destroy.restype = None
     L.adsb_version.restype = C.c_char_p
+    L.adsb_get_stats.argtypes = [C.c_void_p, C.c_void_p]
     return L
 
 
@@ -163,6 +166,39 @@ def unordered(torch, libs, passes=8):
     return res
 
 
+def alone(torch, libs, blocks=4):
+    """Blocking sparse passes, a launch on its own: per library the scan's duration by its own launch's events."""
+    import ctypes as C
+    from dump1090_rs_amd import synth
+    from dump1090_rs_amd._lib import AdsbMsg, AdsbStats
+    n = 512 * CHUNK
+    bufs = [synth.make_iq_torch(n, n_bursts=64, seed=synth.SEED_DEFAULT + b, device="cuda") for b in range(3)]
+    want = [oracle_frames(b.cpu().numpy()) for b in bufs]
+    torch.cuda.synchronize()
+    cap = 1 << 16
+    out, cnt, st = (AdsbMsg * cap)(), C.c_size_t(), AdsbStats()
+    ctx, t, ok = {}, {k: [] for k in libs}, {k: True for k in libs}
+    for name, L in libs.items():
+        h = C.c_void_p()
+        assert L.adsb_create(C.byref(h), 0, 512) == 0 and L.adsb_set_profiling(h, 1) == 0
+        ctx[name] = h
+    for b in range(blocks + 1):   # (the first block of each library: warm-up and clock ramp, not counted)
+        for name, L in libs.items():
+            ms = []
+            for k in range(PER_BLOCK):
+                assert L.adsb_icao_flush(ctx[name]) == 0
+                assert L.adsb_demod_iq_device(ctx[name], C.c_void_p(bufs[k % 3].data_ptr()), n, out, cap, C.byref(cnt)) == 0
+                assert L.adsb_get_stats(ctx[name], C.byref(st)) == 0
+                ms.append(float(st.ms_scan))
+                ok[name] = ok[name] and got_frames(out, cnt.value) == want[k % 3]
+            if b:
+                t[name].append(statistics.mean(ms))
+    for name, L in libs.items():
+        L.adsb_destroy(ctx[name])
+    return {name: {"kernel_avg_ms": round(statistics.mean(t[name]), 5), "kernel_avg_ms_blocks": [round(x, 5) for x in t[name]],
+                   "parity": ok[name]} for name in libs}
+
+
 def kernel_only(path):
     """12 pipelined blocks of 20 sparse steps, then 30 blocking passes, on one library, unchecked: the run to put under
     `rocprofv3 --kernel-trace` for tools/tail_trace.py (the tail kernels beside a scan, and alone)."""
@@ -204,7 +240,7 @@ def round_child(a, libs_spec):
     ver = {name: L.adsb_version().decode() for name, L in libs.items()}
     lines = []
     legs = [("sparse", lambda: pipelined(torch, libs, 64, 0)), ("dense", lambda: pipelined(torch, libs, 5000, 2)),
-            ("unordered", lambda: unordered(torch, libs))]
+            ("unordered", lambda: unordered(torch, libs)), ("alone", lambda: alone(torch, libs))]
     for leg, run in legs:
         if a.only and leg != a.only:
             continue
@@ -224,7 +260,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--label", default=None)
-    ap.add_argument("--only", default=None, help="one leg: sparse, dense, unordered")
+    ap.add_argument("--only", default=None, help="one leg: sparse, dense, unordered, alone")
     ap.add_argument("--round-child", type=int, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.kernel_only:
@@ -247,8 +283,8 @@ def main():
             print(json.dumps({"error": "round %d ended with status %d" % (r, p.returncode)}), flush=True)
             return 1   # (nothing more is started on the device behind a failed round)
     summary = []
-    for leg in ("sparse", "dense", "unordered"):
-        fig = "ms_per_pass" if leg == "unordered" else "ms_per_step"
+    for leg in ("sparse", "dense", "unordered", "alone"):
+        fig = {"unordered": "ms_per_pass", "alone": "kernel_avg_ms"}.get(leg, "ms_per_step")
         per = {}
         for ln in lines:
             if ln["leg"] == leg:
@@ -260,7 +296,7 @@ def main():
             v = [ln[fig] for ln in rows]
             s = {"summary": leg, "library": name, "version": rows[0]["version"], "rounds": len(v), fig: statistics.median(v),
                  "spread": [min(v), max(v)], "parity": all(ln["parity"] for ln in rows)}
-            if leg != "unordered":
+            if leg in ("sparse", "dense"):
                 s["ms_per_step_median"] = statistics.median(ln["ms_per_step_median"] for ln in rows)
                 s["ms_per_step_blocks_median"] = statistics.median(x for ln in rows for x in ln["ms_per_step_blocks"])
             if name != "parent":
