@@ -332,8 +332,14 @@ def lib() -> C.CDLL:
     L.adsb_receiver_carry_reset.argtypes = [vp, u32]
     L.adsb_selftest_rx_seam_tune.argtypes = [vp, u32]
     L.adsb_selftest_rx_seam_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.adsb_set_receiver_carry_scoring.argtypes = [vp, C.c_int]
+    L.adsb_get_receiver_carry_scoring.argtypes = [vp]
+    L.adsb_selftest_rx_seam_score_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.adsb_selftest_reservations.argtypes = [vp]
+    L.adsb_selftest_reservations.restype = C.c_uint64
     for name in ("adsb_set_receiver_carry", "adsb_get_receiver_carry", "adsb_receiver_carry_reset", "adsb_selftest_rx_seam_tune",
-                 "adsb_selftest_rx_seam_counters"):
+                 "adsb_selftest_rx_seam_counters", "adsb_set_receiver_carry_scoring", "adsb_get_receiver_carry_scoring",
+                 "adsb_selftest_rx_seam_score_counters"):
         getattr(L, name).restype = C.c_int
     L.adsb_rx_set_home.restype = u32
     for name in ("adsb_set_receiver_scoring", "adsb_get_receiver_scoring", "adsb_selftest_rx_score_counters",

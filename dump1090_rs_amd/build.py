@@ -18,11 +18,11 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libadsb_hip.so"
-SOURCES = [CSRC / "adsb_scan_fast.hip", CSRC / "adsb_scan_simple.hip", CSRC / "adsb_aux.hip", CSRC / "adsb_score_rx.hip", CSRC / "adsb_stats.hip", CSRC / "adsb_decim.hip", CSRC / "adsb_resamp.hip", CSRC / "adsb_instat.hip", CSRC / "adsb_seam.hip",
+SOURCES = [CSRC / "adsb_scan_fast.hip", CSRC / "adsb_scan_simple.hip", CSRC / "adsb_aux.hip", CSRC / "adsb_score_rx.hip", CSRC / "adsb_stats.hip", CSRC / "adsb_decim.hip", CSRC / "adsb_resamp.hip", CSRC / "adsb_instat.hip", CSRC / "adsb_seam.hip", CSRC / "adsb_seam_score.hip",
            *(CSRC / f for f in ("adsb_context.cpp", "adsb_pass.cpp", "adsb_collect.cpp", "adsb_ring.cpp", "adsb_decim.cpp", "adsb_resamp.cpp", "adsb_bank.cpp", "adsb_mix.cpp", "adsb_fmt.cpp", "adsb_instat.cpp", "adsb_seam.cpp",
                                 "adsb_shard.cpp", "adsb_multi.cpp", "adsb_selftest.cpp", "adsb_replay_host.cpp"))]
 HEADERS = [CSRC / "adsb_ctx.h", CSRC / "adsb_device.h", CSRC / "adsb_dev_common.h", CSRC / "adsb_mix_dev.h", CSRC / "adsb_fmt_dev.h", CSRC / "adsb_scan_geometry.h",
-           CSRC / "adsb_tables.h", CSRC / "adsb_tail_dev.h", CSRC / "adsb_fix_dev.h", CSRC / "adsb_score_dev.h", CSRC / "adsb_record.h", CSRC / "adsb_replay_host.h", CSRC / "mode_s_host.hpp", PKG.parent / "include" / "adsb_hip.h",
+           CSRC / "adsb_tables.h", CSRC / "adsb_tail_dev.h", CSRC / "adsb_fix_dev.h", CSRC / "adsb_score_dev.h", CSRC / "adsb_seam_score_dev.h", CSRC / "adsb_record.h", CSRC / "adsb_replay_host.h", CSRC / "mode_s_host.hpp", PKG.parent / "include" / "adsb_hip.h",
            CSRC / "adsb_scan_fast_body.inc", CSRC / "adsb_resamp_body.inc", CSRC / "adsb_resamp_host.h"]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

@@ -645,6 +645,25 @@ class Context:
         self._check(self._L.adsb_selftest_rx_seam_counters(self._h, out), "adsb_selftest_rx_seam_counters")
         return {"passes": int(out[0]), "records": int(out[1]), "dropped": int(out[2]), "redone": int(out[3])}
 
+    def set_receiver_carry_scoring(self, enabled: bool) -> None:
+        """adsb_set_receiver_carry_scoring: receiver seams AND per-receiver scoring on the device, entered and left
+        together (include/adsb_hip.h, "Receiver seams, scored on the device")."""
+        self._check(self._L.adsb_set_receiver_carry_scoring(self._h, 1 if enabled else 0), "adsb_set_receiver_carry_scoring")
+
+    def get_receiver_carry_scoring(self) -> bool:
+        return int(self._L.adsb_get_receiver_carry_scoring(self._h)) == 1
+
+    def selftest_rx_seam_score_counters(self) -> dict:
+        """adsb_selftest_rx_seam_score_counters: passes with a device-side seam merge / seam records merged on the device /
+        own hits dropped there for j < 326 / merged passes that declared themselves unscored."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.adsb_selftest_rx_seam_score_counters(self._h, out), "adsb_selftest_rx_seam_score_counters")
+        return {"merged_passes": int(out[0]), "seam_records": int(out[1]), "dropped": int(out[2]), "unscored": int(out[3])}
+
+    def selftest_reservations(self) -> int:
+        """adsb_selftest_reservations: what the context's owner holds now (device blocks, pinned blocks and events)."""
+        return int(self._L.adsb_selftest_reservations(self._h))
+
     def set_receiver_scoring(self, enabled: bool) -> None:
         """adsb_set_receiver_scoring: dense passes of a receivers context are scored on the device, a filter per receiver."""
         self._check(self._L.adsb_set_receiver_scoring(self._h, 1 if enabled else 0), "adsb_set_receiver_scoring")

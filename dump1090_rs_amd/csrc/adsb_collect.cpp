@@ -81,7 +81,11 @@ bool apply_adds_rx(adsb_ctx *c, const Slot &sl, size_t na)
 bool take_device_result(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, std::vector<adsb_msg> &out)
 {
     const bool rx = sl.rx_scored;   // (implies device_scored: fill_pass)
-    if (!sl.device_scored || sl.score_epoch != c->score_epoch) return false;
+    if (!sl.device_scored) return false;
+    // (receiver seams scored on the device: the merge ran, whatever becomes of its result -- counted from its own summary,
+    // behind the pass's `done`, also for a pass that is disowned below)
+    count_seam_merge(c, sl);
+    if (sl.score_epoch != c->score_epoch) return false;
     const ScoreSummary *ss = sl.h_ssum;
     if (__atomic_load_n(&ss->seq, __ATOMIC_ACQUIRE) != sl.seq) return false;
     if (rx && ss->no_room) c->rx_no_room++;   // (counted whether or not the pass says it was scored: it never does then)
@@ -267,7 +271,9 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
     if (sl.fused && sl.unsynced_from && c->last_new_insert_seq >= sl.unsynced_from) return 2;
     // Receiver seams: the seam step's records, once per pass (the overflow fallback's one-buffer passes find them taken;
     // so does a pass whose seam collect_oldest redid).  Its k_seam_match ran behind the pass's last kernel.
-    if (sl.seam_on && !c->seam_taken)
+    // (A pass whose seam records were merged on the device, sl.seam_scored, needs them on the host only when its device
+    // result is refused: below, then.)
+    if (sl.seam_on && !c->seam_taken && !sl.seam_scored)
         if (int rc = take_seam(c, sl)) return rc;
     const size_t n = sl.h_sum->n_hits;
     // (k_records' own test: a pass that k_score took over has left its records in device memory)
@@ -328,8 +334,11 @@ int finish_pass(adsb_ctx *c, Slot &sl, uint64_t chunk_offset, adsb_stats &st, st
         if (n >= 8u * (size_t)sl.n_chunks) c->dense_mode = true;
         else if (n < 2u * (size_t)sl.n_chunks) c->dense_mode = false;
     }
+    // (a merged pass taken from the device: the host neither merges nor replays its seam records)
     if (take_device_result(c, sl, chunk_offset, out)) return 0;
     if (sl.rx_scored) c->rx_scored_refused++;
+    if (sl.seam_on && !c->seam_taken)   // (sl.seam_scored and refused: the seam records after all, redone where they overflowed)
+        if (int rc = take_seam(c, sl)) return rc;
     if (rec_on_device && n) {
         HIP_TRY(c, hipMemcpy(sl.h_rec, sl.score.rec, n * sizeof(TrialRecord), hipMemcpyDeviceToHost));
         if (int rc = verify_records(c, sl.h_sum, sl.h_rec, n)) return rc;

@@ -868,7 +868,12 @@ try {
     c->rx_set_valid = c->rx_set_full = c->rx_held_valid = false;
     if (c->rx_scoring) {   // the keyed sets are sized from the number of receivers
         ADSB_ON_DEVICE(c);
-        if (int rc = ensure_rx_scoring(c)) return rc;
+        if (int rc = ensure_rx_scoring(c)) {
+            // (both modes on, adsb_set_receiver_carry_scoring: the seams' storage is sized by the number of receivers too and
+            // must not stay at the old one -- re-sized all the same; without keyed sets the passes are the host's)
+            if (c->rx_carry && c->seam_receivers_changed) (void)c->seam_receivers_changed(c);
+            return rc;
+        }
     }
     if (c->rx_carry && c->seam_receivers_changed) {   // receiver seams: every stream restarts; n = 0 turns the mode off
         ADSB_ON_DEVICE(c);
@@ -928,6 +933,8 @@ int adsb_set_receiver_scoring(adsb_ctx *c, int enabled)
 try {
     if (!c) return ADSB_ERR_INVALID;
     if (c->submitted != c->delivered || c->shard_active) return ADSB_ERR_BUSY;
+    // (adsb_set_receiver_carry_scoring holds both modes on: the value in effect is fine, a change is not)
+    if (c->rx_carry_scoring) return enabled ? ADSB_OK : ADSB_ERR_INVALID;
     if (enabled && c->rx_carry) return ADSB_ERR_INVALID;   // (seam trials are scored by the host: adsb_set_receiver_carry)
     if (enabled && !c->rx_scoring) {
         ADSB_ON_DEVICE(c);

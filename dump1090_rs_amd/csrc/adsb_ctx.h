@@ -147,6 +147,15 @@ struct Slot {
     SeamCounters *d_seam_ctr = nullptr;
     uint32_t *d_seam_lead = nullptr;
     TrialRecord *d_seam_list = nullptr;
+    // ... scored on the device (adsb_set_receiver_carry_scoring; all null until that mode is first enabled in a context
+    // that scores on the device): whether this pass went through the device-side merge (adsb_seam_score.hip), the merge's
+    // parameters -- the merged arrays, the mirror of the seam records, the work arrays: views into the context's one device
+    // block -- its summary in mapped host memory, and the event behind the pass's k_seam_match that the score stream
+    // waits for (`recorded` stays where it is: other passes wait for it before they clear a bitmap)
+    bool seam_scored = false;
+    SeamMergeParams merge{};
+    SeamMergeSummary *h_merge_sum = nullptr, *h_merge_sum_dev = nullptr;
+    hipEvent_t seam_matched = nullptr;
 };
 
 // Passes in flight: 4 and the device never waits for the host between large passes (3 do for sparse
@@ -410,6 +419,14 @@ struct adsb_ctx {
     // the first enable, so that adsb_context.cpp refers to nothing of adsb_seam.cpp -- tests/test_context_lifetime_cpu.py
     // links adsb_context.cpp against a fake runtime WITHOUT that unit, as InStat::count is installed for adsb_instat.cpp
     int (*seam_receivers_changed)(adsb_ctx *c) = nullptr;
+    // Receiver seams scored on the device (adsb_set_receiver_carry_scoring; include/adsb_hip.h, "Receiver seams, scored on
+    // the device"): rx_carry AND rx_scoring, entered and left together.  A pass of the mode that is scored on the device
+    // has its seam records merged into its ordered hits there (adsb_seam_score.hip), in a second set of score arrays per
+    // slot: one device block and one small mapped block for all slots, reserved by the enable where the context scores on
+    // the device at all, released when the mode goes off.
+    bool rx_carry_scoring = false;
+    char *d_merge_block = nullptr, *h_merge_block = nullptr, *h_merge_block_dev = nullptr;
+    uint64_t seam_sc_passes = 0, seam_sc_records = 0, seam_sc_dropped = 0, seam_sc_unscored = 0;   // adsb_selftest_rx_seam_score_counters
     uint32_t rx_set_lg() const { return rx_tune_lg ? std::min(rx_tune_lg, rx_set_alloc_lg) : rx_set_alloc_lg; }
     uint32_t rx_probe_max() const { return rx_tune_probe ? rx_tune_probe : kRxProbeMax; }
 };
@@ -661,6 +678,12 @@ int seam_front(adsb_ctx *c, Slot &sl, ScanParams &p, SrcFormat fmt, bool plain_i
 int seam_tail(adsb_ctx *c, Slot &sl, hipStream_t ts);
 int take_seam(adsb_ctx *c, Slot &sl);
 int redo_seam(adsb_ctx *c, Slot &sl);
+// ... scored on the device (adsb_set_receiver_carry_scoring).  seam_merge: for a pass with sl.seam_scored, in front of the
+// keyed kernels on the score stream `qs` -- behind the pass's k_seam_match (Slot::seam_matched) the device-side merge, and
+// in *pm the pass's parameters with the merged arrays for launch_score_rx; any other pass: *pm = p, nothing launched.
+// count_seam_merge: at collect, the merge's summary into the mode's counters (once per pass scored on the device).
+int seam_merge(adsb_ctx *c, Slot &sl, const ScanParams &p, ScanParams *pm, hipStream_t qs);
+void count_seam_merge(adsb_ctx *c, const Slot &sl);
 
 // adsb_collect.cpp
 int verify_records(adsb_ctx *c, const Summary *sum, const TrialRecord *rec, size_t n);

@@ -582,10 +582,53 @@ struct SeamParams {
     SeamCounters *ctr;
     SeamSummary *summary;    // mapped host memory
     uint32_t seq;
+    // receiver seams scored on the device (adsb_set_receiver_carry_scoring), both null everywhere else -- the kernels then
+    // do what they always did: a mirror of `rec` in device memory (rec_cap entries: the device-side merge never reads
+    // records back out of mapped host memory), and the word pair where k_seam_match leaves (n_rec, overflow) before it
+    // zeroes the counters.  After everything else, so that the fields above stay where they were.
+    TrialRecord *rec_dev;
+    uint32_t *note;
 };
 int launch_seam_lead(const SeamParams &q, void *stream);    // k_rx_lead, then k_rx_carry_update
 int launch_seam_scan(const SeamParams &q, void *stream);    // k_seam_scan
 int launch_seam_match(const SeamParams &q, void *stream);   // k_seam_match: the list against the bitmap, then the summary
+// Receiver seams scored on the device (adsb_seam_score.hip; adsb_seam_score_dev.h has the index arithmetic): in front of
+// k_rx_adders on the score stream, the pass's seam records are merged into the records kernel's ordered arrays and the
+// pass's own hits at j < kLead dropped -- into a second set of arrays, which the three keyed kernels then take for the
+// pass's.  The first set stays as the records kernel left it (the host fetches ScoreDev::rec when it refuses the result).
+struct SeamMergeState {      // device memory, per slot; ticket and bad are zero between passes
+    uint32_t n_own;          // ScoreState::n as the records kernel left it
+    uint32_t n_seam;         // seam records of the pass (the note's n_rec)
+    uint32_t go;             // 1: the merged arrays are to be written and ScoreState::n is the merged count
+    uint32_t ticket;         // k_seam_place: workgroups that have finished (the last one cleans up)
+    uint32_t bad;            // k_seam_mark: a record that cannot be placed (a buffer or key out of range, a key twice)
+    uint32_t reserved[3];
+};
+struct SeamMergeSummary {    // mapped host memory, `seq` issued last
+    uint32_t merged;         // 1: the pass came scored from the records kernel and went through the merge
+    uint32_t n_seam;         // seam records merged
+    uint32_t dropped;        // own hits dropped for j < kLead
+    uint32_t unscored;       // 1: the merge declared the pass unscored (seam overflow, more merged hits than ScoreDev::cap)
+    uint32_t reserved[3];
+    uint32_t seq;
+};
+struct SeamMergeParams {
+    const TrialRecord *seam_rec;   // SeamParams::rec_dev
+    uint32_t seam_cap;             // ... and its entries
+    uint32_t *note;                // SeamParams::note; the merge zeroes it
+    ScoreDev merged;               // the pass's ScoreDev with rec, si, pos, slot and flag pointing at the merged arrays
+    uint32_t *present;             // n_chunks rows of kSeamKeyStride words: bit 5 j + try_phase - 4 of row b, all zero between passes
+    uint32_t *own_start;           // n_chunks + 1: the first own hit of every buffer
+    uint32_t *drop;                // n_chunks: own hits with j < kLead, all zero between passes
+    uint32_t *seam_base;           // n_chunks: where the buffer's first seam record lands
+    uint32_t *own_shift;           // n_chunks: what a kept own hit's index moves by
+    SeamMergeState *st;
+    SeamMergeSummary *summary;
+    uint32_t seq;
+};
+// k_seam_mark, k_seam_prefix, k_seam_place on `stream`, in that order; p: the pass's own parameters (p.score: the records
+// kernel's arrays, the plain first-adder table -- emptied here -- and the state)
+int launch_seam_merge(const ScanParams &p, const SeamMergeParams &m, void *stream);
 // self-test: out[i] = the repair k_score finds for residuals[i] under `mode` (adsb_fix_dev.h: fix_lookup), device memory
 int launch_fix_lookup(const uint32_t *tables, const uint32_t *d_residuals, uint32_t n, uint32_t mode, uint32_t *d_out, void *stream);
 

@@ -161,7 +161,10 @@ static int plan_pass(adsb_ctx *c, const Slot &sl, SrcFormat fmt, uint32_t n_chun
     // through the keyed kernels of adsb_score_rx.hip; otherwise its replay is the host's, buffer by buffer)
     const bool rx = c->n_receivers != 0;
     if (rx && c->flush_pending) c->rx_set_full = false;   // (every filter starts empty again: so can the keyed set)
-    const bool score_on_device = pl.ordered && c->score.si && (!rx || (c->rx_scoring && c->rx_set[0] && !c->rx_set_full));
+    // (receiver seams: only with the device-side merge's storage in hand, adsb_set_receiver_carry_scoring -- a seam pass
+    // scored without it would lack its seam records)
+    const bool score_on_device = pl.ordered && c->score.si && (!rx || (c->rx_scoring && c->rx_set[0] && !c->rx_set_full)) &&
+                                 (!c->rx_carry || c->d_merge_block);
     if (score_on_device && rx) {
         if (!c->rx_set_valid) {
             // the keyed set can only be rebuilt from the host's filters once every pass in flight has been replayed:
@@ -497,7 +500,11 @@ static int enqueue_score(adsb_ctx *c, Slot &sl, const ScanParams &p, const PassP
             // (the slot's previous pass read its copy earlier on this very stream)
             std::memcpy(sl.h_rx_map, sl.rx_map.data(), (size_t)p.n_chunks * sizeof(uint32_t));
             HIP_TRY(c, hipMemcpyAsync(sl.d_rx_map, sl.h_rx_map, (size_t)p.n_chunks * sizeof(uint32_t), hipMemcpyHostToDevice, qs));
-            if (int e = launch_score_rx(p, sl.rx, qs)) return fail(c, (hipError_t)e, "launch_score_rx");
+            // receiver seams scored on the device: behind the pass's k_seam_match (edge 4s) the seam records are merged
+            // into the ordered hits, and the keyed kernels take the merged arrays for the pass's (any other pass: pm = p)
+            ScanParams pm;
+            if (int rc = seam_merge(c, sl, p, &pm, qs)) return rc;
+            if (int e = launch_score_rx(pm, sl.rx, qs)) return fail(c, (hipError_t)e, "launch_score_rx");
         } else if (int e = launch_score(p, qs)) return fail(c, (hipError_t)e, "launch_score");
         ts = qs;
     }

@@ -58,6 +58,9 @@ __device__ __forceinline__ void seam_emit(const SeamParams &q, const TrialRecord
 #pragma unroll
     for (int k = 0; k < 4; k++) seam_store64(dst + k, w[k]);
     atomicAdd(&q.ctr->rec_sum, w[0] + w[1] + w[2] + w[3]);
+    // scored on the device (adsb_seam_score.hip): the same record into the mirror the merge reads, behind this pass's
+    // k_seam_match on another stream -- a kernel boundary and an event, like ScoreDev::rec
+    if (q.rec_dev) q.rec_dev[at] = r;
 }
 
 __device__ __forceinline__ bool seam_bitmap_test(const uint32_t *bitmap, uint32_t lg, uint32_t a)
@@ -227,6 +230,10 @@ __global__ __launch_bounds__(256) void k_seam_match(SeamParams q)
     // the counters back to zero, BEFORE the summary's sequence word goes out: the host may reuse the slot as soon as it
     // has seen that word, and the slot's next k_seam_scan (scan stream 0) need not be in stream order behind this kernel
     // (a three-launch pass's match runs on the tail stream)
+    if (q.note) {   // ... and what the device-side merge needs of them first
+        q.note[0] = vals[0];
+        q.note[1] = ovf;
+    }
     q.ctr->n_list = q.ctr->n_rec = q.ctr->overflow = q.ctr->reserved = 0;
     q.ctr->rec_sum = 0;
     __threadfence();

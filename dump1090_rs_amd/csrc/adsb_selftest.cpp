@@ -199,4 +199,7 @@ int adsb_selftest_set_sparse_scan(adsb_ctx *c, int on)
 
 uint64_t adsb_selftest_sparse_scans(const adsb_ctx *c) { return c ? c->sparse_scans : 0; }
 
+// what the context's owner holds now: device blocks, pinned blocks and events
+uint64_t adsb_selftest_reservations(const adsb_ctx *c) { return c ? (uint64_t)c->mem.entries.size() : 0; }
+
 }  // extern "C"

@@ -602,6 +602,60 @@ int adsb_selftest_rx_seam_tune(adsb_ctx *ctx, uint32_t list_cap);
 int adsb_selftest_rx_seam_counters(const adsb_ctx *ctx, uint64_t *out4);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Receiver seams, scored on the device -- adsb_set_receiver_carry AND adsb_set_receiver_scoring, which refuse each other
+ * as single modes (above: each says why), as one mode with an entry point of its own.  Opt-in, off by default; with it
+ * off nothing changes: no launch, no allocation, the two single setters behave as documented.
+ *
+ * Definition.  The "Receiver seams" definition, unchanged: the list equals one plain context WITH carry-over per receiver,
+ * relabelled and merged in (chunk, j), field for field, signal_level bit for bit, every receiver's filter table slot for
+ * slot, in all three error-correction modes, through every _rx call, its _u8 twin, submit / collect,
+ * adsb_ring_submit_rx and the plain IQ calls.  The only difference from adsb_set_receiver_carry alone is who scores: a
+ * pass the library orders on the device (a large context, more than 16 buffers, a stream that has left >= 8 trial records
+ * per buffer) takes its result from the device.
+ *
+ * How: behind the pass's seam match, on the score stream, kernels of their own merge the pass's seam records into the
+ * records kernel's ordered hits and drop the pass's own hits at j < 326 -- into a second set of score arrays, which the
+ * keyed score kernels of adsb_set_receiver_scoring then take for the pass's, unchanged.  The seam records reach that merge
+ * through a mirror in device memory.  A pass whose seam list or record block overflowed, or whose merged hits outnumber
+ * the score arrays, declares itself unscored on the device: the host then redoes the seam step in pieces and replays, as
+ * under adsb_set_receiver_carry, and the next pass scored on the device rebuilds the keyed set.  Every other pass of the
+ * mode (small contexts, passes of <= 16 buffers, sparse streams, caller-supplied magnitudes) is the host's, seams
+ * included, exactly as under adsb_set_receiver_carry.
+ *
+ *   adsb_set_receiver_carry_scoring(ctx, enabled)   ADSB_ERR_BUSY while passes are pending; ADSB_ERR_INVALID for a null
+ *                           context and with receivers off; ADSB_OK on every context size (a context that never orders a
+ *                           pass on the device keeps host-scoring its seam passes).  Enabling may come from any state of
+ *                           the two single modes, reserves what both reserve and the footprint below, and restarts every
+ *                           receiver's stream, as enabling adsb_set_receiver_carry does; afterwards
+ *                           adsb_get_receiver_carry and adsb_get_receiver_scoring both return 1.  While it is on,
+ *                           adsb_set_receiver_carry and adsb_set_receiver_scoring return ADSB_OK for the value in effect
+ *                           (1) and ADSB_ERR_INVALID for a change.  Disabling turns both off and releases the seams' and
+ *                           the merge's storage (the keyed sets stay reserved, as after adsb_set_receiver_scoring(ctx, 0));
+ *                           adsb_set_receivers(ctx, 0) turns the mode off; any other change of the receiver count
+ *                           restarts every stream and re-sizes both footprints.
+ *   adsb_get_receiver_carry_scoring   1 / 0, or ADSB_ERR_INVALID for a null context.
+ *   unchanged               adsb_receiver_carry_reset, adsb_icao_flush (switches to the empty keyed set) and
+ *                           adsb_icao_flush_receiver (still DRAINS while scoring is on) behave as documented for the
+ *                           single modes.
+ *   footprint               on top of both single modes', in a context that scores on the device.  Device, per pass in
+ *                           flight: 52 S bytes of merged score arrays (S the scored message slots of adsb_create's
+ *                           footprint), a mirror of the seam's record block (32 bytes x the seam list's entries) and 228
+ *                           max_chunks bytes of work arrays: about 1.4 MB at max_chunks = 20, about 15 MB at 512.  Pinned
+ *                           host: 256 bytes per pass in flight.
+ *   counters                a merged pass whose device result is taken leaves adsb_selftest_rx_seam_counters' records,
+ *                           dropped and redone where they were: the host neither merges nor replays its seam records
+ *                           ([0], passes with a seam step, counts it as before).
+ * Test hooks (results never depend on them).  counters, out4: [0] passes with a device-side seam merge, [1] seam records
+ * merged on the device, [2] own hits dropped on the device for j < 326, [3] merged passes that declared themselves
+ * unscored (seam overflow, or more merged hits than the score arrays hold).  Counted at collect for every pass whose merge
+ * ran, also one whose device result is then refused or disowned.  adsb_selftest_reservations: how many
+ * reservations (device blocks, pinned blocks, events) the context's owner holds now. */
+int adsb_set_receiver_carry_scoring(adsb_ctx *ctx, int enabled);
+int adsb_get_receiver_carry_scoring(const adsb_ctx *ctx);
+int adsb_selftest_rx_seam_score_counters(const adsb_ctx *ctx, uint64_t *out4);
+uint64_t adsb_selftest_reservations(const adsb_ctx *ctx);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Decimation -- IQ sampled at an integer multiple of 2.4 MS/s.  Every entry point above takes IQ at exactly 2.4 MS/s;
  * a HackRF, bladeRF, USRP or Airspy runs at 4.8, 9.6, 12, 19.2 or 24 MS/s.  An adsb_decim is a stateful, exact-integer
  * FIR decimator by an integer factor D that runs on the device in front of the scan, in a kernel of its own: its output

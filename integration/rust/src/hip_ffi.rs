@@ -255,6 +255,11 @@ unsafe extern "C" {
     pub fn adsb_receiver_carry_reset(ctx: *mut AdsbCtx, receiver: u32) -> c_int;
     pub fn adsb_selftest_rx_seam_tune(ctx: *mut AdsbCtx, list_cap: u32) -> c_int;
     pub fn adsb_selftest_rx_seam_counters(ctx: *const AdsbCtx, out4: *mut u64) -> c_int;
+    // ... receiver seams AND scoring on the device, as one mode (opt-in), and its test hooks
+    pub fn adsb_set_receiver_carry_scoring(ctx: *mut AdsbCtx, enabled: c_int) -> c_int;
+    pub fn adsb_get_receiver_carry_scoring(ctx: *const AdsbCtx) -> c_int;
+    pub fn adsb_selftest_rx_seam_score_counters(ctx: *const AdsbCtx, out4: *mut u64) -> c_int;
+    pub fn adsb_selftest_reservations(ctx: *const AdsbCtx) -> u64;
     pub fn adsb_shard_scan(ctx: *mut AdsbCtx, device_iq: *const c_void, n_samples: usize, addrs_out: *mut u32, cap: usize, n_addrs: *mut usize) -> c_int;
     pub fn adsb_shard_finish(ctx: *mut AdsbCtx, extra_addrs: *const u32, n_extra: usize, records_out: *mut AdsbTrial, cap: usize, n_records: *mut usize) -> c_int;
     pub fn adsb_multi_create(out: *mut *mut AdsbMulti, devices: *const c_int, n_devices: c_int, max_chunks_per_device: usize) -> c_int;
