@@ -26,8 +26,22 @@ bool adds_have_room(adsb_ctx *c, size_t na)
     return held + na + 64 < IcaoFilter::kSize;
 }
 
+// the distinct values among receiver r's additions of the pass
+size_t distinct_adds_rx(adsb_ctx *c, const Slot &sl, size_t na, uint32_t r)
+{
+    std::vector<uint32_t> &v = c->rx_add_values;
+    v.clear();
+    for (size_t i = 0; i < na; i++)
+        if (sl.h_add_rx[i] == r) v.push_back(sl.h_adds[i]);
+    std::sort(v.begin(), v.end());
+    return (size_t)(std::unique(v.begin(), v.end()) - v.begin());
+}
+
 // ... for EVERY receiver that has an addition in the pass (sl.h_add_rx: the receiver of each) -- held[r] + adds[r] + 64
-// < 4096, with held[r] kept from pass to pass and counted afresh whenever the host has touched the filters itself
+// < 4096, with held[r] kept from pass to pass and counted afresh whenever the host has touched the filters itself.  The
+// list has one entry per add() CALL (a DF18 whose plain address is unknown re-adds address | NT on every frame and
+// phase), the table one per distinct value: a receiver whose calls alone would not fit has its distinct values counted
+// (as adsb_multi.cpp's fits() does), so that a long pass of few receivers is not refused for its repetitions.
 bool adds_have_room_rx(adsb_ctx *c, const Slot &sl, size_t na)
 {
     if (!c->rx_held_valid) {
@@ -45,7 +59,8 @@ bool adds_have_room_rx(adsb_ctx *c, const Slot &sl, size_t na)
         else if (c->rx_pass_adds[r]++ == 0) c->rx_touched.push_back(r);
     }
     for (uint32_t r : c->rx_touched) {
-        room = room && (size_t)c->rx_held[r] + c->rx_pass_adds[r] + 64 < IcaoFilter::kSize;
+        if (room && (size_t)c->rx_held[r] + c->rx_pass_adds[r] + 64 >= IcaoFilter::kSize)
+            room = (size_t)c->rx_held[r] + distinct_adds_rx(c, sl, na, r) + 64 < IcaoFilter::kSize;
         c->rx_pass_adds[r] = 0;
     }
     return room;

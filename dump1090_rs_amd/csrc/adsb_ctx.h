@@ -397,6 +397,7 @@ struct adsb_ctx {
     // addresses each receiver's filter holds (counted afresh when !rx_held_valid: the host replayed a pass; kept in step by the
     // flushes and by the additions of the results taken) / additions of the pass being looked at, and the receivers that have any
     std::vector<uint32_t> rx_held, rx_pass_adds, rx_touched;
+    std::vector<uint32_t> rx_add_values;   // one receiver's additions of that pass, where its distinct values have to be counted
     bool rx_held_valid = false;
     uint64_t rx_scored_taken = 0, rx_scored_refused = 0, rx_set_rebuilds = 0, rx_no_room = 0;   // adsb_selftest_rx_score_counters
     // Receiver seams (adsb_set_receiver_carry; include/adsb_hip.h, "Receiver seams"; adsb_seam.cpp): carry-over with
